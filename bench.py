@@ -205,6 +205,61 @@ def load_json_newest(pattern, pred=lambda d: True):
     return None
 
 
+# ---- --dump-outputs: what the timed path returns to its caller, for output-by-output comparison of two builds ----------
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 0x4455
+
+
+def _columns(rec):
+    """structured records -> [n, fields] float64 (u32 / i32 ids and f32 / f64 values are all exact in float64)"""
+    return np.concatenate([rec[f].reshape(len(rec), int(np.prod(rec.dtype[f].shape))).astype(np.float64)
+                           for f in rec.dtype.names], 1)
+
+
+def collect_outputs(l3d, scene):
+    """the arrays a caller of matchImages + computeAffinity receives from the context, as float64 arrays: the surviving
+    matches of every view (matches_, with the CSR offsets over each view's segments), the best hypotheses
+    (estimated_position3D_) and the affinity matrix (A_, local2global_, med_scene_depth_lines_)"""
+    ms, offs = [], []
+    for v in scene.views:
+        m, off = l3d.matches(v.cam)
+        ms.append(_columns(m)); offs.append(off.astype(np.float64))
+    s2, s3, bm = l3d.best()
+    edges, l2g, msdl = l3d.affinity()
+    return {"matches": np.concatenate(ms), "match_offsets": np.concatenate(offs),
+            "best_segment2d": _columns(s2), "best_segment3d": _columns(s3), "best_match": _columns(bm),
+            "affinity_edges": _columns(edges), "affinity_rows": _columns(l2g),
+            "affinity_median_depth": np.array([msdl], np.float64)}
+
+
+def write_outputs(arrays, out_dir):
+    """DIR/<name>.npy for every array; above DUMP_LIMIT_BYTES in all, the arrays of more than 1 MB keep a fixed seeded
+    sample of their rows (in order), and DIR/<name>_rows.npy says which"""
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    big = {k for k, a in arrays.items() if a.nbytes > (1 << 20)}
+    header = 4096                    # room for the .npy headers (128 B per file)
+    keep = 1.0
+    if total + header > DUMP_LIMIT_BYTES:
+        small = total - sum(arrays[k].nbytes for k in big)
+        # (the row-index files of the sampled arrays count against the limit too)
+        keep = (DUMP_LIMIT_BYTES - header - small) / sum(arrays[k].nbytes + 8 * len(arrays[k]) for k in big)
+    written = 0
+    for k, a in arrays.items():
+        if k in big and keep < 1.0:
+            n = int(len(a) * keep)
+            rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(len(a), n, replace=False))
+            a = a[rows]
+            path = os.path.join(out_dir, f"{k}_rows.npy")
+            np.save(path, rows.astype(np.float64))
+            written += os.path.getsize(path)
+        path = os.path.join(out_dir, f"{k}.npy")
+        np.save(path, a)
+        written += os.path.getsize(path)
+    assert written <= DUMP_LIMIT_BYTES, written
+    return {"dir": out_dir, "arrays": sorted(arrays), "bytes": written, "sampled": sorted(big) if keep < 1.0 else []}
+
+
 def multi_gpu_model(pairs, M, kNN, phase, lists_ms, record_bytes, tail_bytes=0.0, sim_bytes=0.0):
     """What the halo form of the multi-GPU call (line3dpp_amd/dist.py) is expected to take on N GPUs of one node, term by
     term, from THIS run's single-GPU phase times and the plan the N ranks would follow (l3d_plan_shards): no multi-GPU
@@ -434,7 +489,12 @@ def main():
     ap.add_argument("--launcher-selftest", action="store_true",
                     help="start the ranks as --gpus N would, over gloo on the CPU, report them and exit (no GPU work): the "
                          "CPU test of the launcher")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps write what the last of them computed (matches, best hypotheses, affinity) "
+                         "as DIR/<name>.npy, float64, at most 64 MB in all")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # ---- one process per GPU.  Under torchrun / torch.distributed.run (WORLD_SIZE set) this process IS a rank; started
     # plainly with --gpus N > 1 it starts the N ranks itself -- `python bench.py --gpus 8` must never run one rank and
@@ -571,6 +631,8 @@ def main():
         kern_ms += tm_raw.match_kernel_ms; kern_launches += tm_raw.match_kernel_launches
     barrier()
     dt = time.perf_counter() - t0
+    # (every rank ends a step with the complete result: rank 0 writes it)
+    dumped = write_outputs(collect_outputs(l3d, scene), args.dump_outputs) if args.dump_outputs and rank == 0 else None
     l3d.setTimingLevel(2)
     phase_steps = max(1, min(args.steps, 5))
     for _ in range(phase_steps):
@@ -751,6 +813,8 @@ def main():
         }
         if extra_line is not None:
             out["baseline_8gpu_config_line"] = extra_line
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         # (not in the profiling / A-B invocations, which all pass --no-cpu-baseline: a second configuration in the process would
         # mix its kernels into their per-kernel summaries)
         if world == 1 and args.config == "C1" and not args.no_extra_lines and not args.no_cpu_baseline:

@@ -1,8 +1,9 @@
 """The BIN result format of Line3D::save3DLinesAsBIN (line3D.cc:2690-2711): boost::archive::binary_oarchive of
 std::vector<FinalLine3D>, read and written without Boost (line3dpp_amd/io.py; the library's own writer is
 l3d_save_3d_lines_bin).  Pinned on the reference's own fixtures testdata/Line3D++_ref/*vis_3.bin: parse -> re-serialise
-is byte-identical for both files (where /root/reference exists), and a committed excerpt (first 40 records) agrees
-with the TXT fixture of the same run to all six printed digits."""
+is byte-identical for both files (stored xz-compressed under tests/golden/ref_full/), and a committed excerpt (first 40
+records) agrees with the TXT fixture of the same run to all six printed digits."""
+import lzma
 import os
 
 import numpy as np
@@ -11,7 +12,8 @@ import pytest
 from line3dpp_amd import io
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
-REF_DIR = "/root/reference/testdata/Line3D++_ref"
+# the reference's fixtures testdata/Line3D++_ref/Line3D++__W_FULL__N_10__sigmaP_2.5__sigmaA_10__epiOverlap_0.25__<tag>.{bin,txt}
+FULL_DIR = os.path.join(GOLD, "ref_full")
 
 
 def test_excerpt_of_the_reference_fixture_parses_and_round_trips():
@@ -34,13 +36,16 @@ def test_excerpt_of_the_reference_fixture_parses_and_round_trips():
         assert L["reference_view"] in set(L["residuals"][:, 0].tolist())
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_DIR), reason="reference checkout not present")
 @pytest.mark.parametrize("tag", ["kNN_10__vis_3", "kNN_10__OPTIMIZED__vis_3"])
-def test_full_reference_fixtures_round_trip_byte_for_byte(tag):
-    path = os.path.join(REF_DIR, f"Line3D++__W_FULL__N_10__sigmaP_2.5__sigmaA_10__epiOverlap_0.25__{tag}.bin")
-    lines, version = io.read_3d_lines_bin(path)
-    assert io.format_3d_lines_bin(lines, version) == open(path, "rb").read()
-    txt = io.read_3d_lines_txt(path[:-4] + ".txt")
+def test_full_reference_fixtures_round_trip_byte_for_byte(tag, tmp_path):
+    paths = {}
+    for ext in ("bin", "txt"):
+        paths[ext] = str(tmp_path / f"{tag}.{ext}")
+        with lzma.open(os.path.join(FULL_DIR, f"{tag}.{ext}.xz")) as src, open(paths[ext], "wb") as dst:
+            dst.write(src.read())
+    lines, version = io.read_3d_lines_bin(paths["bin"])
+    assert io.format_3d_lines_bin(lines, version) == open(paths["bin"], "rb").read()
+    txt = io.read_3d_lines_txt(paths["txt"])
     assert len(lines) == len(txt) >= 2489
     for L, T in zip(lines, txt):
         assert np.array_equal(L["residuals"], T["residuals"])

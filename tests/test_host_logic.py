@@ -280,3 +280,27 @@ def test_multi_gpu_model_prices_the_sharded_tail_and_the_weak_reading():
     assert abs(w8["total_ms"] - sum(w8["terms_ms"].values())) < 1e-3 and 0.3 < w8["efficiency"] < 1.0
     assert abs(w8["throughput_over_1_gpu"] - 8 * w8["efficiency"]) < 0.05
     assert out["2"]["weak"]["efficiency"] > w8["efficiency"]
+
+
+def test_bench_dump_outputs_stays_within_its_limit_and_samples_reproducibly(tmp_path):
+    """bench.py --dump-outputs: float64 .npy files, at most 64 MB in all; an output too large keeps the same seeded sample
+    of its rows from run to run, and says which rows"""
+    b, _ = _bench_module()
+    from line3dpp_amd._lib import SEGMENT3D_DTYPE
+    s3 = np.zeros(3, SEGMENT3D_DTYPE); s3["P1"] = [[1, 2, 3]] * 3; s3["valid"] = 4294967295
+    cols = b._columns(s3)
+    assert cols.shape == (3, 11) and cols.dtype == np.float64 and cols[0, 0] == 1 and cols[0, 10] == 4294967295
+    assert b._columns(np.zeros(0, SEGMENT3D_DTYPE)).shape == (0, 11)
+    big = np.arange(9_000_000, dtype=np.float64).reshape(-1, 9)          # 72 MB
+    arrays = {"matches": big, "affinity_median_depth": np.array([2.5])}
+    r1, r2 = b.write_outputs(arrays, str(tmp_path / "a")), b.write_outputs(arrays, str(tmp_path / "b"))
+    assert r1["sampled"] == ["matches"] and r1["bytes"] == r2["bytes"]
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["affinity_median_depth.npy", "matches.npy", "matches_rows.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 << 20
+    rows = np.load(tmp_path / "a" / "matches_rows.npy").astype(np.int64)
+    m = np.load(tmp_path / "a" / "matches.npy")
+    assert m.dtype == np.float64 and len(rows) > 0.8 * len(big) and np.all(np.diff(rows) > 0)
+    assert np.array_equal(m, big[rows]) and np.array_equal(m, np.load(tmp_path / "b" / "matches.npy"))
+    small = b.write_outputs({"x": np.ones((4, 3))}, str(tmp_path / "c"))
+    assert small["sampled"] == [] and os.listdir(tmp_path / "c") == ["x.npy"]
