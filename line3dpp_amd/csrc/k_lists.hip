@@ -1332,15 +1332,12 @@ hipError_t launch_pair_csr(const PairDesc* pairs, uint32_t n_pairs, uint32_t max
     // The staged form (LDS cursors, 16-bit targets).  Stage size: room for the entries of the largest pair in ONE range (about
     // 0.6 of its slots hand an inverse match over) -- beside the cursors inside 78 KiB if that fits (two workgroups per CU: C1,
     // C3), else inside one workgroup's whole LDS (C2: 0.26 against 0.35 ms with two ranges at 78 KiB); pairs beyond that take
-    // several ranges (C4: 0.64 ms with 4 or with 27 of them).  L3D_CSR_STAGED=0: the direct form; L3D_CSR_STAGE_KB: the budget (A/B).
-    const char* st_env = std::getenv("L3D_CSR_STAGED");
-    if (tgt16 && !force_global && max_Mt <= lds_segs && !(st_env && std::atoi(st_env) == 0)) {
+    // several ranges (C4: 0.64 ms with 4 or with 27 of them).
+    if (tgt16 && !force_global && max_Mt <= lds_segs) {
         const size_t cur_bytes = ((size_t)lds_segs_round(max_Mt) + 64) * 4;
-        const char* kb_env = std::getenv("L3D_CSR_STAGE_KB");
         const size_t two = 78 * 1024, one = 156 * 1024 - 4096;
         const size_t want = (size_t)(0.6 * (double)max_pair_slots) * 4 + 4096;
-        size_t budget = cur_bytes + want <= two ? two : one;
-        if (kb_env) budget = std::min<size_t>(std::max<size_t>((size_t)std::atoi(kb_env) * 1024, cur_bytes + 4096), one);
+        const size_t budget = cur_bytes + want <= two ? two : one;
         size_t cap = (budget - cur_bytes) / 4;
         cap = std::min<size_t>(cap, (size_t)std::max<uint64_t>(max_pair_slots, 1024));   // (never more entries than slots)
         static const hipError_t attr2 = hipFuncSetAttribute((const void*)k_pair_csr<true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
@@ -1403,9 +1400,7 @@ hipError_t launch_lists(uint32_t v0, uint32_t nv, uint32_t max_M, const ViewDev*
                         SimConst sc, ListPools lp, uint32_t* seg_of_g, HugeScratchArgs hsa, hipStream_t st) {
     if (!nv || !max_M) return hipSuccess;
     // the one-wave tier stages 128 hypotheses (8 waves per SIMD) unless the scene's lists are long on average
-    // (L3D_LISTS_WIDE=0|1: A/B switch of the staging width, read per launch)
-    const char* wide_env = std::getenv("L3D_LISTS_WIDE");
-    const bool wide = wide_env ? std::atoi(wide_env) != 0 : hsa.mean_list > 96;
+    const bool wide = hsa.mean_list > 96;
 #define L3D_LISTS(B)                                                                                                       \
     do {                                                                                                                   \
         const size_t lds1 = ListCfg<1, B>::BYTES, lds2 = ListCfg<2, B>::BYTES, lds4 = ListCfg<4, B>::BYTES;                \

@@ -170,11 +170,11 @@ __device__ __forceinline__ void store_inverse_target(const OrientFuse& of, uint6
 // MODE 2: write every accepted match in ascending target order (kNN <= 0, pass 2)
 // BRUTE: skip the pre-filter (every pair goes through the exact test) -- on-GPU check that the
 //        pre-filter never loses a match.
-// WPG: waves per workgroup (1 or 2).  Both waves of a workgroup hold the SAME 64 source rows and share their top-K
-//      tables in LDS; wave q visits the target chunks with index = q (mod 2).  A work item is then half as long, which
-//      shortens the ramp-down tail of the launch (waves cannot migrate: at the end some SIMDs still hold a full set of
-//      long items while others are empty).  The waves meet at two barriers only (tables initialised / all candidates
-//      inserted); a row's table is guarded by a compare-and-swap lock in LDS.
+// WPG: waves per workgroup (1 or 2; 2 for the staged bounded-kNN variant only).  Both waves of a workgroup hold the SAME
+//      64 source rows and share their top-K tables in LDS; wave q visits the target chunks with index = q (mod 2).  A
+//      work item is then half as long, which shortens the ramp-down tail of the launch (waves cannot migrate: at the end
+//      some SIMDs still hold a full set of long items while others are empty).  The waves meet at two barriers only
+//      (tables initialised / all candidates inserted); a row's table is guarded by a compare-and-swap lock in LDS.
 // amdgpu_waves_per_eu: with two waves per work item the LDS tables leave room for 7 waves per SIMD; the kernel would
 // otherwise take 75 VGPRs (6 waves) -- held to 72 it spills one register and runs 5 % faster on C1 (0.718 against
 // 0.754 ms).  One wave per item (the large scenes) is limited to 6 per SIMD by its LDS (6.3 KiB per wave) whatever the
@@ -193,20 +193,10 @@ __device__ __forceinline__ void store_inverse_target(const OrientFuse& of, uint6
 //     The FIFO carries what is left over (< 64 / R records) to the next chunk, so sparse chunks cost no partial steps;
 //   * one ballot + one compaction per 64 lane-tests (two per 128 in the row form), no scalar bit scan, no record address
 //     arithmetic on the scalar unit.
-#ifndef L3D_MATCH_WAVES
-#define L3D_MATCH_WAVES (TILE ? L3D_TILE_WAVES : MODE == 1 ? 5 : (WPG == 2 ? 7 : 6))   // (MODE 1: the keep-all pass holds both ray records)
-#endif
-#ifndef L3D_ROW_CACHE
-#define L3D_ROW_CACHE 1   // 0: never stage the source rows' records in LDS (A/B)
-#endif
-#ifndef L3D_TILE_WAVES
-#define L3D_TILE_WAVES 6
-#endif
-#ifndef L3D_ROW_CLASSES_DEFAULT
-#define L3D_ROW_CLASSES_DEFAULT 1   // row form: padded class layout (1) or the legacy layout (0)
-#endif
-template <int MODE, bool BRUTE, bool IX16, int WPG, bool STAGED, int TILE = 0>
-__global__ __launch_bounds__(kBlock * WPG) __attribute__((amdgpu_waves_per_eu(L3D_MATCH_WAVES))) void k_match_pairs(const ViewDev* __restrict__ views,
+// waves per SIMD the registers are budgeted for (above; the tile form: 6; MODE 1: 5, the keep-all pass holds both ray records)
+constexpr int match_waves_per_eu(int mode, int wpg, int tile) { return tile ? 6 : mode == 1 ? 5 : (wpg == 2 ? 7 : 6); }
+template <int MODE, bool BRUTE, bool IX16, int WPG, int TILE = 0>
+__global__ __launch_bounds__(kBlock * WPG) __attribute__((amdgpu_waves_per_eu(match_waves_per_eu(MODE, WPG, TILE)))) void k_match_pairs(const ViewDev* __restrict__ views,
                                                            const PairDesc* __restrict__ pairs,
                                                            const WorkItem* __restrict__ work, uint32_t nwork,
                                                            Slot* __restrict__ slots,
@@ -236,7 +226,8 @@ __global__ __launch_bounds__(kBlock * WPG) __attribute__((amdgpu_waves_per_eu(L3
     const uint32_t K = pd.K, Ms = pd.Ms, Mt = pd.Mt;
     const bool fastm = (pd.flags & kPairFastMath) != 0;     // l3d_dev.h: IEEE division / sqrt without operand scaling
     typedef typename IdxT<IX16>::type idx_t;
-    static_assert(!STAGED || (MODE == 0 && !BRUTE), "the two-stage candidate pipeline exists for the bounded-kNN variant");
+    constexpr bool STAGED = MODE == 0 && !BRUTE;   // the two-stage candidate pipeline (the other variants drain one stage)
+    static_assert(WPG == 1 || STAGED, "two waves per item: the staged bounded-kNN kernel only");
     static_assert(TILE == 0 || (TILE == 16 && STAGED && WPG == 1), "the tile form: bounded kNN, staged, one wave per item");
     constexpr uint32_t ROWS = TILE ? (uint32_t)TILE : (uint32_t)kBlock;   // rows of a work item
     constexpr uint32_t TPS = 64u / ROWS;                                  // targets per step of the tile form's walk
@@ -245,7 +236,7 @@ __global__ __launch_bounds__(kBlock * WPG) __attribute__((amdgpu_waves_per_eu(L3
     // work item instead of being gathered from the view's arrays by every candidate
     // (C1: kernel 0.601 -> 0.585 ms; not for launches that do not fill the machine -- C0 0.179 -> 0.182: the launcher sets
     // CullPools::row_cache by the number of work items; profiles/r05_ab_match_forms.txt)
-    constexpr bool ROWCACHE_BUILT = L3D_ROW_CACHE != 0 && STAGED && WPG == 2 && TILE == 0;
+    constexpr bool ROWCACHE_BUILT = WPG == 2;   // (staged, row form)
     const bool ROWCACHE = ROWCACHE_BUILT && cp.row_cache != 0;
     Lds<IX16> L = carve<IX16>((L3D_LDS char*)smem, MODE == 0 ? K : 0, WPG, STAGED, ROWS, TILE != 0, ROWCACHE);
     // wave of the workgroup -- through readfirstlane: the compiler must know it is wave-uniform, or the chunk loop
@@ -548,25 +539,12 @@ __global__ __launch_bounds__(kBlock * WPG) __attribute__((amdgpu_waves_per_eu(L3
             }
         }
         // several candidates of one drain may belong to the same row: one at a time, lowest lane first (without
-        // culling a row therefore sees its candidates in ascending target order, which MODE 2 relies on)
-        // With several waves per row group the row's table is a critical section: compare-and-swap lock (a wave's
-        // own contenders are serialised by the LDS atomic unit just the same), released after the update.
+        // culling a row therefore sees its candidates in ascending target order, which MODE 2 relies on).  One wave per
+        // item here (the single-stage variants), so the row's table needs no lock across waves.
         while (L3D_BALLOT(pending)) {
-            bool win;
-            if (WPG > 1) {
-                win = false;
-                if (pending) {
-                    uint32_t expect = kEmpty;
-                    win = __hip_atomic_compare_exchange_strong((L3D_LDS uint32_t*)&L.claim[sl], &expect, threadIdx.x,
-                                                               __ATOMIC_ACQUIRE, __ATOMIC_RELAXED,
-                                                               __HIP_MEMORY_SCOPE_WORKGROUP);
-                }
-            } else {
-                if (pending) __hip_atomic_fetch_min((L3D_LDS uint32_t*)&L.claim[sl], lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                win = pending && (L.claim[sl] == lane);
-            }
-            if (win) {
-                if (WPG == 1) L.claim[sl] = kEmpty;
+            if (pending) __hip_atomic_fetch_min((L3D_LDS uint32_t*)&L.claim[sl], lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            if (pending && L.claim[sl] == lane) {
+                L.claim[sl] = kEmpty;
                 pending = false;
                 const uint32_t c = L.cnt[sl];
                 if (MODE == 1) {
@@ -606,9 +584,6 @@ __global__ __launch_bounds__(kBlock * WPG) __attribute__((amdgpu_waves_per_eu(L3
                         }
                     }
                 }
-                if (WPG > 1)
-                    __hip_atomic_store((L3D_LDS uint32_t*)&L.claim[sl], kEmpty, __ATOMIC_RELEASE,
-                                       __HIP_MEMORY_SCOPE_WORKGROUP);
             }
         }
         // feed the K-th best overlap back into the owning lane's pre-filter threshold
@@ -993,19 +968,14 @@ __global__ __launch_bounds__(kBlock * WPG) __attribute__((amdgpu_waves_per_eu(L3
 #endif
 }
 
-// the two-stage candidate pipeline (default) or the single-stage one of round 2 (L3D_MATCH_STAGED=0: A/B switch; the
-// brute-force test hook always takes the single-stage path, so the two check each other)
-bool match_staged(int mode, bool brute) {
-    static const bool off = [] { const char* e = std::getenv("L3D_MATCH_STAGED"); return e && std::atoi(e) == 0; }();
-    return mode == 0 && !brute && !off;
-}
+// The bounded-kNN launch (mode 0, !brute) takes the two-stage candidate pipeline; the brute-force test hook and the keep-all
+// passes drain one stage, so the hook cross-checks the staged kernel.  Two waves per item imply the staged kernel.
 bool match_row_cache(int mode, bool brute, uint32_t nwork, uint32_t tile_rows) {
-    return L3D_ROW_CACHE != 0 && match_staged(mode, brute) && !tile_rows && match_waves_per_group(mode, brute, nwork) == 2 &&
-           nwork > kMatchOrderMinItems;
+    return !tile_rows && match_waves_per_group(mode, brute, nwork) == 2 && nwork > kMatchOrderMinItems;
 }
 size_t match_lds_bytes(int mode, uint32_t K, bool ix16, uint32_t waves, bool brute, uint32_t tile_rows, bool row_cache) {
     const size_t ib = ix16 ? 2 : 4;
-    const bool staged = match_staged(mode, brute);
+    const bool staged = mode == 0 && !brute;
     if (tile_rows)   // (one wave per item: FIFO + the two rings + the tables of R rows)
         return (size_t)kFifo * (sizeof(v4f) + 4) + (size_t)(ring_entries(true, 1) + kRing2) * 4 + 2 * (size_t)tile_rows * 4 +
                2 * (size_t)tile_rows * ib + (size_t)tile_rows * K * (4 + ib);
@@ -1015,11 +985,11 @@ size_t match_lds_bytes(int mode, uint32_t K, bool ix16, uint32_t waves, bool bru
 }
 
 // The tile form serves the bounded-kNN launches of the two-stage pipeline (everything else -- keep-all passes, the
-// brute-force hook, the single-stage A/B switch -- keeps the row form) whose row form would leave the machine half empty:
+// brute-force hook -- keeps the row form) whose row form would leave the machine half empty:
 // up to kMatchTileMaxItems items of 64 rows (est_row_items: what the caller expects the launch to hold).  L3D_MATCH_TILE = 0 | 16
 // overrides.
 uint32_t match_tile_rows(int mode, bool brute, uint64_t est_row_items) {
-    if (!match_staged(mode, brute)) return 0;
+    if (mode != 0 || brute) return 0;
     // (read per call -- once per l3d_match_begin --, not latched: a test switches forms inside one process)
     const char* e = std::getenv("L3D_MATCH_TILE");
     const int forced = e ? std::atoi(e) : -1;
@@ -1028,11 +998,7 @@ uint32_t match_tile_rows(int mode, bool brute, uint64_t est_row_items) {
 }
 uint32_t match_layout_rows(int mode, bool brute, uint32_t tile_rows) {
     if (mode != 0 || brute) return 0;
-    const uint32_t t = tile_rows;
-    if (t) return t;
-    const char* e = std::getenv("L3D_MATCH_CLASSES");
-    const int classes = e ? std::atoi(e) : L3D_ROW_CLASSES_DEFAULT;
-    return classes ? (uint32_t)kMatchRows : 0u;
+    return tile_rows ? tile_rows : (uint32_t)kMatchRows;
 }
 
 // Two waves per work item pay off while the launch has few items for the machine (C0: kernel 0.34 -> 0.24 ms, C1 with
@@ -1041,8 +1007,6 @@ uint32_t match_layout_rows(int mode, bool brute, uint32_t tile_rows) {
 // feedback arrives later and more candidates reach the exact test).
 uint32_t match_waves_per_group(int mode, bool brute, uint32_t nwork) {
     if (mode != 0 || brute) return 1;   // keep-all rows need ascending target order; the brute path is a test hook
-    static const int forced = [] { const char* e = std::getenv("L3D_MATCH_WPG"); return e ? std::atoi(e) : 0; }();
-    if (forced == 1 || forced == 2) return (uint32_t)forced;
     return nwork <= kMatchOrderMaxItems ? 2u : 1u;
 }
 
@@ -1055,29 +1019,27 @@ hipError_t launch_match_pairs(int mode, bool brute, const ViewDev* views, const 
     const uint32_t grid = ((nwork + 7) / 8) * 8;
     if (!(mode == 0 && !brute)) ix16 = false;       // the compact layout is only instantiated for the hot variant
     if (tile_rows && tile_rows != 16u) return hipErrorInvalidValue;
-    if (tile_rows && !match_staged(mode, brute)) return hipErrorInvalidValue;   // (the tile form exists for the staged bounded-kNN kernel)
+    if (tile_rows && (mode != 0 || brute)) return hipErrorInvalidValue;   // (the tile form exists for the staged bounded-kNN kernel)
     const uint32_t wpg = tile_rows ? 1u : match_waves_per_group(mode, brute, nwork);
     pools.row_cache = match_row_cache(mode, brute, nwork, tile_rows) ? 1u : 0u;
     const size_t lds = match_lds_bytes(mode, maxK, ix16, wpg, brute, tile_rows, pools.row_cache != 0);
-#define L3D_LAUNCH(M, B, X, W, S, T)                                                                          \
+#define L3D_LAUNCH(M, B, X, W, T)                                                                             \
     do {                                                                                                      \
-        hipError_t e = hipFuncSetAttribute((const void*)k_match_pairs<M, B, X, W, S, T>,                      \
+        hipError_t e = hipFuncSetAttribute((const void*)k_match_pairs<M, B, X, W, T>,                         \
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);             \
         if (e != hipSuccess) return e;                                                                        \
-        hipLaunchKernelGGL((k_match_pairs<M, B, X, W, S, T>), dim3(grid), dim3(kBlock * W), lds, stream, views, \
+        hipLaunchKernelGGL((k_match_pairs<M, B, X, W, T>), dim3(grid), dim3(kBlock * W), lds, stream, views,  \
                            pairs, work, nwork, slots, row_counts, thr, pools, of);                            \
     } while (0)
-#define L3D_LAUNCH_HOT(X, W) do { if (match_staged(mode, brute)) L3D_LAUNCH(0, false, X, W, true, 0); else L3D_LAUNCH(0, false, X, W, false, 0); } while (0)
     if (mode == 0 && tile_rows) {
-        if (ix16) L3D_LAUNCH(0, false, true, 1, true, 16); else L3D_LAUNCH(0, false, false, 1, true, 16);
+        if (ix16) L3D_LAUNCH(0, false, true, 1, 16); else L3D_LAUNCH(0, false, false, 1, 16);
     } else if (mode == 0) {
-        if (brute) L3D_LAUNCH(0, true, false, 1, false, 0);
-        else if (ix16) { if (wpg == 2) L3D_LAUNCH_HOT(true, 2); else L3D_LAUNCH_HOT(true, 1); }
-        else { if (wpg == 2) L3D_LAUNCH_HOT(false, 2); else L3D_LAUNCH_HOT(false, 1); }
+        if (brute) L3D_LAUNCH(0, true, false, 1, 0);
+        else if (ix16) { if (wpg == 2) L3D_LAUNCH(0, false, true, 2, 0); else L3D_LAUNCH(0, false, true, 1, 0); }
+        else { if (wpg == 2) L3D_LAUNCH(0, false, false, 2, 0); else L3D_LAUNCH(0, false, false, 1, 0); }
     }
-    else if (mode == 1) { if (brute) L3D_LAUNCH(1, true, false, 1, false, 0); else L3D_LAUNCH(1, false, false, 1, false, 0); }
-    else { if (brute) L3D_LAUNCH(2, true, false, 1, false, 0); else L3D_LAUNCH(2, false, false, 1, false, 0); }
-#undef L3D_LAUNCH_HOT
+    else if (mode == 1) { if (brute) L3D_LAUNCH(1, true, false, 1, 0); else L3D_LAUNCH(1, false, false, 1, 0); }
+    else { if (brute) L3D_LAUNCH(2, true, false, 1, 0); else L3D_LAUNCH(2, false, false, 1, 0); }
 #undef L3D_LAUNCH
     return hipGetLastError();
 }

@@ -32,7 +32,7 @@ constexpr uint64_t kMatchTileMaxItems = 2048;     // launches of up to this many
                                                   // kernel -7 %; C1's 10 560 and C3's 81 920 lose 20 % in it)
 uint32_t match_tile_rows(int mode, bool brute, uint64_t est_row_items);   // 0: row form; 16: tile form (L3D_MATCH_TILE overrides)
 uint32_t match_layout_rows(int mode, bool brute, uint32_t tile_rows); // rows per work item of the padded class layout: the tile form's R, 64 for the
-                                                  // row form (L3D_MATCH_CLASSES=0: 0 = its legacy layout without padding)
+                                                  // row form, 0 for the keep-all passes and the brute-force hook (legacy layout)
 struct WorkItem {
     uint32_t pair;  // index into the pair array
     uint32_t src0;  // first source row (position in the pair's row order) of the work item
