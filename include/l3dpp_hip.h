@@ -298,7 +298,14 @@ int l3d_compute_affinity(l3d_ctx*);
  * filterTinySegments, untranslate().  perform_diffusion != 0 runs the replicator-dynamics diffusion of A_
  * (performRDD, line3D.cc:2026-2076) on the device-resident matrix; collinearity_t > 0 adds the per-image collinearity
  * tests (View::findCollinearSegments, view.cc:150-258) and the collinear affinity links (line3D.cc:1904-1974).
- * use_CERES is reported and ignored like in a reference build without Ceres (line3D.cc:1741-1743).
+ * use_CERES != 0 bundles the 3D lines between the clustering and the final 3D segments (optimizeClusters,
+ * line3D.cc:1800-1805; LineOptimizer::optimize, optimization.cc): per line, the reference's robust reprojection cost
+ * (Huber(2) on the squared 2-vector of end point distances, angle weighted) over its 4 Cayley parameters, cameras and
+ * intrinsics constant, minimised by Levenberg-Marquardt with at most max_iter_CERES iterations -- one kernel launch for
+ * all lines (k_lineopt.hip).  The reference solves all lines as one Ceres problem with one trust region and one
+ * stopping test, so the per-line iterates and stopping points are not the reference's: what is kept is the cost
+ * function and a per-line local optimum of it.  The output file names then carry "OPTIMIZED__" (line3D.cc:2889-2890);
+ * l3d_line_opt_stats reports the stage.  use_CERES = 0 leaves the path exactly as it was.
  * The clustering / reconstruction tail is small sequential host work in the reference and runs on the host
  * here as well. */
 int l3d_reconstruct_3d_lines(l3d_ctx*, uint32_t visibility_t, int perform_diffusion, float collinearity_t,
@@ -308,6 +315,22 @@ int l3d_reconstruct_3d_lines(l3d_ctx*, uint32_t visibility_t, int perform_diffus
  * [res_offsets[i], res_offsets[i+1]) (underlyingCluster_.residuals_); cluster_lines[i] is
  * underlyingCluster_.seg3D_, reference_views[i] its reference_view_.  Original (untranslated) frame. */
 int l3d_num_3d_lines(l3d_ctx*, uint32_t* n_lines, uint32_t* n_segments, uint32_t* n_residuals);
+/* what the line bundling of the last reconstruct3Dlines did (all zero when it ran with use_CERES = 0) */
+typedef struct l3d_line_opt_summary {
+    uint32_t lines_bundled;   /* clusters whose parameters were optimised */
+    uint32_t lines_constant;  /* clusters held constant: a NaN in their Cayley form (the reference's #unoptimizable_lines) */
+    uint32_t lines_dropped;   /* clusters dropped at write-back (|P1 - P2| <= 1e-12) */
+    uint32_t stop_gradient, stop_function, stop_parameter, stop_max_iter;   /* bundled lines stopped by each rule */
+    uint32_t stop_other;      /* ... by a failed evaluation at the start or a collapsed trust region */
+    uint32_t max_iterations;  /* largest iteration count of a line */
+    uint32_t residuals;       /* residual 2D segments of all clusters */
+    uint32_t lines_wide;      /* bundled lines with more than 16 residuals (one wave each; the rest: 16 lanes each) */
+    uint32_t max_residuals;   /* largest residual count of a bundled line */
+    double cost_before, cost_after;   /* sum of the bundled lines' robust costs at the start / at the end */
+    float kernel_ms;          /* the bundling kernel (one event pair; only at timing level >= 2, else 0) */
+    uint32_t reserved;
+} l3d_line_opt_summary;
+int l3d_line_opt_stats(l3d_ctx*, l3d_line_opt_summary* out);
 int l3d_get_3d_lines(l3d_ctx*, uint32_t* seg_offsets, l3d_segment3d* segments, uint32_t* res_offsets,
                      l3d_segment2d* residuals, l3d_segment3d* cluster_lines, uint32_t* reference_views);
 
@@ -343,6 +366,18 @@ int l3d_get_sparse_matrix(l3d_ctx*, int sort_by_row, l3d_float4* entries, int32_
 /* test hook (host only): principal direction of a row-major symmetric 3x3 scatter matrix as Line3D::get3DlineFromCluster
  * (line3D.cc:2196-2211) takes it from JacobiSVD -- this library's closed-form solver, checked against LAPACK on the CPU */
 int l3d_principal_direction(const double S9[9], double dir3[3]);
+/* test hooks (host only) of the line bundling: LineOptimizer::optimize's parametrisation of the line through P1, P2
+ * (Plücker, then Cayley: x = (omega, s), optimization.cc:31-95; returns 1 when the line is held constant, x = (-1,0,0,0))
+ * and its write-back (optimization.cc:209-295: new end points from x around the old mid point; returns 0 when the
+ * cluster is dropped) */
+int l3d_line_to_cayley(const double P1[3], const double P2[3], double x[4]);
+int l3d_cayley_to_segment(const double x[4], const double P1_old[3], const double P2_old[3], double P1[3], double P2[3]);
+/* test hook (device): the bundling kernel's own evaluator of LineReprojectionError (optimization.h) at line parameters
+ * x for n observations: obs [n x 6] = (p1x, p1y, p2x, p2y, nx, ny) (end points, normal of the segment's direction),
+ * cams [n x 16] = (R row-major, C, fx, fy, px, py).  residuals [2n]; jacobians [8n]: d r / d x, 2x4 row-major per
+ * observation, before the loss; ok [n]: 0 where the evaluation fails (residual 0); *cost = 1/2 sum Huber2(|r_i|^2) */
+int l3d_line_opt_eval(int device, uint32_t n, const double x[4], const double* obs, const double* cams, double* cost,
+                      double* residuals, double* jacobians, int32_t* ok);
 
 /* test hook (device): the unscaled IEEE division / square root of the exact tests (l3d_dev.h: rcp_refined, div_by,
  * sqrt_unscaled) against the compiler's own expansions on n random operand sets; counts[3] = results whose bits differ

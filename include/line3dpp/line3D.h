@@ -100,14 +100,20 @@ public:
 
     // void Line3D::reconstruct3Dlines(...), line3D.h:162-166: affinity matrix, graph clustering, 3D line per
     // cluster, collinear 3D segments; perform_diffusion runs the replicator-dynamics diffusion (performRDD) on the
-    // GPU like a CUDA build of the reference; no Ceres (like a reference build without it)
+    // GPU like a CUDA build of the reference; use_CERES bundles the 3D lines (optimizeClusters) on the GPU, one
+    // Levenberg-Marquardt solve per line of the reference's cost (include/l3dpp_hip.h).  use_CERES defaults to false
+    // as in a reference build without Ceres (a build with Ceres defaults to true, commons.h:84)
     void reconstruct3Dlines(const unsigned int visibility_t = 3, const bool perform_diffusion = false,
                             const float collinearity_t = -1.0f, const bool use_CERES = false,
                             const unsigned int max_iter_CERES = 250) {
         std::cout << std::endl << prefix_ << "[3] RECONSTRUCTION ===============================" << std::endl;
-        if (use_CERES) std::cout << prefix_err_ << "CERES was not found! no optimization will be performed..." << std::endl;
         const int rc = l3d_reconstruct_3d_lines(ctx_, visibility_t, perform_diffusion, collinearity_t, use_CERES, max_iter_CERES);
-        if (rc != L3D_OK) std::cout << prefix_err_ << l3d_last_error() << std::endl;
+        if (rc != L3D_OK) { std::cout << prefix_err_ << l3d_last_error() << std::endl; return; }
+        if (use_CERES) {   // optimization.cc:190
+            l3d_line_opt_summary st{};
+            l3d_line_opt_stats(ctx_, &st);
+            std::cout << prefix_ << "#unoptimizable_lines = " << st.lines_constant << std::endl;
+        }
     }
 
     // void Line3D::get3Dlines(std::vector<FinalLine3D>&), line3D.h:173.  FinalLine3D / LineCluster3D with the reference's member

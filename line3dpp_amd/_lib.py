@@ -53,6 +53,15 @@ class Timings(C.Structure):
                 ("slots_lo", C.c_uint32), ("slots_hi", C.c_uint32)]
 
 
+class LineOptStats(C.Structure):
+    """l3d_line_opt_summary (include/l3dpp_hip.h)"""
+    _fields_ = [("lines_bundled", C.c_uint32), ("lines_constant", C.c_uint32), ("lines_dropped", C.c_uint32),
+                ("stop_gradient", C.c_uint32), ("stop_function", C.c_uint32), ("stop_parameter", C.c_uint32),
+                ("stop_max_iter", C.c_uint32), ("stop_other", C.c_uint32), ("max_iterations", C.c_uint32),
+                ("residuals", C.c_uint32), ("lines_wide", C.c_uint32), ("max_residuals", C.c_uint32),
+                ("cost_before", C.c_double), ("cost_after", C.c_double), ("kernel_ms", C.c_float), ("reserved", C.c_uint32)]
+
+
 EXPORTS = [
     "l3d_last_error", "l3d_build_info", "l3d_create", "l3d_destroy", "l3d_add_view", "l3d_match_images",
     "l3d_match_begin", "l3d_num_pairs", "l3d_get_pairs", "l3d_match_pairs", "l3d_slot_buffer", "l3d_match_finish",
@@ -70,6 +79,7 @@ EXPORTS = [
     "l3d_trim_cache", "l3d_set_timing_level", "l3d_tail_shard_count", "l3d_tail_shard_layout", "l3d_tail_shard_commit",
     "l3d_sfm_open_colmap", "l3d_sfm_open_bundler", "l3d_sfm_num_images", "l3d_sfm_get_image", "l3d_sfm_get_worldpoints",
     "l3d_sfm_close", "l3d_debug_counter", "l3d_affinity_shard_begin", "l3d_affinity_shard_finish", "l3d_affinity_shard_abort", "l3d_shard_options",
+    "l3d_line_opt_stats", "l3d_line_to_cayley", "l3d_cayley_to_segment", "l3d_line_opt_eval",
 ]
 
 _lib = None
@@ -161,6 +171,10 @@ def load():
     L.l3d_get_segment_coords2d.argtypes = [vp, u32, u32, vp]
     L.l3d_find_collinear_segments.argtypes = [i32, vp, u32, f32, vp, vp, u64, vp]
     L.l3d_principal_direction.argtypes = [vp, vp]
+    L.l3d_line_opt_stats.argtypes = [vp, C.POINTER(LineOptStats)]
+    L.l3d_line_to_cayley.argtypes = [vp, vp, vp]
+    L.l3d_cayley_to_segment.argtypes = [vp, vp, vp, vp, vp]
+    L.l3d_line_opt_eval.argtypes = [i32, u32, vp, vp, vp, vp, vp, vp, vp]
     L.l3d_selftest_arith.argtypes = [i32, u64, u64, vp]
     L.l3d_score_matches.argtypes = [i32, vp, u32, vp, vp, vp, u32, vp, vp, f32, f32, vp]
     for name in EXPORTS:

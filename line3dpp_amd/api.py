@@ -188,11 +188,21 @@ class Line3D:
     # Line3D::reconstruct3Dlines, line3D.h:162-166 (defaults commons.h:63-70)
     def reconstruct3Dlines(self, visibility_t=L3D_DEF_MIN_VISIBILITY_T, perform_diffusion=False, collinearity_t=-1.0,
                            use_CERES=False, max_iter_CERES=250):
-        if use_CERES:           # line3D.cc:1741-1743
-            print(f"{self.PREFIX}ERROR: CERES was not found! no optimization will be performed...")
-        return self._check(self.L.l3d_reconstruct_3d_lines(self.h, int(visibility_t), int(perform_diffusion),
-                                                           float(collinearity_t), int(use_CERES), int(max_iter_CERES)),
-                           "reconstruct3Dlines")
+        """use_CERES bundles the 3D lines (optimizeClusters, line3D.cc:1800-1805) on the GPU: a per-line
+        Levenberg-Marquardt solve of the reference's robust reprojection cost (include/l3dpp_hip.h).  The default stays
+        False, as in a reference build without Ceres; a reference build with Ceres defaults to True (commons.h:84)."""
+        ok = self._check(self.L.l3d_reconstruct_3d_lines(self.h, int(visibility_t), int(perform_diffusion),
+                                                         float(collinearity_t), int(use_CERES), int(max_iter_CERES)),
+                         "reconstruct3Dlines")
+        if ok and use_CERES:    # optimization.cc:190
+            print(f"{self.PREFIX}#unoptimizable_lines = {self.lineOptStats()['lines_constant']}")
+        return ok
+
+    def lineOptStats(self):
+        """l3d_line_opt_stats: what the line bundling of the last reconstruct3Dlines did (dict)"""
+        st = _lib.LineOptStats()
+        self._check(self.L.l3d_line_opt_stats(self.h, C.byref(st)), "lineOptStats")
+        return {name: getattr(st, name) for name, _ in st._fields_ if name != "reserved"}
 
     # Line3D::createOutputFilename (private in the reference; line3D.cc:2853-2893)
     def outputFilename(self, max_image_width=-1):

@@ -306,14 +306,14 @@ int l3d_affinity_shard_abort(l3d_ctx* c) {
 // Line3D::reconstruct3Dlines, line3D.cc:1702-1824
 int l3d_reconstruct_3d_lines(l3d_ctx* c, uint32_t visibility_t, int perform_diffusion, float collinearity_t,
                              int use_CERES, uint32_t max_iter_CERES) {
-    (void)max_iter_CERES;
     if (!c) return fail(L3D_ERR_ARG, "null argument");
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     if (c->state != l3d_ctx::MATCHED || c->n_hyps == 0)
         return fail(L3D_ERR_STATE, "no clusterable segments! forgot to match lines?");   // line3D.cc:1712-1718
     if (c->aff_shard_open) return fail(L3D_ERR_STATE, "a sharded affinity fill is open: l3d_affinity_shard_finish (or _abort) first");
     c->collinearity_t = collinearity_t;                                                          // :1725-1726
-    if (use_CERES) set_error("CERES not available, no optimization will be performed");             // :1741-1743
+    c->use_ceres = use_CERES != 0;                                                              // :1739-1740
+    c->lo_stats = l3d_line_opt_summary{};
     const unsigned vis = std::max<unsigned>(visibility_t, 3);
     c->visibility_t = vis; c->perform_rdd = perform_diffusion != 0;
     c->lines3D.clear();
@@ -350,7 +350,11 @@ int l3d_reconstruct_3d_lines(l3d_ctx* c, uint32_t visibility_t, int perform_diff
         for (size_t i = 0; i < in.hyps.size(); ++i) in.entry_map[{in.hyps[i].m.src_cam, in.hyps[i].m.src_seg}] = i;
         for (auto* v : c->order) in.views[v->cam] = v;
         uint32_t ncl = 0, nvalid = 0;
-        reconstruct_lines(in, c->lines3D, &ncl, &nvalid);
+        std::vector<ReconCluster> clusters;
+        cluster_lines(in, clusters, &ncl, &nvalid);
+        if (use_CERES) rc = line_opt(c, in.views, clusters, max_iter_CERES);                    // optimizeClusters, :1800-1805
+        if (rc != L3D_OK) { untranslate(*c); return rc; }
+        final_lines(in, clusters, c->lines3D);
         // untranslate the lines (performTranslation(translation_), line3D.cc:559-574)
         const d3 t = c->translation;
         auto shift = [&](ReconSeg3D& s) { s.P1 = s.P1 + t; s.P2 = s.P2 + t; };

@@ -4,6 +4,7 @@
 //   l3d_affinity_host.hip  the affinity part of reconstruct3Dlines, collinear links, diffusion, reconstruction tail
 //   l3d_access.hip         accessors (matches_, estimated_position3D_, A_, SparseMatrix, timings)
 //   l3d_output.hip         get3Dlines and the result writers (TXT / OBJ / STL)
+//   l3d_lineopt.hip        line bundling (optimizeClusters) between the clustering and the final 3D segments
 //   l3d_seam.hip           the accelerator-seam entries (cudawrapper.h:54-80) with CPU-path semantics
 #pragma once
 #include <algorithm>
@@ -108,6 +109,10 @@ float ev_ms(const ::l3d_ctx* c, int a, int b);   // 0 when the timing level left
 int affinity_core(::l3d_ctx* c);           // l3d_affinity_host.hip
 int ensure_affinity_host(::l3d_ctx* c);    // l3d_affinity_host.hip
 std::string output_filename(::l3d_ctx* c, int max_image_width);   // l3d_output.hip
+// l3d_lineopt.hip: LineOptimizer::optimize on clusters3D_ (translated frame), and its parametrisation / write-back
+int line_opt(::l3d_ctx* c, const std::map<uint32_t, const HostView*>& views, std::vector<ReconCluster>& clusters, uint32_t max_iter);
+bool line_to_cayley(const d3& P1, const d3& P2, double x[4]);
+bool cayley_to_segment(const double x[4], const d3& P1_old, const d3& P2_old, d3& P1, d3& P2);
 
 }  // namespace l3d
 
@@ -275,6 +280,12 @@ struct l3d_ctx {
     std::vector<l3d_segment2d> l2g;
     std::vector<ReconLine> lines3D;                 // lines3D_ (original frame)
     bool lines_done = false;
+    // line bundling (use_CERES_ of the last reconstruct3Dlines; l3d_lineopt.hip)
+    bool use_ceres = false;
+    l3d_line_opt_summary lo_stats{};
+    PinnedBuf<char> h_lopt;
+    DevBuf<char> d_lopt;
+    hipEvent_t lo_ev[2] = {};                       // around k_lineopt, created on first use at timing level >= 2
     // timings.  Every hipEventRecord between two kernels costs a ~6 us bubble on the stream (rocprofv3 kernel trace of C1:
     // gaps exactly where the ten events of a call sit, none between other back-to-back kernels): timing_level 2 records
     // all of them (profiling, opt-in), 1 -- THE DEFAULT since round 5: what a facade user of matchImages gets is the fast

@@ -22,7 +22,8 @@ std::string output_filename(l3d_ctx* c, int max_image_width) {
         if (c->const_regularization_depth > 0.0f) str << "REG_DEPTH_" << c->const_regularization_depth << "__";
     }
     if (c->perform_rdd) str << "DIFFUSION__";
-    str << "vis_" << c->visibility_t;     // (no "OPTIMIZED__": Ceres is not part of this library)
+    if (c->use_ceres) str << "OPTIMIZED__";   // the lines were bundled (l3d_lineopt.hip)
+    str << "vis_" << c->visibility_t;
     return str.str();
 }
 

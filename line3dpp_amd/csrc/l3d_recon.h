@@ -7,6 +7,7 @@
 //   performClustering            clustering.cc:6-48, universe.h
 //   Line3D::clusterSegments      line3D.cc:2079-2152
 //   Line3D::get3DlineFromCluster :2155-2218
+//   (Line3D::optimizeClusters :2269-2275 sits between the two: l3d_lineopt.h)
 //   Line3D::project2DsegmentOnto3Dline :2221-2266
 //   Line3D::computeFinal3Dsegments :2278-2300, findCollinearSegments(cluster) :2342-2452
 //   Line3D::filterTinySegments   :2302-2339, View::projectedLongEnough view.cc:422-427, View::project :374-392
@@ -48,7 +49,18 @@ struct ReconInput {
     unsigned visibility_t = 3;
 };
 
-// lines3D_ in the translated frame (the caller translates back, line3D.cc:1820 / :559-574)
-void reconstruct_lines(const ReconInput& in, std::vector<ReconLine>& out, uint32_t* n_clusters, uint32_t* n_valid);
+ReconSeg3D segment3d(const d3& P1, const d3& P2);   // L3DPP::Segment3D(P1, P2)
+
+struct ReconCluster {  // L3DPP::LineCluster3D (segment3D.h:120-160): clusters3D_ between clustering and computeFinal3Dsegments
+    ReconSeg3D seg;
+    std::vector<std::pair<uint32_t, uint32_t>> residuals;   // (camID, segID)
+    uint32_t ref_view = 0;
+};
+
+// clusterSegments + get3DlineFromCluster: clusters3D_ (translated frame)
+void cluster_lines(const ReconInput& in, std::vector<ReconCluster>& clusters, uint32_t* n_clusters, uint32_t* n_valid);
+// computeFinal3Dsegments + filterTinySegments of clusters3D_ (whatever optimizeClusters left of them): lines3D_ in the
+// translated frame (the caller translates back, line3D.cc:1820 / :559-574)
+void final_lines(const ReconInput& in, const std::vector<ReconCluster>& clusters, std::vector<ReconLine>& out);
 
 }  // namespace l3d

@@ -139,9 +139,10 @@ void project(const HostView& v, const d3& P, double& x, double& y) {
 }  // namespace
 
 d3 principal_direction_of(double S[3][3]) { return principal_direction(S); }   // (named entry for the test hook below)
+ReconSeg3D segment3d(const d3& a, const d3& b) { return make_seg(a, b); }   // (named entry for the test hook below)
 
-void reconstruct_lines(const ReconInput& in, std::vector<ReconLine>& out, uint32_t* n_clusters, uint32_t* n_valid) {
-    out.clear();
+void cluster_lines(const ReconInput& in, std::vector<ReconCluster>& clusters, uint32_t* n_clusters, uint32_t* n_valid) {
+    clusters.clear();
     if (n_clusters) *n_clusters = 0;
     if (n_valid) *n_valid = 0;
     if (in.edges.empty()) return;
@@ -157,8 +158,6 @@ void reconstruct_lines(const ReconInput& in, std::vector<ReconLine>& out, uint32
         cluster2cameras[cl][in.l2g[id].camID_] = true;
     }
     if (n_clusters) *n_clusters = (uint32_t)cluster2segments.size();
-    struct Cluster { ReconSeg3D seg; std::vector<std::pair<uint32_t, uint32_t>> residuals; uint32_t ref_view; };
-    std::vector<Cluster> clusters;
     for (int cl : unique_clusters) {
         if (cluster2cameras[cl].size() < in.visibility_t) continue;
         // ---- get3DlineFromCluster, :2155-2218 ----
@@ -190,15 +189,21 @@ void reconstruct_lines(const ReconInput& in, std::vector<ReconLine>& out, uint32
             for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) S[i][j] += c[i] * c[j];
         }
         const d3 dir = principal_direction(S);
-        Cluster c;
+        ReconCluster c;
         c.seg = make_seg(P - dir, P + dir);
         c.residuals = segs;
         c.ref_view = reference_cam;
         if (!c.residuals.empty()) clusters.push_back(std::move(c));
     }
     if (n_valid) *n_valid = (uint32_t)clusters.size();
+}
+
+// (reconstruct3Dlines calls optimizeClusters() here, line3D.cc:1800-1805: l3d_lineopt.hip)
+
+void final_lines(const ReconInput& in, const std::vector<ReconCluster>& clusters, std::vector<ReconLine>& out) {
+    out.clear();
     // ---- computeFinal3Dsegments :2278-2300 + findCollinearSegments(cluster) :2342-2452 ----
-    for (const Cluster& cl : clusters) {
+    for (const ReconCluster& cl : clusters) {
         std::vector<ReconSeg3D> collinear;
         const d3 COG = (cl.seg.P1 + cl.seg.P2) * 0.5;
         struct Pt { size_t line, point; uint32_t cam; float dist; };
