@@ -197,6 +197,10 @@ int l3d_get_pairs(l3d_ctx*, uint32_t* src_cam, uint32_t* tgt_cam, uint64_t* slot
 int l3d_match_pairs(l3d_ctx*, uint32_t first, uint32_t count);
 int l3d_slot_buffer(l3d_ctx*, void** dev_ptr, uint64_t* n_slots);   /* (halo form of a multi-GPU call: only the regions of
                                                                        * the pairs this rank matched or received hold slots) */
+/* test hook: copies the fresh-hypothesis stream the list pass reads to the host, out[2 i], out[2 i + 1] = (depth_p1, depth_p2)
+ * of slot i of the slot buffer when the slot is alive (kSlotAlive in its flags), NaN otherwise; n = n_slots of
+ * l3d_slot_buffer.  Read only; meaningful after l3d_match_finish / l3d_lists_shard* of the current call. */
+int l3d_get_fresh_hyp(l3d_ctx*, float* out, uint64_t n);
 /* (kNN <= 0, keep every match -- line3D.cc:982-992: the device buffer is RAGGED, a row holds exactly its matches in ascending
  *  target order and n_slots is their number; l3d_get_pairs' slot_offset is the pair's first slot; l3d_get_pair_slots below
  *  hands a pair out in the padded Ms x K form, K = its longest row.  The mode runs unsharded.) */
@@ -252,8 +256,10 @@ int l3d_tail_shard_count(l3d_ctx*, uint32_t counts[2]);
  *   first_needed_rank   the chain of a rank only has to cover the records its views DEPEND on: view v depends on view u < v when a
  *                       pair (u -> v) hands inverse matches over (line3D.cc:1680), transitively.  With contiguous view ranges the
  *                       ranks a rank depends on lie below it; the caller (which knows the pair list: l3d_plan_shards) passes the
- *                       lowest one, and may then leave the record slabs of ranks outside [first_needed_rank, rank] unexchanged --
- *                       the COUNTER slab (array 3 of l3d_lists_shard*) must still reach every rank, it carries the pool
+ *                       lowest one.  The chain walks the pools of EVERY rank in [first_needed_rank, rank], so the caller must
+ *                       deliver the record slabs of every rank in that range, including those of a rank in between that this
+ *                       rank does not depend on; it may leave the record slabs of ranks outside the range unexchanged.  The
+ *                       COUNTER slab (array 3 of l3d_lists_shard*) must still reach every rank, it carries the pool
  *                       overflow flags all ranks decide on alike.  0 (default): all ranks below (and the records of all ranks
  *                       must be present, as before).
  *   exchanges_stream_ordered   nonzero: the caller's exchanges are ordered behind the context's stream by themselves (RCCL

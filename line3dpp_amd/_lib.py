@@ -79,7 +79,7 @@ EXPORTS = [
     "l3d_trim_cache", "l3d_set_timing_level", "l3d_tail_shard_count", "l3d_tail_shard_layout", "l3d_tail_shard_commit",
     "l3d_sfm_open_colmap", "l3d_sfm_open_bundler", "l3d_sfm_num_images", "l3d_sfm_get_image", "l3d_sfm_get_worldpoints",
     "l3d_sfm_close", "l3d_debug_counter", "l3d_affinity_shard_begin", "l3d_affinity_shard_finish", "l3d_affinity_shard_abort", "l3d_shard_options",
-    "l3d_line_opt_stats", "l3d_line_to_cayley", "l3d_cayley_to_segment", "l3d_line_opt_eval",
+    "l3d_line_opt_stats", "l3d_line_to_cayley", "l3d_cayley_to_segment", "l3d_line_opt_eval", "l3d_get_fresh_hyp",
 ]
 
 _lib = None
@@ -124,6 +124,7 @@ def load():
     L.l3d_get_pairs.argtypes = [vp, vp, vp, vp]
     L.l3d_match_pairs.argtypes = [vp, u32, u32]
     L.l3d_slot_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(u64)]
+    L.l3d_get_fresh_hyp.argtypes = [vp, vp, u64]
     L.l3d_match_finish.argtypes = [vp]
     L.l3d_match_abort.argtypes = [vp]
     L.l3d_lists_shard.argtypes = [vp, u32, u32, vp, vp, vp]

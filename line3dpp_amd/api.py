@@ -267,6 +267,15 @@ class Line3D:
         self.L.l3d_slot_buffer(self.h, C.byref(p), C.byref(n))
         return p.value, n.value
 
+    def fresh_hyp(self):
+        """test hook: the (depth_p1, depth_p2) stream of the slot buffer the list pass reads -- NaN for a slot that is not
+        alive -- as float32 [n_slots, 2]"""
+        _, n = self.slot_buffer()
+        out = np.zeros((n, 2), np.float32)
+        if not self._check(self.L.l3d_get_fresh_hyp(self.h, ptr(out), n), "fresh_hyp"):
+            return None
+        return out
+
     def slot_index_buffer(self):
         """device pointer of the compact exchange buffer (uint32 target index per slot) and its length"""
         p = C.c_void_p(); n = C.c_uint64()

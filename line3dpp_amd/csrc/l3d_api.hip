@@ -1084,6 +1084,19 @@ int l3d_slot_buffer(l3d_ctx* c, void** dev_ptr, uint64_t* n_slots) {
     return L3D_OK;
 }
 
+// test hook: the fresh-hypothesis stream the list pass reads (hyp_p, l3d_kernels.h: OrientFuse) -> host, read only
+int l3d_get_fresh_hyp(l3d_ctx* c, float* out, uint64_t n) {
+    if (!c || (!out && n)) return fail(L3D_ERR_ARG, "null argument");
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    if (n != c->n_slots) return fail(L3D_ERR_ARG, "l3d_get_fresh_hyp: n must be the call's slot count (l3d_slot_buffer)");
+    if (!n) return L3D_OK;
+    if (!c->d_hyp_p.p || c->d_hyp_p.cap < n) return fail(L3D_ERR_STATE, "l3d_get_fresh_hyp: no hypothesis stream of this call");
+    (void)hipSetDevice(c->device);
+    L3D_HIP_CHECK(hipMemcpyAsync(out, c->d_hyp_p.p, n * sizeof(float2), hipMemcpyDeviceToHost, c->stream));
+    L3D_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return L3D_OK;
+}
+
 // ---- compact exchange (N > 1 ranks): 4 B per slot travel instead of 32 --------------------------------------------
 int l3d_slot_index_buffer(l3d_ctx* c, void** dev_ptr, uint64_t* n_slots) {
     if (!c) return fail(L3D_ERR_ARG, "null argument");

@@ -392,7 +392,8 @@ static int tail_count_run(l3d_ctx* c, bool fresh, const TailShard& ts) {
     const ZeroLayout z = zero_layout(V, G);
     // the chain: over the records this shard's views depend on -- all pools on one GPU and in a replicated tail; the pools of
     // the ranks [shard_dep_rank0, rank] when the tail is sharded (l3d_shard_options; the pools of later ranks hold nothing this
-    // rank's scores read, those of ranks it does not depend on need not even have arrived: their counters are zero)
+    // rank's scores read).  EVERY pool in that range is walked, with the counters every rank received: the records of each
+    // rank in the range must have arrived, also of a rank this one does not depend on (dist.shard_needs closes the set)
     const bool dep = ts.npools < kListPools && c->shard_world > 1 && c->shard_dep_rank0 <= c->shard_rank;
     const uint32_t cp0 = dep ? c->shard_dep_rank0 * c->shard_ppr : 0u, cp1 = dep ? (c->shard_rank + 1) * c->shard_ppr : kListPools;
     const ListPools lp = list_pools(c, cp0, cp1 - cp0), lps = list_pools(c, ts.pool0, ts.npools);

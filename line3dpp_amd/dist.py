@@ -148,12 +148,11 @@ def _all_ok(ok, device, group, level=1):
     return bool(int(t.item()))
 
 
-def shard_needs(pairs, M, view_bounds, world_size):
-    """needs[r] = the ranks (other than r) whose RECORDS rank r's chain depends on.  View v depends on view u < v when a pair
+def shard_deps(pairs, M, view_bounds, world_size):
+    """deps[r] = the ranks (other than r) whose RECORDS rank r's chain depends on.  View v depends on view u < v when a pair
     (u -> v) exists (its matches are handed to v as inverse hypotheses, line3D.cc:1680) and, through u's own inverse
     hypotheses, on everything u depends on: the ancestors of r's views in that DAG, by owner.  A function of the pair list
-    alone.  N rings without pairs between them (weak scaling): every set is empty -- no record travels, every rank's chain
-    covers its own records only."""
+    alone.  The set may have holes (rank 0 feeding rank 2 while rank 1 stands alone): shard_needs closes it."""
     cams = sorted(M)
     vidx = {c: i for i, c in enumerate(cams)}
     V = len(cams)
@@ -163,7 +162,7 @@ def shard_needs(pairs, M, view_bounds, world_size):
         if v > u:
             preds[v].append(u)
     owner = np.searchsorted(np.asarray(view_bounds)[1:], np.arange(V), side="right")
-    needs = []
+    deps = []
     for r in range(world_size):
         seen = np.zeros(V, bool)
         stack = list(range(int(view_bounds[r]), int(view_bounds[r + 1])))
@@ -175,16 +174,28 @@ def shard_needs(pairs, M, view_bounds, world_size):
                 if not seen[u]:
                     seen[u] = True
                     stack.append(u)
-        needs.append(sorted(set(int(q) for q in owner[seen]) - {r}))
-    return needs
+        deps.append(sorted(set(int(q) for q in owner[seen]) - {r}))
+    return deps
+
+
+def shard_needs(pairs, M, view_bounds, world_size, deps=None):
+    """needs[r] = the ranks whose record slabs rank r must receive: every rank in [min(deps[r]), r).  The library's chain
+    walks the pools of ALL ranks in [first_needed_rank, rank] (l3d_shard_options) and the counter slab of every rank reaches
+    everyone, so a rank inside that range whose records did not arrive would be followed into records that are not there.
+    Ring slices and independent rings give contiguous (or empty) dependency sets: there needs == deps and nothing more
+    travels.  N rings without pairs between them (weak scaling): every set is empty -- no record travels, every rank's
+    chain covers its own records only."""
+    if deps is None:
+        deps = shard_deps(pairs, M, view_bounds, world_size)
+    return [list(range(min(d), r)) if d else [] for r, d in enumerate(deps)]
 
 
 def gather_slabs(slabs, rank, world_size, device, group=None, l3d=None, needs=None):
     """Every rank's slab of every record array of the sharded list pass (Line3D.listsShard) lands at its place in every
     rank's array.  slabs = [(slab pointer, slab bytes, full-array pointer)]; equal slab sizes by construction.
 
-    needs (round 6, shard_needs): the three RECORD arrays (edges, headers, segment headers) only travel from a rank to the
-    ranks whose chain depends on its records; the fourth array -- the pool counters with every rank's overflow flags, on
+    needs (shard_needs): the three RECORD arrays (edges, headers, segment headers) only travel from a rank q to the ranks r
+    with q in needs[r] -- the ranks whose chain walks q's pools; the fourth array -- the pool counters with every rank's overflow flags, on
     which all ranks decide alike -- always reaches everyone.  None: everything to everyone.
 
     Default: DIRECT exchange -- one send and one receive per peer, all posted at once (batch_isend_irecv).  The xGMI
@@ -275,7 +286,8 @@ def _gather_counts(n_r, h_r, rc, world_size, device, group):
 def plan_halo(pairs, M, world_size):
     """The partition of a call over `world_size` ranks (l3d_plan_shards) and what follows from it for every rank:
     view_bounds, pair_bounds, and per rank the runs of consecutive pairs it sends (pairs it owns whose TARGET view another
-    rank owns): runs[r] = [(peer, first pair, pair count)].  A function of the pair list alone: identical on every rank."""
+    rank owns): runs[r] = [(peer, first pair, pair count)]; deps (shard_deps: the ranks a rank's chain depends on) and needs
+    (shard_needs: those closed to the range the chain walks).  A function of the pair list alone: identical on every rank."""
     import ctypes as C
     from . import _lib
     cams = sorted(M)
@@ -298,7 +310,8 @@ def plan_halo(pairs, M, world_size):
             runs[r][-1] = (q, runs[r][-1][1], runs[r][-1][2] + 1)
         else:
             runs[r].append((q, p, 1))
-    return dict(view_bounds=vb, pair_bounds=pb, runs=runs, needs=shard_needs(pairs, M, vb, world_size))
+    deps = shard_deps(pairs, M, vb, world_size)
+    return dict(view_bounds=vb, pair_bounds=pb, runs=runs, deps=deps, needs=shard_needs(pairs, M, vb, world_size, deps))
 
 
 def early_ranges(first, count, halo_pairs):
@@ -348,7 +361,7 @@ def match_images_halo(l3d, rank, world_size, device=None, group=None, **params):
     plan = plan_halo(pairs, M, world_size)
     l3d.halo_plan = plan
     vb, pb, runs, needs = plan["view_bounds"], plan["pair_bounds"], plan["runs"], plan["needs"]
-    # the chain of this rank covers the records its views depend on (the ranks in needs[rank], all below it), and the
+    # the chain of this rank covers the pools of the ranks in needs[rank] (all below it, the range [min, rank)), and the
     # library's sharded entries need not wait for the device when the exchanges order themselves behind its stream (RCCL on
     # the context's stream = torch's current one); l3d_shard_options
     if hasattr(l3d, "shardOptions"):

@@ -118,7 +118,8 @@ int main(int argc, char** argv) {
         if (!runs[r].empty() && runs[r].back().peer == q && runs[r].back().first + runs[r].back().count == p) ++runs[r].back().count;
         else runs[r].push_back(Run{q, p, 1});
     }
-    // needs[r][q]: rank r's chain depends on the records of rank q (line3dpp_amd/dist.py: shard_needs) -- view v depends on
+    // needs[r][q]: rank r receives the record slabs of rank q.  First the ranks r's chain depends on (line3dpp_amd/dist.py:
+    // shard_deps) -- view v depends on
     // view u < v when a pair (u -> v) exists, transitively; by owner
     std::vector<std::vector<char>> needs(world, std::vector<char>(world, 0));
     {
@@ -135,6 +136,11 @@ int main(int argc, char** argv) {
             for (uint32_t v = 0; v < nv; ++v) if (seen[v] && (int)owner(v) != r) needs[r][owner(v)] = 1;
         }
     }
+    // the chain walks the pools of every rank in [first_needed, rank]: the records of each of them must arrive, also of a
+    // rank in between that this one does not depend on (dist.shard_needs closes the set the same way)
+    for (int r = 0; r < world; ++r)
+        for (int q = 0; q < r; ++q)
+            if (needs[r][q]) { for (int q1 = q + 1; q1 < r; ++q1) needs[r][q1] = 1; break; }
     uint32_t first_needed = (uint32_t)rank;
     for (int q = 0; q < rank; ++q) if (needs[rank][q]) { first_needed = (uint32_t)q; break; }
     // (the exchanges below run on a communication stream of their own: the library's entries must return with their parts

@@ -241,3 +241,29 @@ def compare_pair_fast(slots, omatches):
     for f in ("overlap", "d_p1", "d_p2", "d_q1", "d_q2"):
         r["inexact_fields"] += int(np.count_nonzero(go[f] != oo[f]))
     return r
+
+
+def gap_scene(world, n_segs, seed=0):
+    """A multi-rank topology whose dependency sets have a HOLE: a 12-view ring on the cams of the first and the last rank
+    (cams 0-5 and 6 (world - 1) .. 6 world - 1) and a self-contained 6-view ring on the cams of every rank in between.  The
+    last rank depends on rank 0 alone; the ranks between depend on nobody.  The segment counts (n_segs on the last rank's
+    views, 0.72 n_segs on rank 0's, 0.87 n_segs on the middle rings) give every rank the same matching cost, so that
+    l3d_plan_shards cuts at the rings (rank 0's views hand out 15 pairs, the last rank's 9, a 6-view ring's 12)."""
+    from line3dpp_amd.scene import Scene, make_scene
+    hi = 6 * (world - 1)
+    a, m = int(0.72 * n_segs), int(0.87 * n_segs)
+    ren = {i: (i if i < 6 else hi + i - 6) for i in range(12)}
+    views = []
+    for v in make_scene(12, n_segs, n_neighbors=4, seed=seed).views:
+        if v.cam < 6:
+            v.segs = v.segs[:a].copy()
+        v.cam = ren[v.cam]
+        v.neighbors = [ren[int(x)] for x in v.neighbors]
+        views.append(v)
+    for r in range(1, world - 1):
+        for v in make_scene(6, m, n_neighbors=4, seed=seed + r).views:
+            v.cam += 6 * r
+            v.neighbors = [int(x) + 6 * r for x in v.neighbors]
+            views.append(v)
+    views.sort(key=lambda v: v.cam)
+    return Scene(views, f"gap{world}")

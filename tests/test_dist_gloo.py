@@ -364,16 +364,21 @@ class _HaloReplayContext(_ReplayContext):
         return True
 
     def _slabs_arrived(self, sharded_tail=True):
-        """round 6: the record arrays (k < 3) of the ranks this rank's chain DEPENDS on (dist.shard_needs) and of itself, the
-        counter slab (k = 3) of every rank; the records of a rank it does not depend on must NOT have been sent to it"""
+        """what the library reads: the record arrays (k < 3) of EVERY rank in [first_needed_rank, rank] -- its chain walks
+        all of those pools (l3d_shard_options), whether this rank depends on them or not -- and the counter slab (k = 3) of
+        every rank; the records of a rank outside that range must NOT have been sent to it"""
         vb = self.halo_plan["view_bounds"]
-        needs = set(self.halo_plan["needs"][self.rank]) | {self.rank} if sharded_tail else set(range(self.world))
-        assert getattr(self, "first_needed", 0) == min(needs)
+        first = getattr(self, "first_needed", 0)
+        if sharded_tail:
+            assert first == min(self.halo_plan["needs"][self.rank] + [self.rank])
+            walked = set(range(first, self.rank + 1))
+        else:
+            walked = set(range(self.world))
         for r in range(self.world):
             for k in range(4):
                 got = self.full[k][r * self.SLAB:(r + 1) * self.SLAB]
                 want = self._sig(r, int(vb[r]), int(vb[r + 1]), self.attempt, k)
-                if k == 3 or r in needs:
+                if k == 3 or r in walked:
                     if not np.array_equal(got, want):
                         return False
                 elif got.any():
@@ -473,14 +478,17 @@ def _aff_methods():
  _HaloReplayContext.affinityShardAbort) = _aff_methods()
 
 
-def _halo_worker(rank, world, port, q, shard_tail=True):
+def _halo_worker(rank, world, port, q, shard_tail=True, scene_kind="ring"):
+    """scene_kind "ring": one 9-view ring cut into ranges; "gap": tests.helpers.gap_scene, whose last rank depends on rank 0
+    alone (a hole in its dependency set)"""
     sys.path.insert(0, ROOT)
     from line3dpp_amd import dist
     from line3dpp_amd.scene import make_scene
+    from tests import helpers as H
     os.environ["MASTER_ADDR"] = "127.0.0.1"; os.environ["MASTER_PORT"] = str(port)
     dist_t.init_process_group("gloo", rank=rank, world_size=world)
     try:
-        scene = make_scene(9, 60, n_neighbors=4, seed=6)
+        scene = make_scene(9, 60, n_neighbors=4, seed=6) if scene_kind == "ring" else H.gap_scene(world, 40)
         ctx = _HaloReplayContext(scene, 5, rank, world)
         os.environ["L3D_SHARD_TAIL"] = "1" if shard_tail else "0"
         real = dist.device_tensor
@@ -503,25 +511,40 @@ def _halo_worker(rank, world, port, q, shard_tail=True):
         ok = ok and ctx.ranges_seen == (int(vb[rank]), int(vb[rank + 1]))
         single = _ReplayContext(scene, 5)
         assert single.matchBegin() and single.matchPairs(0, len(single.pairs_)) and single.matchFinish()
-        q.put((rank, ok and ctx.digest() == single.digest(), len(mine), len(incoming), sum(len(r) for r in runs)))
+        status = ctx.last_status
+        q.put((rank, ok and ctx.digest() == single.digest(), len(mine), len(incoming), sum(len(r) for r in runs),
+               [int(v) for v in vb], plan["deps"], plan["needs"], status))
     finally:
         dist_t.destroy_process_group()
 
 
-@pytest.mark.parametrize("world,shard_tail", [(2, True), (3, True), (4, True), (8, True), (3, False)])
-def test_halo_form_over_gloo(world, shard_tail):
+_HALO_CASES = [(2, True, "ring"), (3, True, "ring"), (4, True, "ring"), (8, True, "ring"), (3, False, "ring"), (3, True, "gap"),
+               (4, True, "gap")]
+
+
+@pytest.mark.parametrize("world,shard_tail,scene_kind", _HALO_CASES,
+                         ids=[f"{w}-{t}" + ("" if k == "ring" else f"-{k}") for w, t, k in _HALO_CASES])
+def test_halo_form_over_gloo(world, shard_tail, scene_kind):
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
-    procs = [ctx.Process(target=_halo_worker, args=(r, world, port, q, shard_tail)) for r in range(world)]
+    procs = [ctx.Process(target=_halo_worker, args=(r, world, port, q, shard_tail, scene_kind)) for r in range(world)]
     for p in procs:
         p.start()
-    res = [q.get(timeout=180) for _ in range(world)]
+    res = sorted(q.get(timeout=180) for _ in range(world))
     for p in procs:
         p.join(60)
         assert p.exitcode == 0
-    assert all(r[1] for r in res), res
-    assert sum(r[2] for r in res) == 18                  # 9 views x 4 neighbours / 2: every pair matched exactly once
+    if scene_kind == "gap":
+        # the case must not degenerate: the cuts fall at the rings and the last rank's dependency set has a hole
+        vb, deps = res[0][5], res[0][6]
+        assert vb == list(range(0, 6 * world + 1, 6)), vb
+        assert deps == [[]] * (world - 1) + [[0]], deps
+    assert all(r[1] for r in res), [(r[0], r[1], r[8]) for r in res]     # (rank, ok, last status: -8 = records missing)
+    if scene_kind == "gap":                          # needs fills the hole: the library walks the pools of every rank between
+        assert res[0][7] == [[]] * (world - 1) + [list(range(world - 1))], res[0][7]
+    n_pairs = 18 if scene_kind == "ring" else 24 + 12 * (world - 2)
+    assert sum(r[2] for r in res) == n_pairs             # every pair matched exactly once
     assert sum(r[3] for r in res) > 0 and res[0][4] > 0  # pairs did cross the cuts
 
 
@@ -558,6 +581,101 @@ def test_halo_plan_balances_pairs_and_lists_every_crossing_pair_once():
             assert sum(k for _, k in early) + late[1] == counts[r]
             assert not any(late[0] <= p < late[0] + late[1] for p in halo)     # the stretch matched last sends nothing
         assert len(crossing) < 0.2 * len(pairs) * (world - 1) / world + 120
+        # a ring cut into ranges depends on a contiguous set of lower ranks already: closing it moves no extra record slab
+        assert plan["needs"] == plan["deps"], (world, plan["deps"])
+        assert plan["needs"] == [list(range(r)) for r in range(world)], plan["needs"]
+
+
+def _ancestor_ranks(pairs, cams, view_bounds, world):
+    """the model of dist.shard_deps, by fixed-point iteration over the pair list: view u is an ancestor of view v when a
+    pair between them hands matches from the lower view index to the higher one (line3D.cc:1680), transitively"""
+    index = {c: i for i, c in enumerate(sorted(cams))}
+    edges = set()
+    for s, t in pairs:
+        u, v = index[int(s)], index[int(t)]
+        if u < v:
+            edges.add((u, v))
+    owner = {}
+    for r in range(world):
+        for v in range(int(view_bounds[r]), int(view_bounds[r + 1])):
+            owner[v] = r
+    out = []
+    for r in range(world):
+        anc = set(range(int(view_bounds[r]), int(view_bounds[r + 1])))
+        grown = True
+        while grown:
+            new = {u for (u, v) in edges if v in anc} - anc
+            grown = bool(new)
+            anc |= new
+        out.append(sorted({owner[u] for u in anc} - {r}))
+    return out
+
+
+def test_shard_needs_closes_the_dependency_set_to_the_range_the_chain_walks():
+    """dist.shard_deps against a model written here, on seeded random pair lists (sparse cam ids, clusters with no pair
+    between them, random and planned cuts), and dist.shard_needs = every rank from the lowest dependency up to the rank:
+    the library's chain walks the pools of all of them (l3d_shard_options), so a hole in the set is filled"""
+    sys.path.insert(0, ROOT)
+    from line3dpp_amd import dist
+    rng = np.random.default_rng(1234)
+    holes = 0
+    for trial in range(300):
+        V = int(rng.integers(6, 41))
+        world = int(rng.choice([2, 3, 4, 8]))
+        cams = sorted(rng.choice(10 * V, V, replace=False).tolist())
+        # views fall into clusters (1 .. 4); pairs only inside a cluster, so some lists are deliberately disconnected
+        cluster = rng.integers(0, int(rng.integers(1, 5)), V)
+        pairs = set()
+        for _ in range(int(rng.integers(1, 3 * V))):
+            u, v = rng.choice(V, 2, replace=False)
+            if cluster[u] == cluster[v] and (cams[v], cams[u]) not in pairs:
+                pairs.add((cams[u], cams[v]))
+        pairs = sorted(pairs)
+        M = {c: int(rng.integers(1, 200)) for c in cams}
+        if trial % 2 and pairs:
+            vb = [int(x) for x in dist.plan_halo(pairs, M, world)["view_bounds"]]
+        else:                                        # contiguous ranges, some of them empty
+            vb = [0] + sorted(rng.integers(0, V + 1, world - 1).tolist()) + [V]
+        deps = dist.shard_deps(pairs, M, vb, world)
+        assert deps == _ancestor_ranks(pairs, cams, vb, world), (trial, pairs, vb)
+        needs = dist.shard_needs(pairs, M, vb, world)
+        assert needs == dist.shard_needs(pairs, M, vb, world, deps)
+        for r in range(world):
+            assert needs[r] == (list(range(min(deps[r]), r)) if deps[r] else []), (trial, r, deps[r], needs[r])
+            assert all(q < r for q in needs[r])
+            holes += needs[r] != deps[r]
+        if pairs:
+            plan = dist.plan_halo(pairs, M, world)
+            assert plan["deps"] == dist.shard_deps(pairs, M, plan["view_bounds"], world)
+            assert plan["needs"] == dist.shard_needs(pairs, M, plan["view_bounds"], world)
+    assert holes > 20, holes                         # the random lists did produce sets with holes
+
+
+def test_independent_rings_need_no_records_and_gap_topologies_fill_the_hole():
+    """bench.py --gpus N's weak-scaling layout (N rings, no pair between them): every set stays empty, no record slab
+    travels.  tests.helpers.gap_scene: the last rank depends on rank 0 alone; needs adds the ranks in between."""
+    sys.path.insert(0, ROOT)
+    from line3dpp_amd import dist
+    from tests import helpers as H
+    n, nb = 10, 4
+    pairs = []
+    for ring in range(3):
+        matched = {c: set() for c in range(n)}
+        for c in range(n):
+            for t in sorted((c + d) % n for d in range(-nb // 2, nb // 2 + 1) if d):
+                if t not in matched[c]:
+                    pairs.append((ring * n + c, ring * n + t)); matched[c].add(t); matched[t].add(c)
+    M = {c: 500 for c in range(3 * n)}
+    plan = dist.plan_halo(pairs, M, 3)
+    assert [int(x) for x in plan["view_bounds"]] == [0, 10, 20, 30]
+    assert plan["deps"] == plan["needs"] == [[], [], []]
+    for world in (3, 4):
+        sc = H.gap_scene(world, 40)
+        Mg = {v.cam: len(v.segs) for v in sc.views}
+        plan = dist.plan_halo(sc.pair_tests()[1], Mg, world)
+        assert [int(x) for x in plan["view_bounds"]] == list(range(0, 6 * world + 1, 6))
+        assert plan["deps"] == [[]] * (world - 1) + [[0]]
+        assert plan["needs"] == [[]] * (world - 1) + [list(range(world - 1))]
 
 
 # ---- a rank that fails locally does not strand the others (ADVICE r3: dist.py) --------------------------------------------

@@ -51,6 +51,51 @@ def _check_phase_a(g, scene, kNN, epi=0.25, allow_tie_order=True):
     return total
 
 
+def _assert_slot_liveness(g, present_pairs=None, min_alive=1):
+    """The list pass decides whether a fresh hypothesis is alive from the stream hyp_p (NaN = not alive, k_lists.hip), not
+    from the slot's kSlotAlive flag: every producer of slots (the match epilogue, k_orient_all, k_keep_assemble, the halo
+    expansion) must write both alike.  Over every slot of the present pairs (all of them when present_pairs is None): a slot
+    with a target is alive in hyp_p exactly when its flags say so, and then hyp_p holds its (d_p1, d_p2) bit for bit; a slot
+    without a target is not alive (the uniform-row sweep of the list pass reads it too).  Returns (alive, rejected)."""
+    import torch
+    from line3dpp_amd import dist
+    from line3dpp_amd._lib import SLOT_DTYPE
+    hyp = g.fresh_hyp()                              # (returns when the context's stream is done)
+    assert hyp is not None
+    ptr, n = g.slot_buffer()
+    assert hyp.shape == (n, 2) and n > 0
+    slots = dist.device_tensor(ptr, n * 32, torch.device("cuda", 0)).cpu().numpy().view(SLOT_DTYPE)
+    mask = np.ones(n, bool)
+    if present_pairs is not None:
+        off = [int(o) for o in g.pairs()[1]] + [n]
+        mask[:] = False
+        for p in present_pairs:
+            mask[off[p]:off[p + 1]] = True
+    present = mask & (slots["tgt_seg"] != EMPTY)
+    flag_alive = (slots["flags"] & 1) != 0
+    hyp_alive = ~np.isnan(hyp[:, 0])
+    bad = np.nonzero(present & (flag_alive != hyp_alive))[0]
+    assert not len(bad), f"{len(bad)} present slots whose hyp_p disagrees with kSlotAlive, first {bad[:5]}"
+    bad = np.nonzero(mask & ~present & hyp_alive)[0]
+    assert not len(bad), f"{len(bad)} slots without a target that hyp_p calls alive, first {bad[:5]}"
+    alive = present & flag_alive
+    bits = hyp.view(np.uint32)
+    assert np.array_equal(bits[alive, 0], slots["d_p1"].view(np.uint32)[alive])
+    assert np.array_equal(bits[alive, 1], slots["d_p2"].view(np.uint32)[alive])
+    assert int(alive.sum()) >= min_alive
+    return int(alive.sum()), int((present & ~flag_alive).sum())
+
+
+@pytest.mark.parametrize("kNN", [1, 10])
+def test_fresh_hypotheses_follow_the_alive_flag(kNN):
+    """bounded kNN on one context: the match epilogue writes the slots and the hyp_p stream together"""
+    sc = make_scene(6, 300, n_neighbors=4, seed=1)
+    g = _gpu(sc)
+    assert g.matchImages(kNN=kNN)
+    n_alive, n_rejected = _assert_slot_liveness(g, min_alive=500)
+    assert n_rejected > 0, "the orientation filter rejected nothing: the check saw one side only"
+
+
 @pytest.mark.parametrize("n_views,n_segs,nn,kNN,seed", [
     (6, 300, 4, 10, 1),
     (5, 257, 2, 1, 2),      # ragged: one lane past a full 256 block
@@ -200,6 +245,7 @@ def test_keep_all_single_pass_against_the_two_pass_form(monkeypatch):
         slots = [g.pair_slots(pi) for pi in range(len(g.pairs()[0]))]
         repeats = L.l3d_debug_counter(b"keep_all_repeats") - before
         assert g.matchFinish() and g.computeAffinity()
+        _assert_slot_liveness(g, min_alive=1000)     # (two-pass: k_orient_all over the padded rows; else k_keep_assemble)
         runs[name] = (g, slots, repeats)
     assert runs["two_pass"][2] == 0 and (runs["single_small_scratch"][2] & 0xFFFF) >= 1
     ref = runs["two_pass"][1]
@@ -990,9 +1036,9 @@ def test_sharded_tail_emulated_on_one_gpu_at_c2_slice_size(world):
     after the record slabs have been copied where the exchange would put them, every context runs the chain on the
     records its views depend on, computes scores, filterMatches, outputs and medians of ITS views only and writes them at
     their places in the full arrays; the parts are copied where the exchange would put them; the commit closes the call.
-    Everything a user can read back must equal a single context's result byte for byte.  Round 6: a context only receives
-    the record slabs of the ranks its views DEPEND on (dist.shard_needs; the counter slab of every rank) and its chain only
-    covers those (l3d_shard_options)."""
+    Everything a user can read back must equal a single context's result byte for byte.  A context only receives the record
+    slabs of the ranks its chain walks -- from the lowest rank its views depend on up to itself (dist.shard_needs) -- and the
+    counter slab of every rank; its chain only covers those (l3d_shard_options)."""
     from line3dpp_amd.scene import make_config
     _sharded_tail_emulation(H.ring_slice(make_config("C2", max_views=24), 0, 24), world)
 
@@ -1017,6 +1063,22 @@ def test_sharded_tail_of_independent_rings_needs_no_foreign_records():
     plan = dist.plan_halo(pairs, M, 3)
     assert plan["needs"] == [[], [], []] and not any(plan["runs"]), plan
     _sharded_tail_emulation(sc, 3)
+
+
+@pytest.mark.parametrize("world", [3, 4])
+def test_sharded_tail_of_a_gap_topology(world):
+    """tests.helpers.gap_scene: the last rank depends on rank 0 alone, the ranks in between are self-contained rings.  The
+    library's chain walks the pools of every rank in [first_needed_rank, rank] with the counters every rank received, so the
+    records of the ranks in between must arrive too: dist.shard_needs closes the set, and the emulation delivers exactly
+    what it lists (and poisons the rest)."""
+    from line3dpp_amd import dist
+    sc = H.gap_scene(world, 200)
+    M = {v.cam: len(v.segs) for v in sc.views}
+    plan = dist.plan_halo(sc.pair_tests()[1], M, world)
+    assert [int(x) for x in plan["view_bounds"]] == list(range(0, 6 * world + 1, 6))
+    assert plan["deps"] == [[]] * (world - 1) + [[0]], plan["deps"]                      # the hole
+    assert plan["needs"] == [[]] * (world - 1) + [list(range(world - 1))], plan["needs"]   # filled
+    _sharded_tail_emulation(sc, world)
 
 
 def _sharded_tail_emulation(sc, world):
@@ -1050,6 +1112,12 @@ def _sharded_tail_emulation(sc, world):
             for qq, f, n in runs[r]:
                 if qq == q:
                     assert g.expandSlotIndices(f, n)
+    if world == 3:
+        # own pairs (match epilogue) and received ones (halo expansion): both write the flags and hyp_p alike
+        for q, g in enumerate(ctxs):
+            present = list(range(int(pb[q]), int(pb[q + 1])))
+            present += [p for r in range(world) for qq, f, n in runs[r] if qq == q for p in range(f, f + n)]
+            _assert_slot_liveness(g, present)
     for attempt in range(8):
         slabs = []
         for r, g in enumerate(ctxs):
@@ -1061,7 +1129,7 @@ def _sharded_tail_emulation(sc, world):
             fulls = [dist.device_tensor(sl[k][2], sb * world, dev) for sl in slabs]
             for r in range(world):
                 for q in range(world):
-                    if q != r and (k == 3 or r in needs[q]):      # records: only to the ranks that depend on them
+                    if q != r and (k == 3 or r in needs[q]):      # records: only to the ranks whose chain walks them
                         fulls[q][r * sb:(r + 1) * sb].copy_(fulls[r][r * sb:(r + 1) * sb])
                     elif q != r:
                         fulls[q][r * sb:(r + 1) * sb].fill_(0xA5)   # what never arrives must not be read either
