@@ -179,6 +179,58 @@ int l3d_segment_cache_name(uint32_t camID, uint32_t width, uint32_t height, uint
 int l3d_read_segment_cache(const char* path, float* segs4 /* may be NULL */, uint32_t cap, uint32_t* n);
 int l3d_write_segment_cache(const char* path, const float* segs4, uint32_t n);
 
+/* ---- line-segment detection (Line3D::detectLineSegments, line3D.cc:243-370; GPU: k_lsd.hip) ------------------------
+ * An 8-bit image: channels 1 (CV_8U, grey) or 3 (CV_8UC3; converted with CV_RGB2GRAY, the first channel counts as R);
+ * any other count is "image type not supported" (L3D_ERR_ARG).  row_stride in bytes (>= cols * channels).  The image
+ * must already be undistorted: Line3D::undistortImage is not part of this library. */
+typedef struct l3d_image {
+    const uint8_t* data;
+    uint32_t cols, rows, channels, row_stride;
+} l3d_image;
+/* the constructor arguments of Line3D that detection reads (line3D.cc:6-12) */
+typedef struct l3d_detect_options {
+    const char* output_folder;        /* the cache lives in <output_folder>/L3D++_data/ */
+    int32_t load_segments;            /* load the segment cache if it exists, store it after detecting */
+    int32_t max_image_width;          /* <= 0: no downscale */
+    uint32_t max_line_segments;       /* cap on segments per image (3000 in the reference) */
+} l3d_detect_options;
+/* per image of the last detection */
+typedef struct l3d_detect_stats {
+    uint32_t width, height;           /* image handed to LSD (after the max-width downscale) */
+    uint32_t raw_segments;            /* LSD output before the length filter and the cap */
+    uint32_t segments;                /* what the call returned */
+    uint32_t from_cache;              /* 1: loaded from the segment cache, LSD did not run */
+    uint32_t seeds;                   /* regions grown */
+    uint32_t nfa_evals;               /* rect_nfa evaluations */
+    uint32_t reserved;
+    double max_grad;                  /* ll_angle's largest defined gradient norm (-1: none) */
+} l3d_detect_stats;
+/* LSD with the reference's filter, order and cap on a batch of images (one launch set for all of them); no cache.
+ * counts[n_images] = segments per image; the segments themselves: l3d_get_detected_segments. */
+int l3d_detect_segments(l3d_ctx*, uint32_t n_images, const l3d_image* images, int max_image_width,
+                        uint32_t max_segments, uint32_t* counts);
+/* The same with the segment cache as Line3D::detectLineSegments uses it (opts->load_segments): a cached image is read,
+ * the others are detected in one batch and stored.  camIDs name the cache files. */
+int l3d_detect_view_segments(l3d_ctx*, uint32_t n_images, const uint32_t* camIDs, const l3d_image* images,
+                             const l3d_detect_options* opts, uint32_t* counts);
+/* segments of the last detection on this context, image after image: n x (x1, y1, x2, y2); *n = their number.  "Last"
+ * is context-wide: with several threads detecting on one context, the caller must order the two calls itself. */
+int l3d_get_detected_segments(l3d_ctx*, float* segs4 /* may be NULL */, uint64_t cap, uint64_t* n);
+int l3d_get_detect_stats(l3d_ctx*, l3d_detect_stats* out, uint32_t cap, uint32_t* n);
+/* Line3D::addImage with empty line_segments: detect (or load from the cache), then add the view as l3d_add_view /
+ * l3d_add_view_worldpoints do.  No segment survives: L3D_ERR_NO_SEGMENTS, the view is not added (line3D.cc:184-190).
+ * *n_segments (may be NULL) = the number of segments THIS view was added with (0 when it was not added), set inside the
+ * call: concurrent callers must take it from here, not from l3d_get_detected_segments, which another thread's call may
+ * have replaced in between.  The call holds the context mutex for the whole detection, so concurrent calls on one
+ * context run one after another; to detect many images at once, use l3d_detect_view_segments (one batch) and add the
+ * views with their segments. */
+int l3d_add_view_image(l3d_ctx*, uint32_t camID, const l3d_image* image, const l3d_detect_options* opts,
+                       const double K[9], const double R[9], const double t[3], float median_depth,
+                       const uint32_t* neighbors, uint32_t n_neighbors, uint32_t* n_segments);
+int l3d_add_view_image_worldpoints(l3d_ctx*, uint32_t camID, const l3d_image* image, const l3d_detect_options* opts,
+                                   const double K[9], const double R[9], const double t[3], float median_depth,
+                                   const uint32_t* worldpoints, uint32_t n_worldpoints, uint32_t* n_segments);
+
 /* Line3D::matchImages (line3D.cc:375-497): the whole call on this context's GPU. */
 int l3d_match_images(l3d_ctx*, const l3d_match_params*);
 
@@ -433,7 +485,8 @@ int l3d_set_timing_level(l3d_ctx*, int level);
 /* Test hook (no reference counterpart): process-wide counters that tell a test which form of a kernel ran.
  * "csr_global_launches": launches of the global-cursor form of k_pair_csr (views beyond 32 768 segments, or
  * L3D_CSR_GLOBAL=1); "knn_replay_calls": l3d_match_begin calls whose kNN exceeded the LDS tables of the match kernel
- * (every row then takes the exact replay path).  Unknown name: ~0. */
+ * (every row then takes the exact replay path); "lsd_images_detected": images LSD ran on; "lsd_cache_loads": images
+ * whose segments came from the segment cache.  Unknown name: ~0. */
 unsigned long long l3d_debug_counter(const char* name);
 
 /* ---- (2) seam layer ------------------------------------------------------------------ */

@@ -23,7 +23,10 @@
 #include <iostream>
 #include <list>
 #include <map>
+#include <mutex>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../l3dpp_hip.h"
@@ -37,7 +40,24 @@ constexpr unsigned L3D_DEF_MATCHING_NEIGHBORS = 10;
 constexpr float L3D_DEF_EPIPOLAR_OVERLAP = 0.25f;
 constexpr int L3D_DEF_KNN = 10;
 
-struct ImageSize { int cols, rows; };  // stand-in for cv::Mat when OpenCV is not around
+struct ImageSize { int cols, rows; };  // stand-in for cv::Mat when OpenCV is not around (size only: give segments)
+
+// stand-in for an 8-bit cv::Mat with pixels: grey (channels 1, CV_8U) or RGB (channels 3, CV_8UC3, first channel = R);
+// step = bytes per row.  addImage detects the segments of such an image when it is given none.
+struct Image8U {
+    const unsigned char* data;
+    int cols, rows, channels_;
+    size_t step;
+    int channels() const { return channels_; }
+    int type() const { return channels_ == 1 ? 0 : channels_ == 3 ? 16 : -1; }   // CV_8U, CV_8UC3
+};
+
+namespace detail {
+template <class I, class = void> struct has_pixels : std::false_type {};
+template <class I>
+struct has_pixels<I, std::void_t<decltype(std::declval<const I&>().data), decltype(std::declval<const I&>().type()),
+                                 decltype(std::declval<const I&>().step)>> : std::true_type {};
+}  // namespace detail
 
 class Line3D {
 public:
@@ -45,8 +65,11 @@ public:
            const unsigned int max_line_segments = 3000, const bool neighbors_by_worldpoints = false,
            const bool use_GPU = true, const int device = 0, void* hip_stream = nullptr)
         : prefix_("[L3D++] "), prefix_err_("[L3D++] ERROR: ") {
-        (void)output_folder; (void)load_segments; (void)max_line_segments; (void)use_GPU;
+        (void)use_GPU;
+        output_folder_ = output_folder;
+        load_segments_ = load_segments;
         max_img_width_ = max_img_width;
+        max_line_segments_ = max_line_segments;
         // addImage's list is a worldpoint list; neighbours from the worldpoint overlap at every matchImages
         // (Line3D::findVisualNeighborsFromWPs, line3D.cc:578-699 -> l3d_add_view_worldpoints)
         neighbors_by_worldpoints_ = neighbors_by_worldpoints;
@@ -58,8 +81,13 @@ public:
     Line3D& operator=(const Line3D&) = delete;
 
     // void Line3D::addImage(...), line3D.h:104-108.  Image: anything with .cols/.rows; Mat3: K(r,c);
-    // Vec3: t(i); Seg: s[0..3] (cv::Vec4f).  `line_segments` must be given (LSD detection is outside
-    // the accelerated path).  [multithreading safe like the reference]
+    // Vec3: t(i); Seg: s[0..3] (cv::Vec4f).  Empty `line_segments` and an image with pixels (.data, .step, .type() as
+    // cv::Mat or Image8U has them): the segments are detected on the GPU, or read from the segment cache with
+    // load_segments (line3D.cc:168-173, 243-370).  The image must already be undistorted (Line3D::undistortImage is not
+    // part of this library).  A size-only image (ImageSize) needs its segments.  [multithreading safe like the reference;
+    // detection holds the context mutex, so image views added from several threads are detected one after another:
+    // about 7 s per 3072x2304 image.  A front end with many images detects them in one batch with
+    // l3d_detect_view_segments and hands each view its segments -- the batch costs about what one image does.]
     template <class Image, class Mat3, class Vec3, class Seg>
     void addImage(const unsigned int camID, const Image& image, const Mat3& K, const Mat3& R, const Vec3& t,
                   const float median_depth, const std::list<unsigned int>& wps_or_neighbors,
@@ -69,15 +97,31 @@ public:
             for (int j = 0; j < 3; ++j) { k[3 * i + j] = K(i, j); r[3 * i + j] = R(i, j); }
             tt[i] = t(i);
         }
+        std::vector<uint32_t> nb(wps_or_neighbors.begin(), wps_or_neighbors.end());
+        if constexpr (detail::has_pixels<Image>::value) {
+            if (line_segments.empty()) {
+                const int ty = image.type();
+                const l3d_image im{(const uint8_t*)image.data, (uint32_t)image.cols, (uint32_t)image.rows,
+                                   ty == 0 ? 1u : ty == 16 ? 3u : 0u, (uint32_t)(size_t)image.step};
+                const l3d_detect_options o{output_folder_.c_str(), load_segments_ ? 1 : 0, max_img_width_, max_line_segments_};
+                uint32_t n = 0;     // this view's own segment count, set by the call that added it
+                const int rc = (neighbors_by_worldpoints_ ? l3d_add_view_image_worldpoints : l3d_add_view_image)(
+                    ctx_, camID, &im, &o, k, r, tt, median_depth, nb.data(), (uint32_t)nb.size(), &n);
+                if (rc == L3D_ERR_NO_SEGMENTS)
+                    std::cout << "[L3D++] WARNING: no line segments found in image [" << camID << "]!" << std::endl;
+                else if (rc != L3D_OK) std::cout << prefix_err_ << "view [" << camID << "]: " << l3d_last_error() << std::endl;
+                else { std::lock_guard<std::mutex> lk(lines_mu_); num_lines_[camID] = n; }
+                return;
+            }
+        }
         std::vector<float> segs(4 * line_segments.size());
         for (size_t i = 0; i < line_segments.size(); ++i)
             for (int j = 0; j < 4; ++j) segs[4 * i + j] = line_segments[i][j];
-        std::vector<uint32_t> nb(wps_or_neighbors.begin(), wps_or_neighbors.end());
         const int rc = (neighbors_by_worldpoints_ ? l3d_add_view_worldpoints : l3d_add_view)(
             ctx_, camID, segs.data(), (uint32_t)line_segments.size(), k, r, tt, (uint32_t)image.cols, (uint32_t)image.rows,
             median_depth, nb.data(), (uint32_t)nb.size());
         if (rc != L3D_OK) std::cout << prefix_err_ << "view [" << camID << "]: " << l3d_last_error() << std::endl;
-        else num_lines_[camID] = (uint32_t)line_segments.size();
+        else { std::lock_guard<std::mutex> lk(lines_mu_); num_lines_[camID] = (uint32_t)line_segments.size(); }
     }
 
     // void Line3D::matchImages(...), line3D.h:143-148
@@ -189,20 +233,25 @@ public:
             std::cout << prefix_ << "WARNING: " << l3d_last_error() << std::endl;
     }
 
-    size_t numImages() const { return num_lines_.size(); }
+    size_t numImages() const { std::lock_guard<std::mutex> lk(lines_mu_); return num_lines_.size(); }
 
     // matches_[camID] rebuilt in the reference's container type (line3D.h:348)
     std::vector<std::list<l3d_match>> matches(const unsigned int camID) {
         std::vector<std::list<l3d_match>> out;
-        auto f = num_lines_.find(camID);
-        if (f == num_lines_.end()) return out;
+        uint32_t M = 0;
+        {
+            std::lock_guard<std::mutex> lk(lines_mu_);
+            auto f = num_lines_.find(camID);
+            if (f == num_lines_.end()) return out;
+            M = f->second;
+        }
         uint64_t n = 0;
-        std::vector<uint32_t> off(f->second + 1);
+        std::vector<uint32_t> off(M + 1);
         if (l3d_get_matches(ctx_, camID, nullptr, 0, off.data(), &n) != L3D_OK) return out;
         std::vector<l3d_match> flat(n);
         if (n) l3d_get_matches(ctx_, camID, flat.data(), n, off.data(), &n);
-        out.resize(f->second);
-        for (uint32_t s = 0; s < f->second; ++s) out[s].assign(flat.begin() + off[s], flat.begin() + off[s + 1]);
+        out.resize(M);
+        for (uint32_t s = 0; s < M; ++s) out[s].assign(flat.begin() + off[s], flat.begin() + off[s + 1]);
         return out;
     }
 
@@ -234,9 +283,13 @@ public:
 
 private:
     l3d_ctx* ctx_ = nullptr;
+    std::string output_folder_;
+    bool load_segments_ = true;
     int max_img_width_ = -1;
+    unsigned int max_line_segments_ = 3000;
     bool neighbors_by_worldpoints_ = false;
-    std::map<unsigned int, uint32_t> num_lines_;
+    std::map<unsigned int, uint32_t> num_lines_;    // segments per added view (addImage may run on several threads)
+    mutable std::mutex lines_mu_;
     std::string prefix_, prefix_err_;
 };
 

@@ -27,6 +27,7 @@ SLOT_DTYPE = np.dtype([
 FLOAT4_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("w", "<f4")])
 assert MATCH_DTYPE.itemsize == 40 and SLOT_DTYPE.itemsize == 32 and SEGMENT3D_DTYPE.itemsize == 80
 EMPTY = 0xFFFFFFFF
+L3D_ERR_NO_SEGMENTS = -5
 
 
 class MatchParams(C.Structure):
@@ -62,6 +63,25 @@ class LineOptStats(C.Structure):
                 ("cost_before", C.c_double), ("cost_after", C.c_double), ("kernel_ms", C.c_float), ("reserved", C.c_uint32)]
 
 
+class Image(C.Structure):
+    """l3d_image (include/l3dpp_hip.h)"""
+    _fields_ = [("data", C.c_void_p), ("cols", C.c_uint32), ("rows", C.c_uint32), ("channels", C.c_uint32),
+                ("row_stride", C.c_uint32)]
+
+
+class DetectOptions(C.Structure):
+    """l3d_detect_options (include/l3dpp_hip.h)"""
+    _fields_ = [("output_folder", C.c_char_p), ("load_segments", C.c_int32), ("max_image_width", C.c_int32),
+                ("max_line_segments", C.c_uint32)]
+
+
+class DetectStats(C.Structure):
+    """l3d_detect_stats (include/l3dpp_hip.h)"""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("raw_segments", C.c_uint32), ("segments", C.c_uint32),
+                ("from_cache", C.c_uint32), ("seeds", C.c_uint32), ("nfa_evals", C.c_uint32), ("reserved", C.c_uint32),
+                ("max_grad", C.c_double)]
+
+
 EXPORTS = [
     "l3d_last_error", "l3d_build_info", "l3d_create", "l3d_destroy", "l3d_add_view", "l3d_match_images",
     "l3d_match_begin", "l3d_num_pairs", "l3d_get_pairs", "l3d_match_pairs", "l3d_slot_buffer", "l3d_match_finish",
@@ -80,6 +100,8 @@ EXPORTS = [
     "l3d_sfm_open_colmap", "l3d_sfm_open_bundler", "l3d_sfm_num_images", "l3d_sfm_get_image", "l3d_sfm_get_worldpoints",
     "l3d_sfm_close", "l3d_debug_counter", "l3d_affinity_shard_begin", "l3d_affinity_shard_finish", "l3d_affinity_shard_abort", "l3d_shard_options",
     "l3d_line_opt_stats", "l3d_line_to_cayley", "l3d_cayley_to_segment", "l3d_line_opt_eval", "l3d_get_fresh_hyp",
+    "l3d_detect_segments", "l3d_detect_view_segments", "l3d_get_detected_segments", "l3d_get_detect_stats",
+    "l3d_add_view_image", "l3d_add_view_image_worldpoints",
 ]
 
 _lib = None
@@ -177,6 +199,14 @@ def load():
     L.l3d_cayley_to_segment.argtypes = [vp, vp, vp, vp, vp]
     L.l3d_line_opt_eval.argtypes = [i32, u32, vp, vp, vp, vp, vp, vp, vp]
     L.l3d_selftest_arith.argtypes = [i32, u64, u64, vp]
+    L.l3d_detect_segments.argtypes = [vp, u32, vp, i32, u32, vp]
+    L.l3d_detect_view_segments.argtypes = [vp, u32, vp, vp, C.POINTER(DetectOptions), vp]
+    L.l3d_get_detected_segments.argtypes = [vp, vp, u64, C.POINTER(u64)]
+    L.l3d_get_detect_stats.argtypes = [vp, vp, u32, C.POINTER(u32)]
+    L.l3d_add_view_image.argtypes = [vp, u32, C.POINTER(Image), C.POINTER(DetectOptions), vp, vp, vp, f32, vp, u32,
+                                     C.POINTER(u32)]
+    L.l3d_add_view_image_worldpoints.argtypes = [vp, u32, C.POINTER(Image), C.POINTER(DetectOptions), vp, vp, vp, f32,
+                                                 vp, u32, C.POINTER(u32)]
     L.l3d_score_matches.argtypes = [i32, vp, u32, vp, vp, vp, u32, vp, vp, f32, f32, vp]
     for name in EXPORTS:
         fn = getattr(L, name)

@@ -10,10 +10,11 @@ bench and torch.distributed plumbing -- the C++ facade over the same C-ABI is
 include/line3dpp/line3D.h.
 """
 import ctypes as C
+import threading
 
 import numpy as np
 
-from . import _lib
+from . import _lib, lsd
 from ._lib import (CLEDGE_DTYPE, EMPTY, FLOAT4_DTYPE, MATCH_DTYPE, SEGMENT2D_DTYPE, SEGMENT3D_DTYPE, SLOT_DTYPE,
                    MatchParams, Timings, ptr)
 
@@ -34,6 +35,13 @@ class Line3D:
         # neighbors_by_worldpoints (line3D.cc:6-69): addImage's list is a WORLDPOINT list and the visual neighbours are found
         # from the worldpoint overlap at every matchImages (Line3D::findVisualNeighborsFromWPs, line3D.cc:578-699)
         self.neighbors_by_worldpoints = bool(neighbors_by_worldpoints)
+        # what addImage's detection reads (line3D.cc:6-12): the cache folder <output_folder>/L3D++_data/, whether the
+        # segment cache is used, the max-width downscale and the cap on segments per image
+        self.output_folder = str(output_folder)
+        self.load_segments = bool(load_segments)
+        self.max_img_width = int(max_img_width)
+        self.max_line_segments = int(max_line_segments)
+        self._detect_lock = threading.Lock()
         self.L = _lib.load()
         self.verbose = verbose
         self.last_status = 0
@@ -63,19 +71,74 @@ class Line3D:
         return rc == 0
 
     # Line3D::addImage(camID, image, K, R, t, median_depth, wps_or_neighbors, line_segments), line3D.h:104-108
-    def addImage(self, camID, image_size, K, R, t, median_depth, wps_or_neighbors, line_segments):
-        """image_size = (cols, rows) stands in for the cv::Mat, which only contributes its size once
-        `line_segments` are given (line3D.cc:119,198)."""
+    def addImage(self, camID, image, K, R, t, median_depth, wps_or_neighbors, line_segments=()):
+        """image = a (cols, rows) tuple, which stands in for the cv::Mat when `line_segments` are given (the image then
+        only contributes its size, line3D.cc:119,198), or a uint8 HxW / HxWx3 ndarray (undistorted; first channel = R).
+        An ndarray with no segments is detected on the GPU, or loaded from the segment cache (line3D.cc:168-173)."""
         segs = np.ascontiguousarray(line_segments, np.float32).reshape(-1, 4)
         K = np.ascontiguousarray(K, np.float64).reshape(3, 3)
         R = np.ascontiguousarray(R, np.float64).reshape(3, 3)
         t = np.ascontiguousarray(t, np.float64).reshape(3)
         nb = np.ascontiguousarray(list(wps_or_neighbors), np.uint32)
+        if isinstance(image, np.ndarray):
+            img, keep = lsd.as_image(image)
+            if len(segs) == 0:
+                add = self.L.l3d_add_view_image_worldpoints if self.neighbors_by_worldpoints else self.L.l3d_add_view_image
+                opts = self._detect_options()
+                n_segs = C.c_uint32(0)          # this view's own count, set by the call that added it
+                with self._detect_lock:         # keeps addImages' detection and the fetch of its segments together
+                    rc = add(self.h, int(camID), C.byref(img), C.byref(opts), ptr(K), ptr(R), ptr(t), float(median_depth),
+                             ptr(nb), len(nb), C.byref(n_segs))
+                if rc == _lib.L3D_ERR_NO_SEGMENTS and len(nb) and max(img.cols, img.rows) >= 800:
+                    self.last_status = rc
+                    print(f"{self.PREFIX}WARNING: no line segments found in image [{camID}]!")
+                    return
+                if self._check(rc, f"addImage [{camID}]"):
+                    self._M[int(camID)] = int(n_segs.value)
+                return
+            image_size = (img.cols, img.rows)
+        else:
+            image_size = image
         add = self.L.l3d_add_view_worldpoints if self.neighbors_by_worldpoints else self.L.l3d_add_view
         rc = add(self.h, int(camID), ptr(segs), len(segs), ptr(K), ptr(R), ptr(t),
                  int(image_size[0]), int(image_size[1]), float(median_depth), ptr(nb), len(nb))
         if self._check(rc, f"addImage [{camID}]"):
             self._M[int(camID)] = len(segs)
+
+    def _detect_options(self):
+        folder = self.output_folder.encode()
+        opts = _lib.DetectOptions(folder, int(self.load_segments), self.max_img_width, self.max_line_segments)
+        opts._keep = folder             # the bytes behind output_folder live as long as the options
+        return opts
+
+    def addImages(self, camIDs, images, Ks, Rs, ts, median_depths, wps_or_neighbors):
+        """addImage for many images with no segments, with ONE detection batch for all of them (a front end that reads
+        every image first).  Views are added in the order given, each exactly as addImage would add it."""
+        camIDs = [int(c) for c in camIDs]
+        images = list(images)
+        lists = [list(x) for x in wps_or_neighbors]
+        # addImage's checks before detection (line3D.cc:119-158): such views are handed on without detecting them
+        go = [i for i in range(len(images)) if max(images[i].shape[:2]) >= 800 and len(lists[i]) and camIDs[i] not in self._M
+              and camIDs[i] not in camIDs[:i]]
+        found = {}
+        if go:
+            arr, keep = lsd.image_array([images[i] for i in go])
+            cams = np.array([camIDs[i] for i in go], np.uint32)
+            counts = np.zeros(len(go), np.uint32)
+            opts = self._detect_options()
+            with self._detect_lock:         # the detection and the fetch of its segments, with no other detection between
+                rc = self.L.l3d_detect_view_segments(self.h, len(go), ptr(cams), arr, C.byref(opts), ptr(counts))
+                if not self._check(rc, "addImages"):
+                    return
+                found = dict(zip(go, lsd.fetch(self.L, self.h, counts)))
+        for i in range(len(images)):
+            im = np.asarray(images[i])
+            if i in found and len(found[i]) == 0:
+                self.last_status = _lib.L3D_ERR_NO_SEGMENTS
+                print(f"{self.PREFIX}WARNING: no line segments found in image [{camIDs[i]}]!")
+                continue
+            self.addImage(camIDs[i], (im.shape[1], im.shape[0]), Ks[i], Rs[i], ts[i], median_depths[i], lists[i],
+                          found.get(i, np.zeros((0, 4), np.float32)))
 
     def add_scene(self, scene):
         for v in scene.views:

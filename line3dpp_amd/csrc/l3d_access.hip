@@ -2,6 +2,7 @@
 // SparseMatrix COO form in the reference's own layouts (commons.h:186-203, segment3D.h:99-115, clustering.h:47-51,
 // sparsematrix.cc:8-60), per-view k / median depth, timings.
 #include "l3d_ctx.h"
+#include "l3d_lsd.h"
 
 using namespace l3d;
 
@@ -166,6 +167,8 @@ unsigned long long l3d_debug_counter(const char* name) {
     if (name && std::string(name) == "csr_global_launches") return g_csr_global_launches.load(std::memory_order_relaxed);
     if (name && std::string(name) == "knn_replay_calls") return g_knn_replay_calls.load(std::memory_order_relaxed);
     if (name && std::string(name) == "keep_all_repeats") return g_keep_all_repeats.load(std::memory_order_relaxed);
+    if (name && std::string(name) == "lsd_images_detected") return g_lsd_images_detected.load(std::memory_order_relaxed);
+    if (name && std::string(name) == "lsd_cache_loads") return g_lsd_cache_loads.load(std::memory_order_relaxed);
     return ~0ull;
 }
 

@@ -294,4 +294,8 @@ struct l3d_ctx {
     int timing_level = 1;
     bool ev_on(int k) const { return timing_level >= 2 || (timing_level == 1 && (k == 4 || k == 5)); }
     l3d_timings tm{};
+    // the last line-segment detection (l3d_lsd.hip): segments of every image, image after image
+    std::vector<float> det_segs;
+    std::vector<uint32_t> det_counts;
+    std::vector<l3d_detect_stats> det_stats;
 };

@@ -1,0 +1,321 @@
+// l3d_lsd.hip -- host side of line-segment detection: Line3D::detectLineSegments (line3D.cc:243-370) for a batch of
+// images.  The image checks, the max-width downscale geometry, the arena of device buffers, the launch of k_lsd.hip's
+// stages, then per image the upscale, the length filter, the length order (the reference's std::priority_queue) and
+// the cap; the segment cache of addImage (line3D.cc:295-309, 362-366).  DESIGN §11.
+#include <sys/stat.h>
+
+#include <array>
+#include <atomic>
+#include <cmath>
+#include <queue>
+
+#include "l3d_ctx.h"
+#include "l3d_lsd.h"
+
+namespace l3d {
+
+std::atomic<uint64_t> g_lsd_images_detected{0};   // test hooks (l3d_debug_counter)
+std::atomic<uint64_t> g_lsd_cache_loads{0};
+
+namespace {
+
+constexpr uint32_t kDefMaxNumSegments = 3000;     // L3D_DEF_MAX_NUM_SEGMENTS: the cache name carries this, not the cap
+constexpr float kMinLineLengthFactor = 0.005f;    // L3D_DEF_MIN_LINE_LENGTH_FACTOR
+
+// SegmentData2D and its comparator (commons.h:132-156): the heap looks at the length only
+struct Seg2D { float p1x, p1y, p2x, p2y, length; };
+struct SegLess { bool operator()(const Seg2D& a, const Seg2D& b) const { return a.length < b.length; } };
+
+// cv::resize(src, dst, Size(), f, f): dsize = round(n * f)
+uint32_t resize_size(uint32_t n, double f) { return (uint32_t)std::nearbyint((double)n * f); }
+
+struct Geometry {
+    uint32_t gw, gh, sw, sh;
+    bool down;
+    double down_scale;    // 1 / s
+    float upx, upy;
+};
+
+Geometry geometry(const l3d_image& im, int max_image_width) {
+    Geometry g{im.cols, im.rows, 0, 0, false, 1.0, 1.0f, 1.0f};
+    const int max_dim = (int)std::max(im.cols, im.rows);
+    if (max_image_width > 0 && max_dim > max_image_width) {
+        const float s = float(max_image_width) / float(max_dim);
+        g.gw = resize_size(im.cols, (double)s);
+        g.gh = resize_size(im.rows, (double)s);
+        g.down = true;
+        g.down_scale = 1.0 / (double)s;
+        g.upx = float(im.cols) / float(g.gw);
+        g.upy = float(im.rows) / float(g.gh);
+    }
+    g.sw = resize_size(g.gw, kLsdScale);
+    g.sh = resize_size(g.gh, kLsdScale);
+    return g;
+}
+
+int check_image(const l3d_image& im) {
+    if (im.channels != 1 && im.channels != 3)
+        return fail(L3D_ERR_ARG, "image type not supported! must be CV_8U (gray) or CV_8UC3 (RGB)!");
+    if (!im.data || im.cols < 2 || im.rows < 2 || im.row_stride < im.cols * im.channels)
+        return fail(L3D_ERR_ARG, "empty image or row stride smaller than a row");
+    if ((uint64_t)im.cols * im.rows * 3 >= (1ull << 31)) return fail(L3D_ERR_LIMIT, "image larger than 2^31 bytes");
+    return L3D_OK;
+}
+
+// every stage needs at least 2 x 2 pixels (the resample maps index n - 1)
+int check_geometry(const Geometry& g) {
+    if (std::min({g.gw, g.gh, g.sw, g.sh}) < 2) return fail(L3D_ERR_ARG, "image too small for line-segment detection");
+    return L3D_OK;
+}
+
+size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// LSD on the device for every image; raw[i] = its segments in detection order (LSD-input pixels), stats filled
+int run_lsd(l3d_ctx* c, const std::vector<const l3d_image*>& ims, const std::vector<Geometry>& geo,
+            std::vector<std::vector<float4>>& raw, std::vector<l3d_detect_stats>& stats) {
+    const uint32_t n = (uint32_t)ims.size();
+    raw.assign(n, {});
+    if (!n) return L3D_OK;
+    std::vector<LsdImage> d(n);
+    size_t bytes = align256(n * sizeof(LsdImage)) + align256(n * sizeof(LsdResult));
+    uint32_t max_src = 0, max_small = 0, max_scaled = 0;
+    // first pass: offsets inside the arena (pointers are offsets until the arena exists)
+    std::vector<std::array<size_t, 10>> off(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        const l3d_image& im = *ims[i];
+        const Geometry& g = geo[i];
+        const size_t src = (size_t)im.cols * im.rows, sm = (size_t)g.gw * g.gh, sc = (size_t)g.sw * g.sh;
+        LsdImage& I = d[i];
+        I.cols = im.cols; I.rows = im.rows; I.channels = im.channels;
+        I.gw = g.gw; I.gh = g.gh; I.sw = g.sw; I.sh = g.sh;
+        I.down = g.down; I.down_scale = g.down_scale;
+        // every accepted segment keeps at least two pixels of its region marked used for good: at most sc / 2 of them
+        I.out_cap = (uint32_t)(sc / 2 + 1);
+        I.log_nt = 5 * (std::log10(double(g.sw)) + std::log10(double(g.sh))) / 2 + std::log10(11.0);
+        I.min_reg_size = int(-I.log_nt / std::log10(22.5 / 180));
+        const size_t sizes[10] = {src * im.channels, src, g.down ? sm : 0, sm * 8, sm * 8, sc * 4, sc * 8, sc,
+                                  sc * sizeof(int2), (size_t)I.out_cap * sizeof(float4)};
+        for (int k = 0; k < 10; ++k) { off[i][k] = bytes; bytes += align256(sizes[k]); }
+        max_src = std::max(max_src, (uint32_t)src);
+        max_small = std::max(max_small, (uint32_t)sm);
+        max_scaled = std::max(max_scaled, (uint32_t)sc);
+    }
+    DevBuf<char> arena;
+    struct Guard { DevBuf<char>& a; hipStream_t st; ~Guard() { (void)hipStreamSynchronize(st); a.release(); } } guard{arena, c->stream};
+    L3D_HIP_CHECK(arena.reserve(bytes));
+    char* base = arena.p;
+    LsdImage* d_imgs = (LsdImage*)base;
+    LsdResult* d_res = (LsdResult*)(base + align256(n * sizeof(LsdImage)));
+    for (uint32_t i = 0; i < n; ++i) {
+        LsdImage& I = d[i];
+        const auto& o = off[i];
+        I.src = (const uint8_t*)(base + o[0]);
+        I.gray = (uint8_t*)(base + o[1]);
+        I.small = I.down ? (uint8_t*)(base + o[2]) : I.gray;
+        I.tmp = (double*)(base + o[3]);
+        I.blur = (double*)(base + o[4]);
+        I.deg = (float*)(base + o[5]);
+        I.mod = (double*)(base + o[6]);
+        I.used = (uint8_t*)(base + o[7]);
+        I.reg = (int2*)(base + o[8]);
+        I.out = (float4*)(base + o[9]);
+        const l3d_image& im = *ims[i];
+        const size_t row = (size_t)im.cols * im.channels;
+        L3D_HIP_CHECK(hipMemcpy2DAsync((void*)I.src, row, im.data, im.row_stride, row, im.rows, hipMemcpyHostToDevice, c->stream));
+    }
+    L3D_HIP_CHECK(hipMemcpyAsync(d_imgs, d.data(), n * sizeof(LsdImage), hipMemcpyHostToDevice, c->stream));
+    L3D_HIP_CHECK(hipMemsetAsync(d_res, 0, n * sizeof(LsdResult), c->stream));
+    LsdConst k{};
+    {
+        // getGaussianKernel(7, sigma_scale / scale): exp(scale2X x x), normalised by the reciprocal of the sum
+        const double sigma = 0.6 / kLsdScale, scale2x = -0.5 / (sigma * sigma);
+        double sum = 0;
+        for (int t = 0; t < kLsdTaps; ++t) {
+            const double x = t - (kLsdTaps - 1) * 0.5;
+            k.gauss[t] = std::exp(scale2x * x * x);
+            sum += k.gauss[t];
+        }
+        sum = 1. / sum;
+        for (int t = 0; t < kLsdTaps; ++t) k.gauss[t] *= sum;
+        k.prec = M_PI * 22.5 / 180;
+        k.p = 22.5 / 180;
+        k.rho = 2.0 / std::sin(k.prec);
+    }
+    L3D_HIP_CHECK(launch_lsd(d_imgs, n, max_src, max_small, max_scaled, k, d_res, c->stream));
+    std::vector<LsdResult> res(n);
+    L3D_HIP_CHECK(hipMemcpyAsync(res.data(), d_res, n * sizeof(LsdResult), hipMemcpyDeviceToHost, c->stream));
+    L3D_HIP_CHECK(hipStreamSynchronize(c->stream));
+    for (uint32_t i = 0; i < n; ++i) {
+        if (res[i].overflow) return fail(L3D_ERR_LIMIT, "line-segment detection: output capacity exceeded");
+        raw[i].resize(res[i].n);
+        if (res[i].n)
+            L3D_HIP_CHECK(hipMemcpyAsync(raw[i].data(), d[i].out, res[i].n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+        l3d_detect_stats& s = stats[i];
+        s.width = geo[i].gw; s.height = geo[i].gh;
+        s.raw_segments = res[i].n; s.seeds = res[i].seeds; s.nfa_evals = res[i].nfa_evals;
+        s.max_grad = -1.0;
+        if (res[i].max_grad_bits) std::memcpy(&s.max_grad, &res[i].max_grad_bits, sizeof(double));
+    }
+    L3D_HIP_CHECK(hipStreamSynchronize(c->stream));
+    g_lsd_images_detected += n;
+    return L3D_OK;
+}
+
+// line3D.cc:318-360: upscale, keep length > 0.005 diag (diag of the ORIGINAL image, float), longest first, cap
+void finish(const l3d_image& im, const Geometry& g, const std::vector<float4>& raw, uint32_t max_segments,
+            std::vector<float>& out) {
+    const float diag = sqrtf(float(im.rows * im.rows) + float(im.cols * im.cols));
+    const float min_len = diag * kMinLineLengthFactor;
+    std::priority_queue<Seg2D, std::vector<Seg2D>, SegLess> sorted;
+    for (const float4& d : raw) {
+        Seg2D s;
+        s.p1x = d.x * g.upx; s.p1y = d.y * g.upy;
+        s.p2x = d.z * g.upx; s.p2y = d.w * g.upy;
+        const float dx = s.p1x - s.p2x, dy = s.p1y - s.p2y;
+        s.length = sqrtf(dx * dx + dy * dy);
+        if (s.length > min_len) sorted.push(s);
+    }
+    const size_t m = std::min<size_t>(sorted.size(), max_segments);
+    for (size_t pos = 0; pos < m; ++pos) {
+        const Seg2D s = sorted.top();
+        sorted.pop();
+        out.insert(out.end(), {s.p1x, s.p1y, s.p2x, s.p2y});
+    }
+}
+
+std::string cache_path(const l3d_detect_options& o, uint32_t cam, const Geometry& g) {
+    char name[128];
+    std::snprintf(name, sizeof name, "segments_L3D++_%u_%ux%u_%u.bin", cam, g.gw, g.gh, kDefMaxNumSegments);
+    return std::string(o.output_folder ? o.output_folder : "") + "/L3D++_data/" + name;
+}
+
+int detect(l3d_ctx* c, uint32_t n, const uint32_t* cams, const l3d_image* images, int max_image_width,
+           uint32_t max_segments, const l3d_detect_options* cache, uint32_t* counts) {
+    if (!c || (n && !images)) return fail(L3D_ERR_ARG, "null argument");
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    for (uint32_t i = 0; i < n; ++i) if (int rc = check_image(images[i])) return rc;
+    (void)hipSetDevice(c->device);
+    std::vector<Geometry> geo(n);
+    std::vector<l3d_detect_stats> stats(n, l3d_detect_stats{});
+    std::vector<std::vector<float>> segs(n);
+    std::vector<const l3d_image*> todo;
+    std::vector<uint32_t> todo_idx;
+    for (uint32_t i = 0; i < n; ++i) {
+        geo[i] = geometry(images[i], max_image_width);
+        if (int rc = check_geometry(geo[i])) return rc;
+        if (cache && cache->load_segments) {
+            const std::string path = cache_path(*cache, cams[i], geo[i]);
+            std::ifstream probe(path, std::ios::binary);
+            if (probe) {
+                probe.close();
+                uint32_t m = 0;
+                if (int rc = l3d_read_segment_cache(path.c_str(), nullptr, 0, &m)) return rc;
+                segs[i].resize(4 * (size_t)m);
+                if (int rc = l3d_read_segment_cache(path.c_str(), segs[i].data(), m, &m)) return rc;
+                stats[i].width = geo[i].gw; stats[i].height = geo[i].gh;
+                stats[i].from_cache = 1;
+                stats[i].max_grad = -1.0;
+                ++g_lsd_cache_loads;
+                continue;
+            }
+        }
+        todo.push_back(&images[i]);
+        todo_idx.push_back(i);
+    }
+    std::vector<Geometry> tgeo;
+    std::vector<l3d_detect_stats> tstats(todo.size(), l3d_detect_stats{});
+    for (uint32_t i : todo_idx) tgeo.push_back(geo[i]);
+    std::vector<std::vector<float4>> raw;
+    if (int rc = run_lsd(c, todo, tgeo, raw, tstats)) return rc;
+    for (size_t j = 0; j < todo.size(); ++j) {
+        const uint32_t i = todo_idx[j];
+        stats[i] = tstats[j];
+        finish(images[i], geo[i], raw[j], max_segments, segs[i]);
+        // line3D.cc:362-366: stored only when segments were found
+        if (cache && cache->load_segments && !segs[i].empty()) {
+            const std::string dir = std::string(cache->output_folder ? cache->output_folder : "") + "/L3D++_data";
+            ::mkdir(dir.c_str(), 0755);
+            if (int rc = l3d_write_segment_cache(cache_path(*cache, cams[i], geo[i]).c_str(), segs[i].data(),
+                                                 (uint32_t)(segs[i].size() / 4)))
+                return rc;
+        }
+    }
+    c->det_segs.clear();
+    c->det_counts.assign(n, 0);
+    for (uint32_t i = 0; i < n; ++i) {
+        stats[i].segments = (uint32_t)(segs[i].size() / 4);
+        c->det_counts[i] = stats[i].segments;
+        if (counts) counts[i] = stats[i].segments;
+        c->det_segs.insert(c->det_segs.end(), segs[i].begin(), segs[i].end());
+    }
+    c->det_stats = stats;
+    return L3D_OK;
+}
+
+int add_view_image(l3d_ctx* c, uint32_t camID, const l3d_image* image, const l3d_detect_options* opts, const double K[9],
+                   const double R[9], const double t[3], float median_depth, const uint32_t* list, uint32_t n_list,
+                   bool by_worldpoints, uint32_t* n_segments) {
+    if (n_segments) *n_segments = 0;
+    if (!c || !image || !opts || !K || !R || !t) return fail(L3D_ERR_ARG, "null argument");
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    // the checks addImage makes before it detects (line3D.cc:119-158): no detection for a view that cannot be added
+    auto add = [&](const float* s, uint32_t m) {
+        return by_worldpoints ? l3d_add_view_worldpoints(c, camID, s, m, K, R, t, image->cols, image->rows, median_depth, list, n_list)
+                              : l3d_add_view(c, camID, s, m, K, R, t, image->cols, image->rows, median_depth, list, n_list);
+    };
+    if (std::max(image->cols, image->rows) < 800 || c->views.count(camID) || !n_list || !list) return add(nullptr, 0);
+    uint32_t m = 0;
+    if (int rc = detect(c, 1, &camID, image, opts->max_image_width, opts->max_line_segments, opts, &m)) return rc;
+    if (!m) return fail(L3D_ERR_NO_SEGMENTS, "no line segments found in image");
+    const int rc = add(c->det_segs.data(), m);
+    if (rc == L3D_OK && n_segments) *n_segments = m;     // still under the context mutex: this view's own count
+    return rc;
+}
+
+}  // namespace
+}  // namespace l3d
+
+using namespace l3d;
+
+extern "C" {
+
+int l3d_detect_segments(l3d_ctx* c, uint32_t n_images, const l3d_image* images, int max_image_width,
+                        uint32_t max_segments, uint32_t* counts) {
+    return detect(c, n_images, nullptr, images, max_image_width, max_segments, nullptr, counts);
+}
+
+int l3d_detect_view_segments(l3d_ctx* c, uint32_t n_images, const uint32_t* camIDs, const l3d_image* images,
+                             const l3d_detect_options* opts, uint32_t* counts) {
+    if (!opts || (n_images && !camIDs)) return fail(L3D_ERR_ARG, "null argument");
+    return detect(c, n_images, camIDs, images, opts->max_image_width, opts->max_line_segments, opts, counts);
+}
+
+int l3d_get_detected_segments(l3d_ctx* c, float* segs4, uint64_t cap, uint64_t* n) {
+    if (!c || !n) return fail(L3D_ERR_ARG, "null argument");
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    *n = c->det_segs.size() / 4;
+    if (segs4) std::memcpy(segs4, c->det_segs.data(), std::min<uint64_t>(cap, *n) * 16);
+    return L3D_OK;
+}
+
+int l3d_get_detect_stats(l3d_ctx* c, l3d_detect_stats* out, uint32_t cap, uint32_t* n) {
+    if (!c || !n) return fail(L3D_ERR_ARG, "null argument");
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    *n = (uint32_t)c->det_stats.size();
+    if (out) std::memcpy(out, c->det_stats.data(), std::min<uint32_t>(cap, *n) * sizeof(l3d_detect_stats));
+    return L3D_OK;
+}
+
+int l3d_add_view_image(l3d_ctx* c, uint32_t camID, const l3d_image* image, const l3d_detect_options* opts,
+                       const double K[9], const double R[9], const double t[3], float median_depth,
+                       const uint32_t* neighbors, uint32_t n_neighbors, uint32_t* n_segments) {
+    return add_view_image(c, camID, image, opts, K, R, t, median_depth, neighbors, n_neighbors, false, n_segments);
+}
+
+int l3d_add_view_image_worldpoints(l3d_ctx* c, uint32_t camID, const l3d_image* image, const l3d_detect_options* opts,
+                                   const double K[9], const double R[9], const double t[3], float median_depth,
+                                   const uint32_t* worldpoints, uint32_t n_worldpoints, uint32_t* n_segments) {
+    return add_view_image(c, camID, image, opts, K, R, t, median_depth, worldpoints, n_worldpoints, true, n_segments);
+}
+
+}  // extern "C"

@@ -1,0 +1,88 @@
+"""Line-segment detection: Line3D::detectLineSegments (line3D.cc:243-370) on the GPU (k_lsd.hip), batched over images.
+
+`detect_line_segments` is the stage on its own: grey conversion, the max-width downscale, LSD (lsd_opencv.cpp,
+LSD_REFINE_ADV), the length filter, the length order and the cap.  `Line3D.addImage` / `addImages` (api.py) run the
+same stage, with the segment cache, when they are given an image and no segments.  Images must already be undistorted.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._lib import ptr
+
+L3D_DEF_MAX_NUM_SEGMENTS = 3000
+
+
+def as_image(img):
+    """uint8 HxW (grey) or HxWx3 (first channel = R) ndarray -> (l3d_image, the contiguous array it points into)"""
+    a = np.asarray(img)
+    if a.dtype != np.uint8 or a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] != 3):
+        raise TypeError("image type not supported! must be uint8 HxW (gray) or HxWx3 (RGB)")
+    a = np.ascontiguousarray(a)
+    ch = 1 if a.ndim == 2 else 3
+    return _lib.Image(a.ctypes.data, a.shape[1], a.shape[0], ch, a.shape[1] * ch), a
+
+
+def image_array(images):
+    """-> (ctypes array of l3d_image, arrays that must stay alive while it is used)"""
+    imgs, keep = zip(*[as_image(im) for im in images]) if len(images) else ((), ())
+    arr = (_lib.Image * max(len(imgs), 1))(*imgs)
+    return arr, keep
+
+
+def fetch(L, h, counts):
+    """the segments of the last detection on context h, split per image"""
+    n = C.c_uint64(0)
+    L.l3d_get_detected_segments(h, None, 0, C.byref(n))
+    flat = np.zeros((max(n.value, 1), 4), np.float32)
+    if n.value:
+        L.l3d_get_detected_segments(h, ptr(flat), n.value, C.byref(n))
+    out, o = [], 0
+    for c in counts:
+        out.append(flat[o:o + int(c)].copy())
+        o += int(c)
+    return out
+
+
+def detect_line_segments(images, max_image_width=-1, max_segments=L3D_DEF_MAX_NUM_SEGMENTS, device=0, stats=False):
+    """LSD on a list of images in one batch -> list of [n,4] float32 (x1, y1, x2, y2), longest first, as
+    Line3D::detectLineSegments hands them to the view.  stats=True also returns the per-image l3d_detect_stats."""
+    L = _lib.load()
+    images = list(images)
+    h = L.l3d_create(int(device), None)
+    if not h:
+        raise RuntimeError("l3d_create failed: " + _lib.last_error())
+    h = C.c_void_p(h)
+    try:
+        arr, keep = image_array(images)
+        counts = np.zeros(max(len(images), 1), np.uint32)
+        rc = L.l3d_detect_segments(h, len(images), arr, int(max_image_width), int(max_segments), ptr(counts))
+        if rc != 0:
+            raise RuntimeError(f"l3d_detect_segments failed [{rc}]: {_lib.last_error()}")
+        segs = fetch(L, h, counts[:len(images)])
+        if not stats:
+            return segs
+        return segs, last_stats(L, h)
+    finally:
+        L.l3d_destroy(h)
+
+
+def last_stats(L, h):
+    n = C.c_uint32(0)
+    L.l3d_get_detect_stats(h, None, 0, C.byref(n))
+    st = (_lib.DetectStats * max(n.value, 1))()
+    L.l3d_get_detect_stats(h, st, n.value, C.byref(n))
+    return [{k: getattr(st[i], k) for k, _ in _lib.DetectStats._fields_ if k != "reserved"} for i in range(n.value)]
+
+
+def read_image_gray(path):
+    """8-bit grey image of a file as cv::imread(path, CV_LOAD_IMAGE_GRAYSCALE) gives it to the reference: for JPEG,
+    libjpeg's own grey decode (the Y channel, through PIL's draft mode) rather than a conversion of the RGB decode."""
+    from PIL import Image
+    with Image.open(path) as im:
+        if im.format == "JPEG":
+            im.draft("L", im.size)
+        if im.mode != "L":
+            im = im.convert("L")
+        return np.asarray(im, np.uint8).copy()
