@@ -181,8 +181,8 @@ int l3d_write_segment_cache(const char* path, const float* segs4, uint32_t n);
 
 /* ---- line-segment detection (Line3D::detectLineSegments, line3D.cc:243-370; GPU: k_lsd.hip) ------------------------
  * An 8-bit image: channels 1 (CV_8U, grey) or 3 (CV_8UC3; converted with CV_RGB2GRAY, the first channel counts as R);
- * any other count is "image type not supported" (L3D_ERR_ARG).  row_stride in bytes (>= cols * channels).  The image
- * must already be undistorted: Line3D::undistortImage is not part of this library. */
+ * any other count is "image type not supported" (L3D_ERR_ARG).  row_stride in bytes (>= cols * channels).  Detection
+ * expects undistorted pixels: a front end that calls Line3D::undistortImage first does so with l3d_undistort_images. */
 typedef struct l3d_image {
     const uint8_t* data;
     uint32_t cols, rows, channels, row_stride;
@@ -230,6 +230,18 @@ int l3d_add_view_image(l3d_ctx*, uint32_t camID, const l3d_image* image, const l
 int l3d_add_view_image_worldpoints(l3d_ctx*, uint32_t camID, const l3d_image* image, const l3d_detect_options* opts,
                                    const double K[9], const double R[9], const double t[3], float median_depth,
                                    const uint32_t* worldpoints, uint32_t n_worldpoints, uint32_t* n_segments);
+
+/* ---- undistortion (Line3D::undistortImage, line3D.cc:83-109; GPU: k_undistort.hip) ---------------------------------
+ * The arguments of undistortImage: K row-major (only fx = K[0], fy = K[4], cx = K[2], cy = K[5] are read: cvK drops
+ * the skew), radial = (k1, k2, k3), tangential = (p1, p2), i.e. OpenCV's (k1, k2, p1, p2, k3).  DESIGN §12 defines the
+ * arithmetic (initUndistortRectifyMap with CV_16SC2 maps, remap INTER_LINEAR with a border of 0).  Images as for
+ * detection (l3d_image: 8-bit, 1 or 3 channels, else L3D_ERR_ARG); a non-finite coefficient or fx, fy, cx, cy, or
+ * fx * fy == 0: L3D_ERR_ARG; a side of 32767 or more: L3D_ERR_LIMIT.  Every image is checked before any is read. */
+typedef struct l3d_distortion { double K[9]; double radial[3]; double tangential[2]; } l3d_distortion;
+/* Line3D::undistortImage (line3D.cc:83-109) for a batch of images in one launch.  out[i] receives rows x
+   cols*channels bytes, packed, and may be the input's own host memory.  Calls on one context are serialised. */
+int l3d_undistort_images(l3d_ctx*, uint32_t n_images, const l3d_image* in, const l3d_distortion* dist,
+                         uint8_t* const* out);
 
 /* Line3D::matchImages (line3D.cc:375-497): the whole call on this context's GPU. */
 int l3d_match_images(l3d_ctx*, const l3d_match_params*);

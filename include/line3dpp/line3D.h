@@ -3,6 +3,7 @@
 //
 //     Line3D(output_folder, load_segments, max_img_width, max_line_segments,
 //            neighbors_by_worldpoints=false, use_GPU=true)
+//     static undistortImage(inImg, outImg, radial_coeffs, tangential_coeffs, K)
 //     addImage(camID, image, K, R, t, median_depth, wps_or_neighbors, line_segments)
 //     matchImages(sigma_position, sigma_angle, num_neighbors, epipolar_overlap, kNN, const_regularization_depth)
 //     computeAffinityMatrix()            // the affinity part of reconstruct3Dlines()
@@ -20,6 +21,7 @@
 #define L3DPP_HIP_FACADE_LINE3D_H_
 
 #include <cstdint>
+#include <cstring>
 #include <iostream>
 #include <list>
 #include <map>
@@ -52,6 +54,44 @@ struct Image8U {
     int type() const { return channels_ == 1 ? 0 : channels_ == 3 ? 16 : -1; }   // CV_8U, CV_8UC3
 };
 
+// owning stand-in for an 8-bit cv::Mat with pixels, for users without OpenCV: what undistortImage writes into (create /
+// release as cv::Mat has them).  It has data, cols, rows, step and type(), so addImage detects on it as it is.
+class ImageBuf8U {
+public:
+    unsigned char* data = nullptr;
+    int cols = 0, rows = 0;
+    size_t step = 0;
+
+    ImageBuf8U() = default;
+    ImageBuf8U(int rows_, int cols_, int type_) { create(rows_, cols_, type_); }
+    ImageBuf8U(const ImageBuf8U& o) : data(nullptr), cols(o.cols), rows(o.rows), step(o.step), buf_(o.buf_), type_(o.type_) {
+        if (!buf_.empty()) data = buf_.data();
+    }
+    ImageBuf8U(ImageBuf8U&& o) noexcept : ImageBuf8U() { swap(o); }
+    ImageBuf8U& operator=(ImageBuf8U o) noexcept { swap(o); return *this; }
+    void swap(ImageBuf8U& o) noexcept {
+        std::swap(data, o.data); std::swap(cols, o.cols); std::swap(rows, o.rows); std::swap(step, o.step);
+        buf_.swap(o.buf_); std::swap(type_, o.type_);
+    }
+
+    // cv::Mat::create: rows x cols pixels of type CV_8U (0) or CV_8UC3 (16), rows packed; kept when they already are
+    void create(int rows_, int cols_, int type) {
+        const size_t ch = type == 16 ? 3 : 1;
+        if (rows_ == rows && cols_ == cols && type == type_ && data) return;
+        buf_.assign((size_t)rows_ * cols_ * ch, 0);
+        rows = rows_; cols = cols_; type_ = type; step = (size_t)cols_ * ch;
+        data = buf_.empty() ? nullptr : buf_.data();
+    }
+    void release() { ImageBuf8U().swap(*this); }
+    bool empty() const { return data == nullptr; }
+    int channels() const { return type_ == 16 ? 3 : 1; }
+    int type() const { return type_; }
+
+private:
+    std::vector<unsigned char> buf_;
+    int type_ = 0;
+};
+
 namespace detail {
 template <class I, class = void> struct has_pixels : std::false_type {};
 template <class I>
@@ -82,9 +122,9 @@ public:
 
     // void Line3D::addImage(...), line3D.h:104-108.  Image: anything with .cols/.rows; Mat3: K(r,c);
     // Vec3: t(i); Seg: s[0..3] (cv::Vec4f).  Empty `line_segments` and an image with pixels (.data, .step, .type() as
-    // cv::Mat or Image8U has them): the segments are detected on the GPU, or read from the segment cache with
-    // load_segments (line3D.cc:168-173, 243-370).  The image must already be undistorted (Line3D::undistortImage is not
-    // part of this library).  A size-only image (ImageSize) needs its segments.  [multithreading safe like the reference;
+    // cv::Mat, Image8U or ImageBuf8U has them): the segments are detected on the GPU, or read from the segment cache with
+    // load_segments (line3D.cc:168-173, 243-370).  Detection expects undistorted pixels: undistortImage below is what the
+    // reference's front ends call first.  A size-only image (ImageSize) needs its segments.  [multithreading safe like the reference;
     // detection holds the context mutex, so image views added from several threads are detected one after another:
     // about 7 s per 3072x2304 image.  A front end with many images detects them in one batch with
     // l3d_detect_view_segments and hands each view its segments -- the batch costs about what one image does.]
@@ -122,6 +162,45 @@ public:
             median_depth, nb.data(), (uint32_t)nb.size());
         if (rc != L3D_OK) std::cout << prefix_err_ << "view [" << camID << "]: " << l3d_last_error() << std::endl;
         else { std::lock_guard<std::mutex> lk(lines_mu_); num_lines_[camID] = (uint32_t)line_segments.size(); }
+    }
+
+    // static void Line3D::undistortImage(inImg, outImg, radial_coeffs, tangential_coeffs, K), line3D.h:110-122, on the GPU
+    // (l3d_undistort_images).  InImage: cv::Mat, Image8U or ImageBuf8U (8-bit, 1 or 3 channels); OutImage:
+    // cv::Mat or ImageBuf8U, made with outImg.create(rows, cols, inImg.type()) and written at outImg.step (it may be the
+    // input itself).  Vec3 / Vec2: radial(i), tangential(i) (Eigen vectors); Mat3: K(r, c).  Errors are printed and leave
+    // outImg empty.  Static like the reference's, so there is no instance context: one process-wide context on device 0,
+    // made by the first call.  Calls from several threads (the front ends' OpenMP loops) run one after another on it.
+    template <class InImage, class OutImage, class Vec3, class Vec2, class Mat3>
+    static void undistortImage(const InImage& inImg, OutImage& outImg, const Vec3& radial_coeffs,
+                               const Vec2& tangential_coeffs, const Mat3& K) {
+        const int ty = inImg.type();
+        const uint32_t ch = ty == 0 ? 1u : ty == 16 ? 3u : 0u;
+        const l3d_image in{(const uint8_t*)inImg.data, (uint32_t)inImg.cols, (uint32_t)inImg.rows, ch,
+                           (uint32_t)(size_t)inImg.step};
+        l3d_distortion d{};
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) d.K[3 * r + c] = K(r, c);
+        for (int i = 0; i < 3; ++i) d.radial[i] = radial_coeffs(i);
+        for (int i = 0; i < 2; ++i) d.tangential[i] = tangential_coeffs(i);
+        const size_t row = (size_t)in.cols * ch;
+        std::vector<uint8_t> tmp;
+        uint8_t* dst = nullptr;
+        if (ch) {
+            outImg.create(inImg.rows, inImg.cols, ty);
+            if ((size_t)outImg.step == row) dst = (uint8_t*)outImg.data;
+            else { tmp.resize(row * in.rows); dst = tmp.data(); }
+        }
+        l3d_ctx* ctx = undistort_context();
+        const int rc = ctx ? l3d_undistort_images(ctx, 1, &in, &d, &dst) : L3D_ERR_HIP;
+        if (rc != L3D_OK) {
+            std::cout << "[L3D++] ERROR: undistortImage: "
+                      << (ctx ? l3d_last_error() : "no HIP context on device 0") << std::endl;
+            outImg.release();
+            return;
+        }
+        if (!tmp.empty())
+            for (uint32_t r = 0; r < in.rows; ++r)
+                std::memcpy((uint8_t*)outImg.data + r * (size_t)outImg.step, tmp.data() + r * row, row);
     }
 
     // void Line3D::matchImages(...), line3D.h:143-148
@@ -282,6 +361,13 @@ public:
     l3d_ctx* handle() { return ctx_; }
 
 private:
+    // the context of the static undistortImage: made once, thread-safely, by the first call; it lives as long as the
+    // process (destroying it from a static destructor could run after the HIP runtime's own teardown)
+    static l3d_ctx* undistort_context() {
+        static l3d_ctx* const ctx = l3d_create(0, nullptr);
+        return ctx;
+    }
+
     l3d_ctx* ctx_ = nullptr;
     std::string output_folder_;
     bool load_segments_ = true;

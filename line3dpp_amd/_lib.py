@@ -75,6 +75,11 @@ class DetectOptions(C.Structure):
                 ("max_line_segments", C.c_uint32)]
 
 
+class Distortion(C.Structure):
+    """l3d_distortion (include/l3dpp_hip.h): the arguments of Line3D::undistortImage"""
+    _fields_ = [("K", C.c_double * 9), ("radial", C.c_double * 3), ("tangential", C.c_double * 2)]
+
+
 class DetectStats(C.Structure):
     """l3d_detect_stats (include/l3dpp_hip.h)"""
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("raw_segments", C.c_uint32), ("segments", C.c_uint32),
@@ -101,7 +106,7 @@ EXPORTS = [
     "l3d_sfm_close", "l3d_debug_counter", "l3d_affinity_shard_begin", "l3d_affinity_shard_finish", "l3d_affinity_shard_abort", "l3d_shard_options",
     "l3d_line_opt_stats", "l3d_line_to_cayley", "l3d_cayley_to_segment", "l3d_line_opt_eval", "l3d_get_fresh_hyp",
     "l3d_detect_segments", "l3d_detect_view_segments", "l3d_get_detected_segments", "l3d_get_detect_stats",
-    "l3d_add_view_image", "l3d_add_view_image_worldpoints",
+    "l3d_add_view_image", "l3d_add_view_image_worldpoints", "l3d_undistort_images",
 ]
 
 _lib = None
@@ -207,6 +212,7 @@ def load():
                                      C.POINTER(u32)]
     L.l3d_add_view_image_worldpoints.argtypes = [vp, u32, C.POINTER(Image), C.POINTER(DetectOptions), vp, vp, vp, f32,
                                                  vp, u32, C.POINTER(u32)]
+    L.l3d_undistort_images.argtypes = [vp, u32, vp, vp, vp]
     L.l3d_score_matches.argtypes = [i32, vp, u32, vp, vp, vp, u32, vp, vp, f32, f32, vp]
     for name in EXPORTS:
         fn = getattr(L, name)

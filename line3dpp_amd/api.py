@@ -73,7 +73,8 @@ class Line3D:
     # Line3D::addImage(camID, image, K, R, t, median_depth, wps_or_neighbors, line_segments), line3D.h:104-108
     def addImage(self, camID, image, K, R, t, median_depth, wps_or_neighbors, line_segments=()):
         """image = a (cols, rows) tuple, which stands in for the cv::Mat when `line_segments` are given (the image then
-        only contributes its size, line3D.cc:119,198), or a uint8 HxW / HxWx3 ndarray (undistorted; first channel = R).
+        only contributes its size, line3D.cc:119,198), or a uint8 HxW / HxWx3 ndarray (undistorted, e.g. by undistortImage;
+        first channel = R).
         An ndarray with no segments is detected on the GPU, or loaded from the segment cache (line3D.cc:168-173)."""
         segs = np.ascontiguousarray(line_segments, np.float32).reshape(-1, 4)
         K = np.ascontiguousarray(K, np.float64).reshape(3, 3)
@@ -104,6 +105,16 @@ class Line3D:
                  int(image_size[0]), int(image_size[1]), float(median_depth), ptr(nb), len(nb))
         if self._check(rc, f"addImage [{camID}]"):
             self._M[int(camID)] = len(segs)
+
+    # static void Line3D::undistortImage(inImg, outImg, radial_coeffs, tangential_coeffs, K), line3D.h:110-122: returns the
+    # undistorted image (None after an error, which is printed); k_undistort.hip, DESIGN §12
+    @staticmethod
+    def undistortImage(img, radial, tangential, K):
+        try:
+            return lsd.undistort_images([img], [K], [radial], [tangential])[0]
+        except (RuntimeError, TypeError) as e:
+            print(f"{Line3D.PREFIX}ERROR: undistortImage: {e}")
+            return None
 
     def _detect_options(self):
         folder = self.output_folder.encode()

@@ -58,4 +58,19 @@ extern std::atomic<uint64_t> g_lsd_cache_loads;
 hipError_t launch_lsd(const LsdImage* d_imgs, uint32_t n, uint32_t max_src_pix, uint32_t max_small_pix,
                       uint32_t max_scaled_pix, const LsdConst& k, LsdResult* d_res, hipStream_t st);
 
+// one image of an undistortion batch (Line3D::undistortImage); every pointer is device memory inside the
+// batch's arena.  The per-image constants are the host's, in double: k_undistort.hip computes the map from them.
+struct UndImage {
+    const uint8_t* src;            // rows x (cols * channels), packed
+    uint8_t* dst;                  // the same shape
+    const double* xtab;            // column table X[0..cols): X[0] = ir2, X[j+1] = X[j] + ir0
+    uint32_t cols, rows, channels;
+    double w;                      // 1 / ir8
+    double ir4, ir5;               // row value Y[i] = i * ir4 + ir5
+    double fx, fy, cx, cy;
+    double k1, k2, k3, p1, p2;
+};
+
+hipError_t launch_undistort(const UndImage* d_imgs, uint32_t n, uint32_t max_pix, hipStream_t st);
+
 }  // namespace l3d

@@ -272,6 +272,79 @@ int add_view_image(l3d_ctx* c, uint32_t camID, const l3d_image* image, const l3d
     return rc;
 }
 
+// Line3D::undistortImage's input checks, made before any pixel is read or any memory is allocated.  Only
+// fx, fy, cx, cy of K are read (cvK drops the skew and sets K(2,2) to 1).
+int check_undistort(const l3d_image& im, const l3d_distortion& d) {
+    if (int rc = check_image(im)) return rc;
+    const double used[9] = {d.K[0], d.K[4], d.K[2], d.K[5], d.radial[0], d.radial[1], d.radial[2], d.tangential[0],
+                            d.tangential[1]};
+    for (double v : used)
+        if (!std::isfinite(v)) return fail(L3D_ERR_ARG, "undistortImage: non-finite distortion coefficient or camera matrix entry");
+    if (d.K[0] * d.K[4] == 0) return fail(L3D_ERR_ARG, "undistortImage: fx * fy == 0, the camera matrix is singular");
+    if (im.cols >= 32767 || im.rows >= 32767)
+        return fail(L3D_ERR_LIMIT, "undistortImage: image side of SHRT_MAX or more (cv::remap refuses it)");
+    return L3D_OK;
+}
+
+// Line3D::undistortImage for a batch: inputs up, one k_undistort launch, outputs down
+int undistort(l3d_ctx* c, uint32_t n, const l3d_image* in, const l3d_distortion* dist, uint8_t* const* out) {
+    if (!c || (n && (!in || !dist || !out))) return fail(L3D_ERR_ARG, "null argument");
+    for (uint32_t i = 0; i < n; ++i) {
+        if (int rc = check_undistort(in[i], dist[i])) return rc;
+        if (!out[i]) return fail(L3D_ERR_ARG, "null argument");
+    }
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    if (!n) return L3D_OK;
+    (void)hipSetDevice(c->device);
+    std::vector<UndImage> d(n);
+    std::vector<std::vector<double>> xtab(n);
+    std::vector<std::array<size_t, 3>> off(n);
+    size_t bytes = align256(n * sizeof(UndImage));
+    uint32_t max_pix = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const l3d_image& im = in[i];
+        const l3d_distortion& D = dist[i];
+        UndImage& U = d[i];
+        // cv::invert's closed form (DECOMP_LU, n = 3) of cvK, reduced: ir1, ir3, ir6, ir7 are +-0
+        const double fx = D.K[0], fy = D.K[4], cx = D.K[2], cy = D.K[5];
+        const double det = fx * fy, dd = 1.0 / det;
+        const double ir0 = fy * dd, ir2 = (-(cx * fy)) * dd, ir8 = (fx * fy) * dd;
+        U.cols = im.cols; U.rows = im.rows; U.channels = im.channels;
+        U.w = 1.0 / ir8; U.ir4 = fx * dd; U.ir5 = (-(fx * cy)) * dd;
+        U.fx = fx; U.fy = fy; U.cx = cx; U.cy = cy;
+        U.k1 = D.radial[0]; U.k2 = D.radial[1]; U.k3 = D.radial[2]; U.p1 = D.tangential[0]; U.p2 = D.tangential[1];
+        // OpenCV accumulates _x += ir[0] along a row; ir1 = 0, so every row starts from ir2 and one table serves all
+        std::vector<double>& X = xtab[i];
+        X.resize(im.cols);
+        X[0] = ir2;
+        for (uint32_t j = 1; j < im.cols; ++j) X[j] = X[j - 1] + ir0;
+        const size_t px = align256((size_t)im.cols * im.rows * im.channels);
+        off[i] = {bytes, bytes + px, bytes + 2 * px};
+        bytes += 2 * px + align256(im.cols * sizeof(double));
+        max_pix = std::max(max_pix, im.cols * im.rows);
+    }
+    DevBuf<char> arena;
+    struct Guard { DevBuf<char>& a; hipStream_t st; ~Guard() { (void)hipStreamSynchronize(st); a.release(); } } guard{arena, c->stream};
+    L3D_HIP_CHECK(arena.reserve(bytes));
+    char* base = arena.p;
+    for (uint32_t i = 0; i < n; ++i) {
+        UndImage& U = d[i];
+        U.src = (const uint8_t*)(base + off[i][0]);
+        U.dst = (uint8_t*)(base + off[i][1]);
+        U.xtab = (const double*)(base + off[i][2]);
+        const size_t row = (size_t)in[i].cols * in[i].channels;
+        L3D_HIP_CHECK(hipMemcpy2DAsync((void*)U.src, row, in[i].data, in[i].row_stride, row, in[i].rows, hipMemcpyHostToDevice, c->stream));
+        L3D_HIP_CHECK(hipMemcpyAsync((void*)U.xtab, xtab[i].data(), in[i].cols * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    }
+    L3D_HIP_CHECK(hipMemcpyAsync(base, d.data(), n * sizeof(UndImage), hipMemcpyHostToDevice, c->stream));
+    L3D_HIP_CHECK(launch_undistort((const UndImage*)base, n, max_pix, c->stream));
+    // after every upload in stream order: out[i] may be the memory of an input
+    for (uint32_t i = 0; i < n; ++i)
+        L3D_HIP_CHECK(hipMemcpyAsync(out[i], d[i].dst, (size_t)in[i].cols * in[i].rows * in[i].channels, hipMemcpyDeviceToHost, c->stream));
+    L3D_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return L3D_OK;
+}
+
 }  // namespace
 }  // namespace l3d
 
@@ -316,6 +389,11 @@ int l3d_add_view_image_worldpoints(l3d_ctx* c, uint32_t camID, const l3d_image* 
                                    const double K[9], const double R[9], const double t[3], float median_depth,
                                    const uint32_t* worldpoints, uint32_t n_worldpoints, uint32_t* n_segments) {
     return add_view_image(c, camID, image, opts, K, R, t, median_depth, worldpoints, n_worldpoints, true, n_segments);
+}
+
+int l3d_undistort_images(l3d_ctx* c, uint32_t n_images, const l3d_image* in, const l3d_distortion* dist,
+                         uint8_t* const* out) {
+    return undistort(c, n_images, in, dist, out);
 }
 
 }  // extern "C"

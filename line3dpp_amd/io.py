@@ -427,3 +427,34 @@ def read_bundler(path):
     for c in cams:
         c["median_depth"] = _median_depth(c["C"], c.pop("_pts"))
     return cams
+
+
+L3D_EPS = 1e-12     # commons.h:95
+
+
+def front_end_undistortion(kind, entry, cols, rows):
+    """(K, radial, tangential) as the reference's front end hands them to Line3D::undistortImage for the image of `entry`
+    (cols x rows pixels), or None when it does not call it.  kind / entry: "nvm" and an element of read_nvm
+    (main_vsfm.cpp:283-297: radial (-d, 0, 0), K from the image size), "bundler" and an element of read_bundler
+    (main_bundler.cpp:352-368: radial (d1, d2, 0), K from the image size), "colmap" and an element of read_colmap
+    (main_colmap.cpp:377-389: the camera's five coefficients and K).  Each calls it only when a coefficient exceeds
+    L3D_EPS in magnitude; main_vsfm and main_bundler skip a camera without worldpoints before that, main_colmap does
+    not."""
+    zero2 = np.zeros(2)
+    if kind == "nvm":
+        d = np.float32(entry["distortion"])
+        if not entry["worldpoints"] or not abs(float(d)) > L3D_EPS:
+            return None
+        return nvm_intrinsics(entry["focal"], cols, rows), np.array([float(-d), 0.0, 0.0]), zero2
+    if kind == "bundler":
+        d1, d2 = float(entry["radial"][0]), float(entry["radial"][1])
+        if not entry["worldpoints"] or not (abs(d1) > L3D_EPS or abs(d2) > L3D_EPS):
+            return None
+        return nvm_intrinsics(entry["focal"], cols, rows), np.array([d1, d2, 0.0]), zero2
+    if kind == "colmap":
+        radial = np.array(entry["radial"], np.float64)
+        tangential = np.array(entry["tangential"], np.float64)
+        if not any(abs(float(v)) > L3D_EPS for v in (*radial, *tangential)):
+            return None
+        return np.array(entry["K"], np.float64), radial, tangential
+    raise ValueError(f"unknown front end {kind!r}: nvm, bundler or colmap")

@@ -2,7 +2,9 @@
 
 `detect_line_segments` is the stage on its own: grey conversion, the max-width downscale, LSD (lsd_opencv.cpp,
 LSD_REFINE_ADV), the length filter, the length order and the cap.  `Line3D.addImage` / `addImages` (api.py) run the
-same stage, with the segment cache, when they are given an image and no segments.  Images must already be undistorted.
+same stage, with the segment cache, when they are given an image and no segments.  Detection expects undistorted
+images: `undistort_images` is Line3D::undistortImage (line3D.cc:83-109) on the GPU (k_undistort.hip), batched over images,
+which the reference's front ends call before addImage.
 """
 import ctypes as C
 
@@ -15,13 +17,15 @@ L3D_DEF_MAX_NUM_SEGMENTS = 3000
 
 
 def as_image(img):
-    """uint8 HxW (grey) or HxWx3 (first channel = R) ndarray -> (l3d_image, the contiguous array it points into)"""
+    """uint8 HxW (grey) or HxWx3 (first channel = R) ndarray -> (l3d_image, the array it points into).  Rows may be
+    padded (a view such as big[:, :w] keeps its row stride); an array whose rows are not packed pixels is copied."""
     a = np.asarray(img)
     if a.dtype != np.uint8 or a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] != 3):
         raise TypeError("image type not supported! must be uint8 HxW (gray) or HxWx3 (RGB)")
-    a = np.ascontiguousarray(a)
     ch = 1 if a.ndim == 2 else 3
-    return _lib.Image(a.ctypes.data, a.shape[1], a.shape[0], ch, a.shape[1] * ch), a
+    if not (a.strides[-1] == 1 and (ch == 1 or a.strides[1] == 3) and a.strides[0] >= a.shape[1] * ch):
+        a = np.ascontiguousarray(a)
+    return _lib.Image(a.ctypes.data, a.shape[1], a.shape[0], ch, a.strides[0]), a
 
 
 def image_array(images):
@@ -74,6 +78,42 @@ def last_stats(L, h):
     st = (_lib.DetectStats * max(n.value, 1))()
     L.l3d_get_detect_stats(h, st, n.value, C.byref(n))
     return [{k: getattr(st[i], k) for k, _ in _lib.DetectStats._fields_ if k != "reserved"} for i in range(n.value)]
+
+
+def distortion(K, radial, tangential):
+    """l3d_distortion of undistortImage's arguments: K 3x3, radial (k1, k2, k3), tangential (p1, p2)"""
+    d = _lib.Distortion()
+    d.K[:] = [float(v) for v in np.asarray(K, np.float64).reshape(9)]
+    d.radial[:] = [float(v) for v in np.asarray(radial, np.float64).reshape(3)]
+    d.tangential[:] = [float(v) for v in np.asarray(tangential, np.float64).reshape(2)]
+    return d
+
+
+def undistort_images(images, Ks, radials, tangentials, device=0):
+    """Line3D::undistortImage (line3D.cc:83-109) for a list of images in one batch on the GPU -> list of uint8 ndarrays of
+    the inputs' shapes.  Per image: K 3x3 (fx, fy, cx, cy are read), radial = (k1, k2, k3), tangential = (p1, p2), as
+    the front ends hand them to undistortImage (io.front_end_undistortion).  DESIGN §12 defines the result."""
+    L = _lib.load()
+    images = list(images)
+    n = len(images)
+    if not len(Ks) == len(radials) == len(tangentials) == n:
+        raise ValueError("one K, radial and tangential per image")
+    views = [as_image(im) for im in images]
+    arr = (_lib.Image * max(n, 1))(*[v[0] for v in views])
+    dist = (_lib.Distortion * max(n, 1))(*[distortion(*a) for a in zip(Ks, radials, tangentials)])
+    outs = [np.empty(v[1].shape, np.uint8) for v in views]
+    ptrs = (C.c_void_p * max(n, 1))(*[o.ctypes.data for o in outs])
+    h = L.l3d_create(int(device), None)
+    if not h:
+        raise RuntimeError("l3d_create failed: " + _lib.last_error())
+    h = C.c_void_p(h)
+    try:
+        rc = L.l3d_undistort_images(h, n, arr, dist, ptrs)
+        if rc != 0:
+            raise RuntimeError(f"l3d_undistort_images failed [{rc}]: {_lib.last_error()}")
+        return outs
+    finally:
+        L.l3d_destroy(h)
 
 
 def read_image_gray(path):
