@@ -449,6 +449,24 @@ int l3d_cayley_to_segment(const double x[4], const double P1_old[3], const doubl
 int l3d_line_opt_eval(int device, uint32_t n, const double x[4], const double* obs, const double* cams, double* cost,
                       double* residuals, double* jacobians, int32_t* ok);
 
+/* main_pix4d.cpp's triangulation of tie points (linearHomTriangulation, main_pix4d.cpp:34-69, in the loop of :354-372)
+ * on the device, one lane per point in fp64 (k_triangulate.hip).  P12: n_cameras row-major 3x4 projection matrices;
+ * the observations of point i are obs_offsets[i] .. obs_offsets[i + 1] (CSR, obs_offsets[0] == 0): obs_camera names the
+ * matrix, obs_xy the pixel.  Per point: the rows (0, -1, y) P_c and (1, 0, -x) P_c of every observation form A; v = the
+ * singular vector of A^T A for its smallest singular value (cyclic Jacobi on the symmetric 4x4; the reference takes
+ * JacobiSVD(AtA).matrixV().col(3)); X = v[0:3] / v[3].  valid[i] = 1 exactly when the point has more than two
+ * observations and norm(X) > L3D_EPS in IEEE arithmetic (a NaN is invalid, an infinite X is valid); X3 holds X for a
+ * valid point and zeros otherwise.  An observation of a camera >= n_cameras: L3D_ERR_ARG, nothing is launched;
+ * n_points == 0: L3D_OK, nothing is launched.  Host pointers in and out. */
+int l3d_triangulate_points(int device, uint32_t n_cameras, const double* P12, uint64_t n_points, const uint64_t* obs_offsets,
+                           const uint32_t* obs_camera, const double* obs_xy, double* X3, uint8_t* valid);
+/* Static members of the reference's Line3D (host only), row-major 3x3 out: rotationFromRPY (line3D.cc:2714-2727:
+ * Rz(yaw) Ry(pitch) Rx(roll)), rotationFromQ (:2730-2754) and decomposeProjectionMatrix (:2784-2853: P = K [R | t] by
+ * three Givens rotations; K with positive diagonal and K[2][2] = 1) */
+int l3d_rotation_from_rpy(double roll, double pitch, double yaw, double R9[9]);
+int l3d_rotation_from_q(double qw, double qx, double qy, double qz, double R9[9]);
+int l3d_decompose_projection_matrix(const double P12[12], double K9[9], double R9[9], double t3[3]);
+
 /* test hook (device): the unscaled IEEE division / square root of the exact tests (l3d_dev.h: rcp_refined, div_by,
  * sqrt_unscaled) against the compiler's own expansions on n random operand sets; counts[3] = results whose bits differ
  * (single divisions, paired divisions, square roots) -- all zero on a correct build */

@@ -203,6 +203,47 @@ public:
                 std::memcpy((uint8_t*)outImg.data + r * (size_t)outImg.step, tmp.data() + r * row, row);
     }
 
+    // static Eigen::Matrix3d Line3D::rotationFromRPY(roll, pitch, yaw) and rotationFromQ(Qw, Qx, Qy, Qz), line3D.h:220-226
+    // (line3D.cc:2714-2754).  Mat3: the matrix type to return, default-constructible with R(r, c) (Eigen::Matrix3d):
+    // Line3D::rotationFromRPY<Eigen::Matrix3d>(r, p, y)
+    template <class Mat3>
+    static Mat3 rotationFromRPY(const double roll, const double pitch, const double yaw) {
+        double r[9];
+        l3d_rotation_from_rpy(roll, pitch, yaw, r);
+        Mat3 R;
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) R(i, j) = r[3 * i + j];
+        return R;
+    }
+    template <class Mat3>
+    static Mat3 rotationFromQ(const double Qw, const double Qx, const double Qy, const double Qz) {
+        double r[9];
+        l3d_rotation_from_q(Qw, Qx, Qy, Qz, r);
+        Mat3 R;
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) R(i, j) = r[3 * i + j];
+        return R;
+    }
+
+    // static void Line3D::decomposeProjectionMatrix(P_in, K_out, R_out, t_out), line3D.h:228-232 (line3D.cc:2784-2853):
+    // P = K [R | t].  MatP: anything with (r, c), rows() and cols() (Eigen::MatrixXd); a P that is neither 3 rows nor 4
+    // columns is reported and leaves the outputs alone, the reference's own test (:2789)
+    template <class MatP, class Mat3, class Vec3>
+    static void decomposeProjectionMatrix(const MatP& P_in, Mat3& K_out, Mat3& R_out, Vec3& t_out) {
+        if (P_in.rows() != 3 && P_in.cols() != 4) {
+            std::cout << "P is not a 3x4 matrix! (" << P_in.rows() << "x" << P_in.cols() << ")" << std::endl;
+            return;
+        }
+        double p[12], k[9], r[9], t[3];
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 4; ++j) p[4 * i + j] = P_in(i, j);
+        l3d_decompose_projection_matrix(p, k, r, t);
+        for (int i = 0; i < 3; ++i) {
+            for (int j = 0; j < 3; ++j) { K_out(i, j) = k[3 * i + j]; R_out(i, j) = r[3 * i + j]; }
+            t_out(i) = t[i];
+        }
+    }
+
     // void Line3D::matchImages(...), line3D.h:143-148
     void matchImages(const float sigma_position = L3D_DEF_SCORING_POS_REGULARIZER,
                      const float sigma_angle = L3D_DEF_SCORING_ANG_REGULARIZER,

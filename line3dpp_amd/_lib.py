@@ -107,6 +107,7 @@ EXPORTS = [
     "l3d_line_opt_stats", "l3d_line_to_cayley", "l3d_cayley_to_segment", "l3d_line_opt_eval", "l3d_get_fresh_hyp",
     "l3d_detect_segments", "l3d_detect_view_segments", "l3d_get_detected_segments", "l3d_get_detect_stats",
     "l3d_add_view_image", "l3d_add_view_image_worldpoints", "l3d_undistort_images",
+    "l3d_triangulate_points", "l3d_rotation_from_rpy", "l3d_rotation_from_q", "l3d_decompose_projection_matrix",
 ]
 
 _lib = None
@@ -214,6 +215,11 @@ def load():
                                                  vp, u32, C.POINTER(u32)]
     L.l3d_undistort_images.argtypes = [vp, u32, vp, vp, vp]
     L.l3d_score_matches.argtypes = [i32, vp, u32, vp, vp, vp, u32, vp, vp, f32, f32, vp]
+    L.l3d_triangulate_points.argtypes = [i32, u32, vp, u64, vp, vp, vp, vp, vp]
+    f64 = C.c_double
+    L.l3d_rotation_from_rpy.argtypes = [f64, f64, f64, vp]
+    L.l3d_rotation_from_q.argtypes = [f64, f64, f64, f64, vp]
+    L.l3d_decompose_projection_matrix.argtypes = [vp, vp, vp, vp]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("l3d_last_error", "l3d_build_info", "l3d_create", "l3d_destroy"):

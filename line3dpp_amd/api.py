@@ -116,6 +116,31 @@ class Line3D:
             print(f"{Line3D.PREFIX}ERROR: undistortImage: {e}")
             return None
 
+    # static members of the reference's Line3D (line3D.cc:2714-2754, :2784-2853), through the C-ABI (host code)
+    @staticmethod
+    def rotationFromRPY(roll, pitch, yaw):
+        R = np.zeros((3, 3))
+        _lib.load().l3d_rotation_from_rpy(float(roll), float(pitch), float(yaw), ptr(R))
+        return R
+
+    @staticmethod
+    def rotationFromQ(Qw, Qx, Qy, Qz):
+        R = np.zeros((3, 3))
+        _lib.load().l3d_rotation_from_q(float(Qw), float(Qx), float(Qy), float(Qz), ptr(R))
+        return R
+
+    @staticmethod
+    def decomposeProjectionMatrix(P_in):
+        """-> (K, R, t) of P = K [R | t]; a P that is not 3x4 is reported and gives None, as the reference leaves its
+        outputs alone"""
+        P = np.ascontiguousarray(P_in, np.float64)
+        if P.shape != (3, 4):
+            print(f"P is not a 3x4 matrix! ({'x'.join(str(n) for n in P.shape)})")
+            return None
+        K, R, t = np.zeros((3, 3)), np.zeros((3, 3)), np.zeros(3)
+        _lib.load().l3d_decompose_projection_matrix(ptr(P), ptr(K), ptr(R), ptr(t))
+        return K, R, t
+
     def _detect_options(self):
         folder = self.output_folder.encode()
         opts = _lib.DetectOptions(folder, int(self.load_segments), self.max_img_width, self.max_line_segments)
@@ -462,6 +487,27 @@ def diffuse_affinity(edges, n_rows, iterations=10, device=0):
     if rc != 0:
         raise RuntimeError(f"l3d_diffuse_affinity failed [{rc}]: {_lib.last_error()}")
     return out
+
+
+def triangulate_points(P, obs_offsets, obs_camera, obs_xy, device=0):
+    """l3d_triangulate_points: main_pix4d.cpp's linear triangulation of tie points (linearHomTriangulation, :34-69) on
+    the GPU.  P [n_cameras, 3, 4]; the observations of point i are obs_offsets[i] .. obs_offsets[i + 1] of obs_camera
+    [n_obs] and obs_xy [n_obs, 2].  -> (X [n, 3] float64, valid [n] bool): valid = more than two observations and
+    norm(X) > L3D_EPS; X is zero where not valid."""
+    L = _lib.load()
+    P = np.ascontiguousarray(P, np.float64).reshape(-1, 3, 4)
+    off = np.ascontiguousarray(obs_offsets, np.uint64).reshape(-1)
+    cam = np.ascontiguousarray(obs_camera, np.uint32).reshape(-1)
+    xy = np.ascontiguousarray(obs_xy, np.float64).reshape(-1, 2)
+    n = max(len(off) - 1, 0)
+    if n and (int(off[-1]) > len(cam) or len(xy) != len(cam)):
+        raise ValueError("obs_offsets, obs_camera and obs_xy do not describe the same observations")
+    X = np.zeros((n, 3), np.float64)
+    valid = np.zeros(n, np.uint8)
+    rc = L.l3d_triangulate_points(int(device), len(P), ptr(P), n, ptr(off), ptr(cam), ptr(xy), ptr(X), ptr(valid))
+    if rc != 0:
+        raise RuntimeError(f"l3d_triangulate_points failed [{rc}]: {_lib.last_error()}")
+    return X, valid.astype(bool)
 
 
 def find_collinear_segments(lines, dist_t, device=0):

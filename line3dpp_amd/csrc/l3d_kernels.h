@@ -194,4 +194,18 @@ size_t rdd_workspace_bytes(uint32_t nnz, uint32_t n_rows);
 hipError_t launch_rdd(const struct ::l3d_cledge* edges_in, uint32_t nnz, uint32_t n_rows, uint32_t iterations,
                       struct ::l3d_cledge* edges_out, void* workspace, size_t workspace_bytes, hipStream_t stream);
 
+// ---- k_triangulate.hip: linear triangulation of tie points (l3d_triangulate_points) ----
+struct TriArgs {
+    const double* P;          // [n_cameras x 12] projection matrices, row-major 3x4
+    uint32_t n_cameras;
+    uint64_t n_points;
+    const uint64_t* off;      // [n_points + 1] CSR over the observations
+    const uint32_t* cam;      // [n_obs] camera of an observation, < n_cameras (the host checks)
+    const double* xy;         // [n_obs x 2] its pixel
+    double* X;                // [n_points x 3]
+    uint8_t* valid;           // [n_points]
+};
+constexpr size_t kTriLdsBytes = 32 * 1024;   // projection matrices up to this size (341 cameras) are staged in LDS
+hipError_t launch_triangulate(const TriArgs& t, hipStream_t st);
+
 }  // namespace l3d

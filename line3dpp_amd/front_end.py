@@ -1,14 +1,20 @@
-"""Run a dataset end to end: the reference's front ends main_vsfm.cpp, main_colmap.cpp and main_bundler.cpp.
+"""Run a dataset end to end: the reference's six front ends main_vsfm.cpp, main_colmap.cpp, main_bundler.cpp,
+main_pix4d.cpp, main_openmvg.cpp and main_mavmap.cpp.
 
     python -m line3dpp_amd.front_end vsfm    -m result.nvm [-i image_folder] [flags]
     python -m line3dpp_amd.front_end colmap  -i image_folder [-m sfm_folder] [flags]
     python -m line3dpp_amd.front_end bundler -i image_folder [-b bundle.rd.out] [-f image_list] [-t extension] [flags]
+    python -m line3dpp_amd.front_end pix4d   -i image_folder -b params_folder -f project_prefix [flags]
+    python -m line3dpp_amd.front_end openmvg -i image_folder -j sfm_data.json [flags]
+    python -m line3dpp_amd.front_end mavmap  -i image_folder -b image-data.txt -t extension [-f image_prefix] [flags]
 
 Each program takes the flags of its reference main (FLAGS below: short and long name, required or not, default), reads
 the SfM result with the readers of io.py, looks its images up as that main does, and drives `Line3D` through the
 reference's call sequence: undistortImage where a camera has distortion, addImage, matchImages, reconstruct3Dlines,
-get3Dlines, then the STL, OBJ, TXT and BIN writers into the output folder.  `run_vsfm`, `run_colmap` and `run_bundler`
-are the same programs as functions; they return the `Line3D` object and the wall-clock seconds per stage.
+get3Dlines, then the STL, OBJ, TXT and BIN writers into the output folder.  `run_vsfm`, `run_colmap`, `run_bundler`,
+`run_pix4d`, `run_openmvg` and `run_mavmap` are the same programs as functions; they return the `Line3D` object and the
+wall-clock seconds per stage.  Pix4D gives no 3D points: its program triangulates every tie point on the GPU
+(api.triangulate_points) while it reads the project, before `Line3D` is constructed.
 
 What differs from the reference:
 - images go through the library in chunks: a chunk is read on the host, the images that need it are undistorted in ONE
@@ -38,7 +44,7 @@ STAGES = ("read", "undistort", "add", "match", "reconstruct", "save")
 _NOT_HERE_G = " (accepted and ignored: this library has no CPU path)"
 _NOT_HERE_C = " (default 0, as in a reference build without Ceres; 1 bundles the 3D lines on the GPU)"
 
-# (short, long, type, required, default, help): the numeric flags the three mains share (main_vsfm.cpp:53-92, commons.h:40-88)
+# (short, long, type, required, default, help): the numeric flags the six mains share (main_vsfm.cpp:53-92, commons.h:40-88)
 _COMMON = [
     ("w", "max_image_width", int, False, -1, "scale image down to fixed max width for line segment detection"),
     ("n", "num_matching_neighbors", int, False, 10, "number of neighbors for matching"),
@@ -72,6 +78,24 @@ FLAGS = {
         ("b", "bundle_file", str, False, "", "full path to the bundle.*.out file (if not specified -> image_folder/../bundle.rd.out)"),
         ("f", "img_list", str, False, "", "full path to an optional image list (e.g. for the Dubrovnik6K dataset)"),
         ("t", "image_extension", str, False, "", "image extension (case sensitive), if not specified: jpg, png or bmp expected"),
+        ("o", "output_folder", str, False, "", "folder where result and temporary files are stored (if not specified --> input_folder+'/Line3D++/')"),
+    ] + _COMMON,
+    "pix4d": [  # main_pix4d.cpp:84-136
+        ("i", "input_folder", str, True, ".", "folder containing the images"),
+        ("b", "params_folder", str, True, "", "folder containing the project files <project_prefix>_calibrated_camera_parameters.txt and <project_prefix>_tp_pix4d.txt"),
+        ("f", "project_prefix", str, True, "", "project name and output file prefix"),
+        ("o", "output_folder", str, False, "", "folder where result and temporary files are stored (if not specified --> image_folder+'/Line3D++/')"),
+    ] + _COMMON,
+    "openmvg": [  # main_openmvg.cpp:45-94
+        ("i", "input_folder", str, True, ".", "folder containing the original images"),
+        ("j", "sfm_json_file", str, True, ".", "full path to the OpenMVG result file (sfm_data.json)"),
+        ("o", "output_folder", str, False, "", "folder where result and temporary files are stored (if not specified --> input_folder+'/Line3D++/')"),
+    ] + _COMMON,
+    "mavmap": [  # main_mavmap.cpp:43-98
+        ("i", "input_folder", str, True, ".", "folder containing the images"),
+        ("b", "mavmap_output", str, True, "", "full path to the mavmap output (image-data-*.txt)"),
+        ("t", "image_extension", str, False, "", "image extension (case sensitive); mavmap needs it: without it the file looked for ends in a bare '.'"),
+        ("f", "image_prefix", str, False, "", "optional image prefix"),
         ("o", "output_folder", str, False, "", "folder where result and temporary files are stored (if not specified --> input_folder+'/Line3D++/')"),
     ] + _COMMON,
 }
@@ -183,9 +207,10 @@ def _chunk_bytes():
     return int(os.environ.get(CHUNK_ENV, CHUNK_BYTES))
 
 
-def run_views(kind, views, s, line3d_factory=None, read_image=None, undistort=None):
+def run_views(kind, views, s, line3d_factory=None, read_image=None, undistort=None, neighbors_by_worldpoints=True):
     """The shared core.  `views`: what a main's image loop visits, in its order, as (camera id, image path, entry of the
-    io reader); `s`: _settings.  -> (Line3D object, seconds per stage)"""
+    io reader); `s`: _settings; `neighbors_by_worldpoints`: what the main constructs Line3D with (main_mavmap.cpp:150-151
+    hands over neighbour lists, the others worldpoint lists).  -> (Line3D object, seconds per stage)"""
     if line3d_factory is None:
         from .api import Line3D as line3d_factory
     if read_image is None:
@@ -207,8 +232,8 @@ def run_views(kind, views, s, line3d_factory=None, read_image=None, undistort=No
         return out
 
     os.makedirs(s["output_folder"], exist_ok=True)
-    line3d = line3d_factory(s["output_folder"], s["load_segments"], s["max_img_width"], s["max_line_segments"], True,
-                            s["use_gpu"])
+    line3d = line3d_factory(s["output_folder"], s["load_segments"], s["max_img_width"], s["max_line_segments"],
+                            neighbors_by_worldpoints, s["use_gpu"])
     budget = _chunk_bytes()
     chunk, held = [], 0
 
@@ -232,11 +257,12 @@ def run_views(kind, views, s, line3d_factory=None, read_image=None, undistort=No
             image = np.zeros((0, 0), np.uint8)                 # cv::imread's empty Mat: 0 x 0 from here on, as there
         rows, cols = image.shape[:2]
         und = io.front_end_undistortion(kind, entry, cols, rows)
-        K = entry["K"] if kind == "colmap" else io.nvm_intrinsics(entry["focal"], cols, rows)
+        K = entry["K"] if "K" in entry else io.nvm_intrinsics(entry["focal"], cols, rows)   # .nvm, bundler: from the image size
         if chunk and held + image.nbytes > budget:
             flush()
             held = 0
-        chunk.append(dict(id=cam_id, image=image, entry=entry, K=K, undistortion=und, add=bool(entry["worldpoints"])))
+        chunk.append(dict(id=cam_id, image=image, entry=entry, K=K, undistortion=und,
+                          add=kind == "mavmap" or bool(entry["worldpoints"])))
         held += image.nbytes
     flush()
 
@@ -341,14 +367,63 @@ def run_bundler(argv, **pieces):
     return run_views("bundler", views, s, **pieces)
 
 
-PROGRAMS = {"vsfm": run_vsfm, "colmap": run_colmap, "bundler": run_bundler}
+def run_pix4d(argv, **pieces):
+    """main_pix4d.cpp"""
+    a = _start("pix4d", argv)
+    folder = a["input_folder"]
+    s = _settings(a, a["output_folder"] or folder + "/Line3D++/")
+    file1, file2 = io.pix4d_files(a["params_folder"], a["project_prefix"])
+    if not os.path.exists(file1) or not os.path.exists(file2):                                        # :171-175
+        raise FrontEndError(f"pix4d file '{file1}' or '\n{file2}' does not exist!")
+    try:
+        cams = io.read_pix4d(a["params_folder"], a["project_prefix"])
+    except (ValueError, RuntimeError) as e:            # RuntimeError: the library's, e.g. no usable device for the triangulation
+        raise FrontEndError(str(e)) from None
+    return run_views("pix4d", [(c["id"], folder + "/" + c["name"], c) for c in cams], s, **pieces)     # :378-419
+
+
+def run_openmvg(argv, **pieces):
+    """main_openmvg.cpp"""
+    a = _start("openmvg", argv)
+    folder, json_file = a["input_folder"], a["sfm_json_file"]
+    s = _settings(a, a["output_folder"] or folder + "/Line3D++/")
+    if not os.path.exists(json_file):                                                                 # :119-125
+        raise FrontEndError(f"OpenMVG json file {json_file} does not exist!")
+    views = _read(lambda path: io.read_openmvg(path, folder), json_file)
+    return run_views("openmvg", [(v["id"], v["path"], v) for v in views], s, **pieces)                # :369-410
+
+
+def run_mavmap(argv, **pieces):
+    """main_mavmap.cpp"""
+    a = _start("mavmap", argv)
+    folder, ext = a["input_folder"], a["image_extension"]
+    if not ext.startswith("."):                        # :125-126: the empty extension gets its dot as well, so the probe
+        ext = "." + ext                                # of :263-274 is never reached
+    s = _settings(a, a["output_folder"] or folder + "/Line3D++/")
+    if np.float32(s["sigma_p"]) < io.L3D_EPS and np.float32(s["const_reg_depth"]) < io.L3D_EPS:       # :130-135
+        print("sigma_p cannot be negative (i.e. in world coordiantes) when no valid regularization depth (--const_reg_depth) is given!")
+        print("reverting to: sigma_p = 2.5px")
+        s["sigma_p"] = 2.5
+    if not os.path.exists(a["mavmap_output"]):                                                        # :137-143
+        raise FrontEndError(f"mavmap file '{a['mavmap_output']}' does not exist!")
+    cams = _read(lambda path: io.read_mavmap(path, s["neighbors"]), a["mavmap_output"])
+    views = []
+    for c in cams:                                     # :256-327: a camera without an image file keeps its position
+        path = folder + "/" + a["image_prefix"] + c["name"] + ext
+        if os.path.exists(path):
+            views.append((c["id"], path, dict(c, median_depth=s["const_reg_depth"])))
+    return run_views("mavmap", views, s, neighbors_by_worldpoints=False, **pieces)
+
+
+PROGRAMS = {"vsfm": run_vsfm, "colmap": run_colmap, "bundler": run_bundler, "pix4d": run_pix4d, "openmvg": run_openmvg,
+            "mavmap": run_mavmap}
 
 
 def main(argv=None, **pieces):
     """the program: -> exit status"""
     argv = list(sys.argv[1:] if argv is None else argv)
     if not argv or argv[0] not in PROGRAMS:
-        print("usage: python -m line3dpp_amd.front_end {vsfm|colmap|bundler} <flags>\n\n"
+        print("usage: python -m line3dpp_amd.front_end {" + "|".join(PROGRAMS) + "} <flags>\n\n"
               + "\n\n".join(usage(p) for p in PROGRAMS), file=sys.stderr)
         return 1
     try:

@@ -432,6 +432,266 @@ def read_bundler(path):
 L3D_EPS = 1e-12     # commons.h:95
 
 
+# ---- mavmap logs, OpenMVG sfm_data.json and Pix4D projects (main_mavmap.cpp, main_openmvg.cpp, main_pix4d.cpp) -----------
+def _getlines(path):
+    """std::getline's view of a file: no extra empty line behind a final newline"""
+    with open(path) as f:
+        lines = f.read().split("\n")
+    return lines[:-1] if lines and lines[-1] == "" else lines
+
+
+_NUMBER = None
+
+
+def _stream_double(text):
+    """what `stream >> double` leaves for a token: its longest numeric prefix, 0 when there is none"""
+    global _NUMBER
+    if _NUMBER is None:
+        import re
+        _NUMBER = re.compile(r"[+-]?(\d+\.?\d*|\.\d+)([eE][+-]?\d+)?")
+    m = _NUMBER.match(text)
+    return float(m.group(0)) if m else 0.0
+
+
+def _row(line, n):
+    tok = line.split()
+    return [_stream_double(tok[k]) if k < len(tok) else 0.0 for k in range(n)]
+
+
+def _mm3(A, B):
+    """A B for a 3x3 A in the evaluation order of _mv3, column by column of B"""
+    B = np.asarray(B, np.float64)
+    return np.stack([_mv3(A, B[:, j]) for j in range(B.shape[1])], axis=1)
+
+
+def rotation_from_rpy(roll, pitch, yaw):
+    """Line3D::rotationFromRPY, line3D.cc:2714-2727: Rz(yaw) Ry(pitch) Rx(roll), each factor as
+    Eigen::AngleAxisd(angle, unit axis).toRotationMatrix() fills it (the axis' own diagonal entry is (1 - c) + c)"""
+    def axis(k, angle):
+        s, c = np.sin(angle), np.cos(angle)
+        i, j = (k + 1) % 3, (k + 2) % 3
+        R = np.zeros((3, 3))
+        R[k, k] = (1.0 - c) + c
+        R[i, i] = R[j, j] = c
+        R[i, j], R[j, i] = -s, s
+        return R
+    return _mm3(_mm3(axis(2, float(yaw)), axis(1, float(pitch))), axis(0, float(roll)))
+
+
+def mavmap_neighbors(i, n_cams, neighbors):
+    """main_mavmap.cpp:311-321: up to neighbors / 2 previous positions, nearest first, then following ones until the list
+    holds `neighbors`"""
+    out = []
+    k = i - 1
+    while k >= 0 and len(out) < neighbors // 2:
+        out.append(k); k -= 1
+    k = i + 1
+    while k < n_cams and len(out) < neighbors:
+        out.append(k); k += 1
+    return out
+
+
+def read_mavmap(path, neighbors=10):
+    """image-data-*.txt as main_mavmap.cpp:153-250 reads it -> list of cameras in file order (position = camera id, also
+    of a camera whose image the program does not find): dict(id, name, K, R, t, C, radial, tangential, worldpoints = the
+    NEIGHBOUR list of :311-321 for `neighbors`, median_depth None: the program hands over const_reg_depth).
+    Leading lines that start with '#' are skipped (:159-163); the list ends at the first line shorter than 28 characters
+    (:173).  17 whitespace-separated tokens per line, and every token that is used loses its last character, the comma
+    -- the last token, cy, as well (:188-245).  A camera model other than PINHOLE: ValueError (:188-192).  The pose is
+    the inverse of [R t; 0 1] with R = rotationFromRPY(roll, pitch, yaw) (:206-226), here R^T and -R^T t."""
+    lines = _getlines(path)
+    pos, line = 0, ""
+    while pos < len(lines):
+        line = lines[pos]; pos += 1
+        if line[:1] != "#":
+            break
+    cams = []
+    while len(line) >= 28:
+        tok = line.split()
+        tok = [tok[k][:-1] if k < len(tok) else "" for k in range(17)]
+        if tok[12] != "PINHOLE":
+            raise ValueError("only PINHOLE camera model supported...")
+        roll, pitch, yaw = (_stream_double(tok[k]) for k in (1, 2, 3))
+        t = np.array([_stream_double(tok[k]) for k in (8, 9, 10)])
+        fx, fy, cx, cy = (_stream_double(tok[k]) for k in (13, 14, 15, 16))
+        R = rotation_from_rpy(roll, pitch, yaw).T.copy()
+        cams.append(dict(id=len(cams), name=tok[0], K=np.array([[fx, 0.0, cx], [0.0, fy, cy], [0.0, 0.0, 1.0]]), R=R,
+                         t=_mv3(R, -1.0 * t), C=t, radial=np.zeros(3), tangential=np.zeros(2), median_depth=None))
+        if pos >= len(lines):
+            break
+        line = lines[pos]; pos += 1
+    for c in cams:
+        c["worldpoints"] = mavmap_neighbors(c["id"], len(cams), neighbors)
+    return cams
+
+
+def read_openmvg(json_file, input_folder):
+    """sfm_data.json as main_openmvg.cpp:135-410 reads it -> list of the views its image loop adds, in the order of
+    `views`: dict(id = id_view, name, path = input_folder/name, K, R, t, C, radial, tangential, worldpoints = the keys of
+    the structure points that observe the view, in file order, median_depth = sorted float32 distances [n // 2]).
+    A view whose file does not exist is warned about and not visited, and its pose maps to no view (:169-187).  The camera
+    model of an intrinsic is its polymorphic_name when it has one, otherwise that of the element before it (:205-211);
+    an unknown model is warned about and has no distortion (:247-250).  t = -R C (:310).  A view is added when it has
+    worldpoints, its file exists and its intrinsic id is known (:374-375).  Empty views, intrinsics, extrinsics or
+    structure: ValueError with the reference's message (:145-149, :199-203, :282-286, :330-334)."""
+    import json
+    import os
+    import sys
+    with open(json_file) as f:
+        d = json.load(f)
+    views = d.get("views") or []
+    if not views:
+        raise ValueError("No aligned cameras in json file!")
+    found, pose2view = [], {}
+    for v in views:
+        data = v["value"]["ptr_wrapper"]["data"]
+        name, view_id = data["filename"], int(data["id_view"])
+        path = input_folder + "/" + name
+        if os.path.exists(path):
+            found.append(dict(id=view_id, name=name, path=path, intrinsic=int(data["id_intrinsic"])))
+            pose2view[int(data["id_pose"])] = view_id
+        else:
+            found.append(None)
+            print(f"WARNING: image '{name}' not found (ID={view_id})", file=sys.stderr)
+    intrinsics = d.get("intrinsics") or []
+    if not intrinsics:
+        raise ValueError("No intrinsics in json file!")
+    cams, model = {}, ""
+    for e in intrinsics:
+        data = e["value"]["ptr_wrapper"]["data"]
+        model = e["value"].get("polymorphic_name", model)
+        group = int(e["key"])
+        radial, tangential = np.zeros(3), np.zeros(2)
+        if model == "pinhole_radial_k3":
+            radial[:] = [float(x) for x in data["disto_k3"][:3]]
+        elif model == "pinhole_radial_k1":
+            radial[0] = float(data["disto_k1"][0])
+        elif model == "pinhole_brown_t2":
+            radial[:] = [float(x) for x in data["disto_t2"][:3]]
+            tangential[:] = [float(x) for x in data["disto_t2"][3:5]]
+        elif model != "pinhole":
+            print(f"WARNING: camera model '{model}' for group {group} unknown! No distortion assumed...", file=sys.stderr)
+        f_, pp = float(data["focal_length"]), data["principal_point"]
+        cams[group] = dict(K=np.array([[f_, 0.0, float(pp[0])], [0.0, f_, float(pp[1])], [0.0, 0.0, 1.0]]), radial=radial,
+                           tangential=tangential)
+    extrinsics = d.get("extrinsics") or []
+    if not extrinsics:
+        raise ValueError("No extrinsics in json file!")
+    poses = {}
+    for e in extrinsics:
+        pose = int(e["key"])
+        if pose in pose2view:
+            R = np.array(e["value"]["rotation"], np.float64).reshape(3, 3)
+            Cc = np.array(e["value"]["center"], np.float64).reshape(3)
+            poses[pose2view[pose]] = dict(R=R, t=_mv3(-R, Cc), C=Cc)
+        else:
+            print(f"WARNING: pose with ID {pose} does not map to an image!", file=sys.stderr)
+    structure = d.get("structure") or []
+    if not structure:
+        raise ValueError("No worldpoints in json file!")
+    wps, depths = {}, {}
+    for e in structure:
+        X = np.array(e["value"]["X"], np.float64).reshape(3)
+        for o in e["value"]["observations"]:
+            view = int(o["key"])
+            if view in poses:
+                wps.setdefault(view, []).append(int(e["key"]))
+                depths.setdefault(view, []).append(np.float32(np.linalg.norm(poses[view]["C"] - X)))
+    out = []
+    for v in found:
+        if v is not None and v["id"] in wps and v["intrinsic"] in cams:
+            dd = sorted(depths[v["id"]])
+            out.append(dict(id=v["id"], name=v["name"], path=v["path"], **cams[v["intrinsic"]], **poses[v["id"]],
+                            worldpoints=list(wps[v["id"]]), median_depth=dd[len(dd) // 2]))
+    return out
+
+
+def pix4d_files(params_folder, project_prefix):
+    """main_pix4d.cpp:163-168: the camera file and the tie-point file of a project"""
+    prefix = params_folder + "/" + project_prefix
+    if prefix[-1:] != "_":
+        prefix += "_"
+    return prefix + "calibrated_camera_parameters.txt", prefix + "tp_pix4d.txt"
+
+
+def read_pix4d(params_folder, project_prefix, device=0, triangulate=None):
+    """<prefix>_calibrated_camera_parameters.txt and <prefix>_tp_pix4d.txt as main_pix4d.cpp:162-420 reads them -> list of
+    the cameras its image loop adds, in file order: dict(id = position in the camera file, name, K, R, t, C, radial,
+    tangential, worldpoints = the feature ids of the camera's key, one per tie-point line, invalid ones included,
+    median_depth).
+    Camera file (:186-279): header lines up to the first line shorter than 2 characters; then blocks of `name width
+    height`, 3 rows of K, radial (3), tangential (2), the camera centre, 3 rows of R, until a line shorter than 5
+    characters; t = -R C, P = K [R | t]; the key of a camera is its name up to the last dot.
+    Tie-point file (:282-349): `id rest...` per line; an id shorter than 2 characters ends the file, one that starts with
+    '-' is skipped; a line of one token names the key image of the lines that follow (an unknown key maps to position 0,
+    as std::map::operator[] gives it, and counts as a camera in the printed total); any other line is `id px py scale`.
+    Every feature is triangulated from its observations (:354-372; `triangulate`, by default api.triangulate_points on
+    `device`): valid with more than two observations and norm(X) > L3D_EPS.  A camera is added when its key has features
+    and more than two of them are valid (:386-405); median_depth = sorted float32 distances to the valid ones [n // 2]."""
+    file1, file2 = pix4d_files(params_folder, project_prefix)
+    lines = _getlines(file1)
+    pos = 0
+    while pos < len(lines):
+        pos += 1
+        if len(lines[pos - 1]) < 2:
+            break
+    take = lambda: lines[pos] if pos < len(lines) else ""
+    cams, img2pos, pos2img = [], {}, {}
+    while pos < len(lines):
+        line = lines[pos]; pos += 1
+        if len(line) < 5:
+            break
+        name = (line.split() + [""])[0]
+        raw = name[:name.rfind(".")] if "." in name else name
+        img2pos[raw] = len(cams); pos2img[len(cams)] = raw
+        rows = []
+        for n in (3, 3, 3, 3, 2, 3, 3, 3, 3):                     # K, radial, tangential, centre, R
+            rows.append(_row(take(), n)); pos += 1
+        K, R = np.array(rows[0:3]), np.array(rows[6:9])
+        t = _mv3(-R, np.array(rows[5]))
+        cams.append(dict(id=len(cams), name=name, K=K, R=R, t=t, C=_mv3(R.T, -1.0 * t), radial=np.array(rows[3]),
+                         tangential=np.array(rows[4]), P=_mm3(K, np.column_stack([R, t]))))
+    per_cam, feat_id, obs = {}, {}, []
+    key, key_pos = "", 0
+    for line in _getlines(file2):
+        tok = line.split()
+        fid, rest = (tok + ["", ""])[:2]
+        if len(fid) < 2:
+            break
+        if fid[0] == "-":
+            continue
+        if rest == "":
+            key = fid
+            key_pos = img2pos.setdefault(key, 0)
+            continue
+        if fid not in feat_id:
+            feat_id[fid] = len(obs)
+            obs.append([])
+        per_cam.setdefault(key, []).append(feat_id[fid])
+        obs[feat_id[fid]].append((key_pos, _stream_double(tok[1]), _stream_double(tok[2]) if len(tok) > 2 else 0.0))
+    print(f"Pix4D: #cameras = {len(img2pos)}")
+    print(f"Pix4D: #points  = {len(obs)}")
+    print("triangulating...")
+    X, valid = np.zeros((len(obs), 3)), np.zeros(len(obs), bool)
+    if obs and cams:
+        if triangulate is None:
+            from .api import triangulate_points
+            triangulate = lambda *a: triangulate_points(*a, device=device)
+        off = np.concatenate([[0], np.cumsum([len(o) for o in obs])]).astype(np.uint64)
+        flat = [o for f in obs for o in f]
+        X, valid = triangulate(np.array([c["P"] for c in cams]), off, np.array([o[0] for o in flat], np.uint32),
+                               np.array([o[1:] for o in flat], np.float64).reshape(-1, 2))
+    out = []
+    for c in cams:
+        feats = per_cam.get(pos2img[c["id"]])
+        if feats is None:
+            continue
+        depths = sorted(np.float32(np.linalg.norm(X[f] - c["C"])) for f in feats if valid[f])
+        if len(depths) > 2:
+            out.append(dict(c, worldpoints=list(feats), median_depth=depths[len(depths) // 2]))
+    return out
+
+
 def front_end_undistortion(kind, entry, cols, rows):
     """(K, radial, tangential) as the reference's front end hands them to Line3D::undistortImage for the image of `entry`
     (cols x rows pixels), or None when it does not call it.  kind / entry: "nvm" and an element of read_nvm
@@ -439,7 +699,8 @@ def front_end_undistortion(kind, entry, cols, rows):
     (main_bundler.cpp:352-368: radial (d1, d2, 0), K from the image size), "colmap" and an element of read_colmap
     (main_colmap.cpp:377-389: the camera's five coefficients and K).  Each calls it only when a coefficient exceeds
     L3D_EPS in magnitude; main_vsfm and main_bundler skip a camera without worldpoints before that, main_colmap does
-    not."""
+    not.  "openmvg" and an element of read_openmvg: as colmap; "pix4d" and an element of read_pix4d: always (an entry of
+    another reader: ValueError, as for an unknown kind); "mavmap": never."""
     zero2 = np.zeros(2)
     if kind == "nvm":
         d = np.float32(entry["distortion"])
@@ -457,4 +718,14 @@ def front_end_undistortion(kind, entry, cols, rows):
         if not any(abs(float(v)) > L3D_EPS for v in (*radial, *tangential)):
             return None
         return np.array(entry["K"], np.float64), radial, tangential
-    raise ValueError(f"unknown front end {kind!r}: nvm, bundler or colmap")
+    if kind == "openmvg":        # main_openmvg.cpp:253-257, :384-393: like colmap's, the intrinsic group's coefficients and K
+        return front_end_undistortion("colmap", entry, cols, rows)
+    if kind == "pix4d":          # main_pix4d.cpp:410-413: every added view, whatever its coefficients
+        # This kind never answers None, so another reader's entry would be undistorted unasked: it is refused.  Only
+        # read_pix4d's entries carry the projection matrix the triangulation used.
+        if "P" not in entry:
+            raise ValueError('front end "pix4d" takes an element of read_pix4d')
+        return np.array(entry["K"], np.float64), np.array(entry["radial"], np.float64), np.array(entry["tangential"], np.float64)
+    if kind == "mavmap":         # main_mavmap.cpp:293-326: never
+        return None
+    raise ValueError(f"unknown front end {kind!r}: nvm, bundler, colmap, openmvg, pix4d or mavmap")
