@@ -75,8 +75,9 @@ typedef enum l3d_status {
     L3D_ERR_STATE = -7,        /* call order */
     L3D_ERR_HIP = -8,          /* HIP runtime error */
     L3D_ERR_LIMIT = -9,        /* size limit of this build */
-    L3D_ERR_RETRY = -10        /* l3d_match_finish after l3d_lists_shard: the record pools were enlarged, repeat
+    L3D_ERR_RETRY = -10,       /* l3d_match_finish after l3d_lists_shard: the record pools were enlarged, repeat
                                 * l3d_lists_shard + the exchange of its slabs + l3d_match_finish (every rank gets it) */
+    L3D_ERR_IO = -11           /* a binary input file is truncated, over-long or states a count it cannot hold */
 } l3d_status;
 
 typedef struct l3d_ctx l3d_ctx;
@@ -149,7 +150,8 @@ int l3d_nvm_get_camera(const l3d_nvm*, uint32_t index, l3d_nvm_camera* out);
 int l3d_nvm_get_worldpoints(const l3d_nvm*, uint32_t index, uint32_t* out, uint32_t cap);   /* = addImage's wps list */
 void l3d_nvm_close(l3d_nvm*);
 void l3d_nvm_intrinsics(float focal, uint32_t width, uint32_t height, double K[9]);          /* main_vsfm.cpp:272-282 */
-/* COLMAP text results (cameras.txt / images.txt / points3D.txt of a folder, main_colmap.cpp:136-348) and bundler files
+/* COLMAP results (cameras.txt / images.txt / points3D.txt of a folder, main_colmap.cpp:136-348; where cameras.txt is
+ * absent and cameras.bin, images.bin and points3D.bin all exist, COLMAP's binary form of the same: DESIGN §15) and bundler files
  * (bundle.rd.out, main_bundler.cpp:147-252) with what those front ends derive per image: K (COLMAP; bundler builds it
  * from the image size: l3d_nvm_intrinsics), R, t, C = R^T (-t), the distortion coefficients handed to undistortImage,
  * the worldpoint list and the median worldpoint distance handed to addImage.  Images in file order; `id` is the camID
@@ -172,6 +174,15 @@ uint32_t l3d_sfm_num_images(const l3d_sfm*);
 int l3d_sfm_get_image(const l3d_sfm*, uint32_t index, l3d_sfm_image* out);
 int l3d_sfm_get_worldpoints(const l3d_sfm*, uint32_t index, uint32_t* out, uint32_t cap);
 void l3d_sfm_close(l3d_sfm*);
+/* COLMAP's camera model of image `index` as l3d_undistort_images_model takes it (K_new all zero).  A model that has no
+ * l3d_camera_model form (SIMPLE_PINHOLE .. OPENCV, which l3d_sfm_image's five coefficients describe in full) and a
+ * bundler handle: model = L3D_CAM_NONE, K as in l3d_sfm_image, params zero.  The declaration of l3d_camera_model is
+ * with the undistortion entries below. */
+struct l3d_camera_model;
+int l3d_sfm_get_camera_model(const l3d_sfm*, uint32_t index, struct l3d_camera_model* out);
+/* COLMAP's name of the camera model of image `index` ("" for a bundler handle) and its raw parameter list in
+ * cameras.txt's order: up to `cap` values to params (may be NULL), *n = their number. */
+const char* l3d_sfm_get_camera_params(const l3d_sfm*, uint32_t index, double* params, uint32_t cap, uint32_t* n);
 /* The segment cache Line3D::detectLineSegments loads / stores per image when load_segments is set (line3D.cc:295-309,
  * 362-366): "<data folder>/segments_L3D++_<camID>_<width>x<height>_<max segments>.bin", the boost binary archive of a
  * one-row L3DPP::DataArray<float4> (dataArray.h:352-374).  segs4 = n x (x1, y1, x2, y2). */
@@ -242,6 +253,29 @@ typedef struct l3d_distortion { double K[9]; double radial[3]; double tangential
    cols*channels bytes, packed, and may be the input's own host memory.  Calls on one context are serialised. */
 int l3d_undistort_images(l3d_ctx*, uint32_t n_images, const l3d_image* in, const l3d_distortion* dist,
                          uint8_t* const* out);
+/* Undistortion by camera model: COLMAP's models beyond the five OpenCV coefficients.  params in COLMAP's
+ * order behind the focal lengths and the principal point, unused ones 0:
+ *   L3D_CAM_FULL_OPENCV            k1 k2 p1 p2 k3 k4 k5 k6
+ *   L3D_CAM_OPENCV_FISHEYE         k1 k2 k3 k4
+ *   L3D_CAM_SIMPLE_RADIAL_FISHEYE  k
+ *   L3D_CAM_RADIAL_FISHEYE         k1 k2
+ *   L3D_CAM_FOV                    omega
+ * K is the camera matrix of the input image, K_new that of the output image (all zero: K, which is what
+ * Line3D::undistortImage passes to initUndistortRectifyMap); of both only fx, fy, cx, cy are read. */
+enum { L3D_CAM_NONE = 0, L3D_CAM_FULL_OPENCV = 1, L3D_CAM_OPENCV_FISHEYE = 2, L3D_CAM_SIMPLE_RADIAL_FISHEYE = 3,
+       L3D_CAM_RADIAL_FISHEYE = 4, L3D_CAM_FOV = 5 };
+typedef struct l3d_camera_model {
+    uint32_t model;
+    uint32_t reserved;
+    double K[9];
+    double params[8];
+    double K_new[9];
+} l3d_camera_model;
+/* A batch in one launch; models and sizes may be mixed.  The checks of l3d_undistort_images (on K, on a non-zero K_new
+ * and on the model's parameters) and an unknown model (L3D_ERR_ARG) are made for every image before any pixel is
+ * read.  out[i] as for l3d_undistort_images. */
+int l3d_undistort_images_model(l3d_ctx*, uint32_t n_images, const l3d_image* in, const l3d_camera_model* cams,
+                               uint8_t* const* out);
 
 /* Line3D::matchImages (line3D.cc:375-497): the whole call on this context's GPU. */
 int l3d_match_images(l3d_ctx*, const l3d_match_params*);

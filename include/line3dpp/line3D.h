@@ -4,6 +4,7 @@
 //     Line3D(output_folder, load_segments, max_img_width, max_line_segments,
 //            neighbors_by_worldpoints=false, use_GPU=true)
 //     static undistortImage(inImg, outImg, radial_coeffs, tangential_coeffs, K)
+//     static undistortImage(inImg, outImg, model, params, K[, K_new])   (COLMAP's camera models beyond five coefficients)
 //     addImage(camID, image, K, R, t, median_depth, wps_or_neighbors, line_segments)
 //     matchImages(sigma_position, sigma_angle, num_neighbors, epipolar_overlap, kNN, const_regularization_depth)
 //     computeAffinityMatrix()            // the affinity part of reconstruct3Dlines()
@@ -22,6 +23,7 @@
 
 #include <cstdint>
 #include <cstring>
+#include <initializer_list>
 #include <iostream>
 #include <list>
 #include <map>
@@ -164,13 +166,17 @@ public:
         else { std::lock_guard<std::mutex> lk(lines_mu_); num_lines_[camID] = (uint32_t)line_segments.size(); }
     }
 
+    // (the third argument tells the two forms of undistortImage apart: a vector of coefficients or an L3D_CAM_* value)
+    template <class T> using IfModel = typename std::enable_if<std::is_integral<T>::value || std::is_enum<T>::value>::type;
+    template <class T> using IfNotModel = typename std::enable_if<!std::is_integral<T>::value && !std::is_enum<T>::value>::type;
+
     // static void Line3D::undistortImage(inImg, outImg, radial_coeffs, tangential_coeffs, K), line3D.h:110-122, on the GPU
     // (l3d_undistort_images).  InImage: cv::Mat, Image8U or ImageBuf8U (8-bit, 1 or 3 channels); OutImage:
     // cv::Mat or ImageBuf8U, made with outImg.create(rows, cols, inImg.type()) and written at outImg.step (it may be the
     // input itself).  Vec3 / Vec2: radial(i), tangential(i) (Eigen vectors); Mat3: K(r, c).  Errors are printed and leave
     // outImg empty.  Static like the reference's, so there is no instance context: one process-wide context on device 0,
     // made by the first call.  Calls from several threads (the front ends' OpenMP loops) run one after another on it.
-    template <class InImage, class OutImage, class Vec3, class Vec2, class Mat3>
+    template <class InImage, class OutImage, class Vec3, class Vec2, class Mat3, class = IfNotModel<Vec3>>
     static void undistortImage(const InImage& inImg, OutImage& outImg, const Vec3& radial_coeffs,
                                const Vec2& tangential_coeffs, const Mat3& K) {
         const int ty = inImg.type();
@@ -201,6 +207,31 @@ public:
         if (!tmp.empty())
             for (uint32_t r = 0; r < in.rows; ++r)
                 std::memcpy((uint8_t*)outImg.data + r * (size_t)outImg.step, tmp.data() + r * row, row);
+    }
+
+    // undistortImage by camera model (l3d_undistort_images_model) for COLMAP's models beyond the reference's
+    // five coefficients: model = L3D_CAM_FULL_OPENCV, _OPENCV_FISHEYE, _SIMPLE_RADIAL_FISHEYE, _RADIAL_FISHEYE or _FOV;
+    // params: the model's distortion parameters in COLMAP's order (std::vector<double>, an initializer list, anything
+    // with begin() / end(); at most 8, missing ones are 0); K: the camera matrix of inImg; K_new: that of outImg (left
+    // out: K).  Images, errors, threads and the context are those of the overload above.
+    template <class InImage, class OutImage, class Model, class Params, class Mat3, class = IfModel<Model>>
+    static void undistortImage(const InImage& inImg, OutImage& outImg, Model model, const Params& params, const Mat3& K,
+                               const Mat3& K_new) {
+        undistort_model(inImg, outImg, (uint32_t)model, params, K, &K_new);
+    }
+    template <class InImage, class OutImage, class Model, class Params, class Mat3, class = IfModel<Model>>
+    static void undistortImage(const InImage& inImg, OutImage& outImg, Model model, const Params& params, const Mat3& K) {
+        undistort_model(inImg, outImg, (uint32_t)model, params, K, (const Mat3*)nullptr);
+    }
+    template <class InImage, class OutImage, class Model, class Mat3, class = IfModel<Model>>
+    static void undistortImage(const InImage& inImg, OutImage& outImg, Model model, std::initializer_list<double> params,
+                               const Mat3& K, const Mat3& K_new) {
+        undistort_model(inImg, outImg, (uint32_t)model, params, K, &K_new);
+    }
+    template <class InImage, class OutImage, class Model, class Mat3, class = IfModel<Model>>
+    static void undistortImage(const InImage& inImg, OutImage& outImg, Model model, std::initializer_list<double> params,
+                               const Mat3& K) {
+        undistort_model(inImg, outImg, (uint32_t)model, params, K, (const Mat3*)nullptr);
     }
 
     // static Eigen::Matrix3d Line3D::rotationFromRPY(roll, pitch, yaw) and rotationFromQ(Qw, Qx, Qy, Qz), line3D.h:220-226
@@ -402,6 +433,47 @@ public:
     l3d_ctx* handle() { return ctx_; }
 
 private:
+    template <class InImage, class OutImage, class Params, class Mat3>
+    static void undistort_model(const InImage& inImg, OutImage& outImg, uint32_t model, const Params& params, const Mat3& K,
+                                const Mat3* K_new) {
+        const int ty = inImg.type();
+        const uint32_t ch = ty == 0 ? 1u : ty == 16 ? 3u : 0u;
+        const l3d_image in{(const uint8_t*)inImg.data, (uint32_t)inImg.cols, (uint32_t)inImg.rows, ch,
+                           (uint32_t)(size_t)inImg.step};
+        l3d_camera_model m{};
+        m.model = model;
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) {
+                m.K[3 * r + c] = K(r, c);
+                if (K_new) m.K_new[3 * r + c] = (*K_new)(r, c);
+            }
+        size_t n_params = 0;
+        for (double v : params) {
+            if (n_params < 8) m.params[n_params] = v;
+            ++n_params;
+        }
+        const size_t row = (size_t)in.cols * ch;
+        std::vector<uint8_t> tmp;
+        uint8_t* dst = nullptr;
+        if (ch) {
+            outImg.create(inImg.rows, inImg.cols, ty);
+            if ((size_t)outImg.step == row) dst = (uint8_t*)outImg.data;
+            else { tmp.resize(row * in.rows); dst = tmp.data(); }
+        }
+        l3d_ctx* ctx = undistort_context();
+        const int rc = n_params > 8 ? L3D_ERR_ARG : ctx ? l3d_undistort_images_model(ctx, 1, &in, &m, &dst) : L3D_ERR_HIP;
+        if (rc != L3D_OK) {
+            std::cout << "[L3D++] ERROR: undistortImage: "
+                      << (n_params > 8 ? "more than 8 distortion parameters" : ctx ? l3d_last_error() : "no HIP context on device 0")
+                      << std::endl;
+            outImg.release();
+            return;
+        }
+        if (!tmp.empty())
+            for (uint32_t r = 0; r < in.rows; ++r)
+                std::memcpy((uint8_t*)outImg.data + r * (size_t)outImg.step, tmp.data() + r * row, row);
+    }
+
     // the context of the static undistortImage: made once, thread-safely, by the first call; it lives as long as the
     // process (destroying it from a static destructor could run after the HIP runtime's own teardown)
     static l3d_ctx* undistort_context() {

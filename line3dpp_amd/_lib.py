@@ -28,6 +28,7 @@ FLOAT4_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("w", "<f4")]
 assert MATCH_DTYPE.itemsize == 40 and SLOT_DTYPE.itemsize == 32 and SEGMENT3D_DTYPE.itemsize == 80
 EMPTY = 0xFFFFFFFF
 L3D_ERR_NO_SEGMENTS = -5
+L3D_ERR_IO = -11
 
 
 class MatchParams(C.Structure):
@@ -80,6 +81,17 @@ class Distortion(C.Structure):
     _fields_ = [("K", C.c_double * 9), ("radial", C.c_double * 3), ("tangential", C.c_double * 2)]
 
 
+# L3D_CAM_* (include/l3dpp_hip.h) by COLMAP's model name, and the number of distortion parameters each takes
+CAMERA_MODELS = {"FULL_OPENCV": 1, "OPENCV_FISHEYE": 2, "SIMPLE_RADIAL_FISHEYE": 3, "RADIAL_FISHEYE": 4, "FOV": 5}
+CAMERA_MODEL_PARAMS = {"FULL_OPENCV": 8, "OPENCV_FISHEYE": 4, "SIMPLE_RADIAL_FISHEYE": 1, "RADIAL_FISHEYE": 2, "FOV": 1}
+
+
+class CameraModel(C.Structure):
+    """l3d_camera_model (include/l3dpp_hip.h): the arguments of undistortion by camera model"""
+    _fields_ = [("model", C.c_uint32), ("reserved", C.c_uint32), ("K", C.c_double * 9), ("params", C.c_double * 8),
+                ("K_new", C.c_double * 9)]
+
+
 class DetectStats(C.Structure):
     """l3d_detect_stats (include/l3dpp_hip.h)"""
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("raw_segments", C.c_uint32), ("segments", C.c_uint32),
@@ -107,6 +119,7 @@ EXPORTS = [
     "l3d_line_opt_stats", "l3d_line_to_cayley", "l3d_cayley_to_segment", "l3d_line_opt_eval", "l3d_get_fresh_hyp",
     "l3d_detect_segments", "l3d_detect_view_segments", "l3d_get_detected_segments", "l3d_get_detect_stats",
     "l3d_add_view_image", "l3d_add_view_image_worldpoints", "l3d_undistort_images",
+    "l3d_undistort_images_model", "l3d_sfm_get_camera_model", "l3d_sfm_get_camera_params",
     "l3d_triangulate_points", "l3d_rotation_from_rpy", "l3d_rotation_from_q", "l3d_decompose_projection_matrix",
 ]
 
@@ -214,6 +227,9 @@ def load():
     L.l3d_add_view_image_worldpoints.argtypes = [vp, u32, C.POINTER(Image), C.POINTER(DetectOptions), vp, vp, vp, f32,
                                                  vp, u32, C.POINTER(u32)]
     L.l3d_undistort_images.argtypes = [vp, u32, vp, vp, vp]
+    L.l3d_undistort_images_model.argtypes = [vp, u32, vp, vp, vp]
+    L.l3d_sfm_get_camera_model.argtypes = [vp, u32, vp]
+    L.l3d_sfm_get_camera_params.argtypes = [vp, u32, vp, u32, vp]; L.l3d_sfm_get_camera_params.restype = C.c_char_p
     L.l3d_score_matches.argtypes = [i32, vp, u32, vp, vp, vp, u32, vp, vp, f32, f32, vp]
     L.l3d_triangulate_points.argtypes = [i32, u32, vp, u64, vp, vp, vp, vp, vp]
     f64 = C.c_double

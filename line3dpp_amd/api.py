@@ -116,6 +116,16 @@ class Line3D:
             print(f"{Line3D.PREFIX}ERROR: undistortImage: {e}")
             return None
 
+    # undistortImage for COLMAP's camera models beyond five coefficients: model = COLMAP's name, params in
+    # its order; K_new = the camera matrix of the returned image (None: K).  None after an error, which is printed
+    @staticmethod
+    def undistortImageModel(img, model, K, params, K_new=None):
+        try:
+            return lsd.undistort_images_model([img], [model], [K], [params], [K_new])[0]
+        except (RuntimeError, TypeError, ValueError) as e:
+            print(f"{Line3D.PREFIX}ERROR: undistortImage: {e}")
+            return None
+
     # static members of the reference's Line3D (line3D.cc:2714-2754, :2784-2853), through the C-ABI (host code)
     @staticmethod
     def rotationFromRPY(roll, pitch, yaw):

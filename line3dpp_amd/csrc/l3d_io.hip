@@ -111,10 +111,14 @@ void l3d_nvm_intrinsics(float focal, uint32_t width, uint32_t height, double K[9
     K[0] = focal; K[4] = focal; K[2] = px; K[5] = py; K[8] = 1.0;
 }
 
-// ---- COLMAP text result and bundler file: one handle type, one record per image ----------------------------------------
+// ---- COLMAP result and bundler file: one handle type, one record per image ---------------------------------------------
 // l3d_sfm_open_colmap: cameras.txt / images.txt / points3D.txt of a COLMAP result folder as main_colmap.cpp:136-348 reads
 // them -- lines that start with '#' are skipped in the first two files; camera models SIMPLE_PINHOLE, PINHOLE,
-// SIMPLE_RADIAL, RADIAL, OPENCV, FULL_OPENCV (:177-219, anything else is an error: -3 there); images.txt alternates an
+// SIMPLE_RADIAL, RADIAL, OPENCV, FULL_OPENCV (:177-219; the reference drops FULL_OPENCV's k4 k5 k6, here they are kept in
+// the parameter list and l3d_sfm_get_camera_model hands them to the undistortion by camera model) and, beyond
+// the reference, OPENCV_FISHEYE, SIMPLE_RADIAL_FISHEYE, RADIAL_FISHEYE and FOV (K from their focal lengths and principal
+// point, the five coefficients zero); anything else, THIN_PRISM_FISHEYE included, is an error (-3 there); without a
+// cameras.txt, cameras.bin / images.bin / points3D.bin (COLMAP's binary model) fill the same records; images.txt alternates an
 // image line (id, quaternion w x y z, t, camera id, name) with a line of 2D points (x y POINT3D_ID ...), of which the
 // non-negative ids are the worldpoint list handed to addImage; an image whose camera is unknown is dropped (:281);
 // R = rotationFromQ (line3D.cc:2730-2754: s = 2 / |q|^2, 0 for a vanishing quaternion), C = R^T (-t); points3D.txt: EVERY
@@ -134,6 +138,9 @@ struct l3d_sfm {
         double K[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, R[9], t[3], C[3], radial[3] = {0, 0, 0}, tangential[2] = {0, 0};
         float focal = 0, median_depth = 0;
         std::vector<uint32_t> worldpoints;
+        std::string model;                                      // COLMAP's name of the camera model ("" for bundler)
+        double params[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // cameras.txt's parameter list
+        uint32_t n_params = 0;
     };
     std::vector<Img> imgs;
 };
@@ -155,88 +162,266 @@ static void centre_from(const double R[9], const double t[3], double C[3]) {   /
 }
 static float median_of(std::vector<float>& d) { std::sort(d.begin(), d.end()); return d[d.size() / 2]; }
 
+// ---- COLMAP: the records both parsers fill, and the code behind them -----------------------------------------------
+extern "C++" {
+namespace {
+
+// COLMAP's camera models in the order of their binary ids, with the length of their parameter lists.  Models 0-4 and 6
+// are main_colmap.cpp's (:177-219); 5, 7, 8, 9 are undistorted by camera model; 10 stays unknown.
+struct ColmapModel { const char* name; uint32_t n_params; bool known; };
+const ColmapModel kColmapModels[] = {
+    {"SIMPLE_PINHOLE", 3, true}, {"PINHOLE", 4, true}, {"SIMPLE_RADIAL", 4, true}, {"RADIAL", 5, true},
+    {"OPENCV", 8, true}, {"OPENCV_FISHEYE", 8, true}, {"FULL_OPENCV", 12, true}, {"FOV", 5, true},
+    {"SIMPLE_RADIAL_FISHEYE", 4, true}, {"RADIAL_FISHEYE", 5, true}, {"THIN_PRISM_FISHEYE", 12, false}};
+
+struct ColmapCam {
+    std::string model;
+    uint32_t w = 0, h = 0, n_params = 0;
+    double params[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    double K[9], radial[3], tangential[2];
+};
+struct ColmapImage {                       // an image of images.txt / images.bin
+    uint32_t id = 0, cam = 0;
+    double q[4] = {0, 0, 0, 0}, t[3] = {0, 0, 0};
+    std::string name;
+    bool has_points = false;               // the line of 2D points was there (text: the file may end before it)
+    std::vector<int> point_ids;            // POINT3D_ID of every 2D point, as atoi gives it
+};
+struct ColmapPoint { uint32_t id; double X, Y, Z; };
+
+// K and the five coefficients of undistortImage from a model's parameter list (p: 12 values, missing ones 0)
+bool colmap_camera(const std::string& model, const double* p, ColmapCam& c) {
+    double fx = 0, fy = 0, cx = 0, cy = 0, k1 = 0, k2 = 0, k3 = 0, p1 = 0, p2 = 0;
+    uint32_t idx = 0;
+    for (; idx < 11; ++idx)
+        if (model == kColmapModels[idx].name) break;
+    if (idx == 11 || !kColmapModels[idx].known) return false;
+    if (model == "SIMPLE_PINHOLE") { fx = p[0]; cx = p[1]; cy = p[2]; fy = fx; }
+    else if (model == "PINHOLE" || model == "FOV" || model == "OPENCV_FISHEYE") { fx = p[0]; fy = p[1]; cx = p[2]; cy = p[3]; }
+    else if (model == "SIMPLE_RADIAL") { fx = p[0]; cx = p[1]; cy = p[2]; k1 = p[3]; fy = fx; }
+    else if (model == "RADIAL") { fx = p[0]; cx = p[1]; cy = p[2]; k1 = p[3]; k2 = p[4]; fy = fx; }
+    else if (model == "SIMPLE_RADIAL_FISHEYE" || model == "RADIAL_FISHEYE") { fx = p[0]; cx = p[1]; cy = p[2]; fy = fx; }
+    else if (model == "OPENCV") { fx = p[0]; fy = p[1]; cx = p[2]; cy = p[3]; k1 = p[4]; k2 = p[5]; p1 = p[6]; p2 = p[7]; }
+    else { fx = p[0]; fy = p[1]; cx = p[2]; cy = p[3]; k1 = p[4]; k2 = p[5]; p1 = p[6]; p2 = p[7]; k3 = p[8]; }   // FULL_OPENCV
+    c.model = model;
+    c.n_params = kColmapModels[idx].n_params;
+    for (uint32_t k = 0; k < 12; ++k) c.params[k] = k < c.n_params ? p[k] : 0.0;
+    const double K[9] = {fx, 0, cx, 0, fy, cy, 0, 0, 1};
+    std::memcpy(c.K, K, 72);
+    c.radial[0] = k1; c.radial[1] = k2; c.radial[2] = k3; c.tangential[0] = p1; c.tangential[1] = p2;
+    return true;
+}
+
+// what main_colmap.cpp derives from the three files (:236-348, :390-406), whichever form they were read in
+void colmap_build(const std::map<uint32_t, ColmapCam>& cams, const std::vector<ColmapImage>& images,
+                  const std::vector<ColmapPoint>& points, l3d_sfm& sfm) {
+    std::map<uint32_t, size_t> by_id;                          // image id -> record (a repeated id overwrites, like the maps there)
+    std::map<uint32_t, d3> wps;                                // worldpoints seen in the images (origin until points3D says otherwise)
+    for (const ColmapImage& r : images) {
+        auto ci = cams.find(r.cam);
+        if (ci == cams.end()) continue;                        // unknown camera: dropped (:281)
+        const ColmapCam& cam = ci->second;
+        l3d_sfm::Img im;
+        im.id = r.id; im.cam = r.cam; im.name = r.name; im.width = cam.w; im.height = cam.h;
+        std::memcpy(im.K, cam.K, 72); std::memcpy(im.radial, cam.radial, 24); std::memcpy(im.tangential, cam.tangential, 16);
+        im.model = cam.model; im.n_params = cam.n_params; std::memcpy(im.params, cam.params, 96);
+        rotation_from_q(r.q[0], r.q[1], r.q[2], r.q[3], im.R);
+        im.t[0] = r.t[0]; im.t[1] = r.t[1]; im.t[2] = r.t[2];
+        centre_from(im.R, im.t, im.C);
+        im.focal = (float)im.K[0];
+        auto it = by_id.find(r.id);
+        if (it == by_id.end()) { by_id[r.id] = sfm.imgs.size(); sfm.imgs.push_back(im); }
+        else { im.worldpoints = sfm.imgs[it->second].worldpoints; sfm.imgs[it->second] = im; sfm.imgs.push_back(im); by_id[r.id] = sfm.imgs.size() - 1; }
+        if (r.has_points) {
+            std::vector<uint32_t> list;
+            for (int id : r.point_ids)
+                if (id >= 0) { list.push_back((uint32_t)id); wps[(uint32_t)id] = d3{0, 0, 0}; }
+            sfm.imgs[by_id[r.id]].worldpoints = list;
+        }
+    }
+    for (const ColmapPoint& p : points) {
+        auto it = wps.find(p.id);
+        if (it != wps.end()) it->second = d3{p.X, p.Y, p.Z};
+    }
+    // a repeated image id: img_seq holds it twice, both entries see the LAST pose and list (the maps are keyed by id)
+    for (auto& im : sfm.imgs) { const l3d_sfm::Img& last = sfm.imgs[by_id[im.id]]; if (&last != &im) im = last; }
+    for (auto& im : sfm.imgs) {
+        std::vector<float> depths;
+        for (uint32_t w : im.worldpoints) depths.push_back((float)norm(d3{im.C[0], im.C[1], im.C[2]} - wps[w]));
+        if (!depths.empty()) im.median_depth = median_of(depths);
+    }
+}
+
+// a COLMAP binary file in memory, read with a cursor that never passes its end
+struct BinFile {
+    std::string name;
+    std::vector<char> buf;
+    size_t pos = 0;
+    bool open(const std::string& dir, const char* file) {
+        name = file;
+        std::ifstream f(dir + "/" + file, std::ios::binary);
+        if (!f) return false;
+        buf.assign(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
+        return true;
+    }
+    size_t left() const { return buf.size() - pos; }
+    template <class T> bool get(T& v) {
+        if (left() < sizeof(T)) return false;
+        std::memcpy(&v, buf.data() + pos, sizeof(T));          // (little-endian, as the hosts of this library are)
+        pos += sizeof(T);
+        return true;
+    }
+    bool doubles(double* v, size_t n) {
+        if (left() / 8 < n) return false;
+        std::memcpy(v, buf.data() + pos, 8 * n);
+        pos += 8 * n;
+        return true;
+    }
+    int truncated() const { return fail(L3D_ERR_IO, name + ": the file ends inside a record (truncated?)"); }
+    int too_many(uint64_t n, const char* what) const {
+        return fail(L3D_ERR_IO, name + ": " + std::to_string(n) + " " + what + " cannot fit in the " + std::to_string(left()) + " bytes that follow");
+    }
+    int finish() const { return pos == buf.size() ? L3D_OK : fail(L3D_ERR_IO, name + ": " + std::to_string(left()) + " bytes behind the last record"); }
+};
+
+// POINT3D_ID of images.bin as the text reader's atoi sees the same number in decimal: strtol saturates at LONG_MAX and
+// the int keeps its low 32 bits, so 2^64 - 1 ("no point") is -1
+int atoi_of(uint64_t id) { return (int)(long)std::min<uint64_t>(id, (uint64_t)LONG_MAX); }
+
+int colmap_read_binary(const std::string& dir, std::map<uint32_t, ColmapCam>& cams, std::vector<ColmapImage>& images,
+                       std::vector<ColmapPoint>& points) {
+    BinFile fc, fi, fp;
+    if (!fc.open(dir, "cameras.bin") || !fi.open(dir, "images.bin") || !fp.open(dir, "points3D.bin"))
+        return fail(L3D_ERR_ARG, "at least one of the colmap result files does not exist in sfm folder: " + dir);
+    uint64_t n = 0;
+    if (!fc.get(n)) return fc.truncated();
+    if (n > fc.left() / 48) return fc.too_many(n, "cameras");           // a camera is at least 24 + 3 x 8 bytes
+    for (uint64_t i = 0; i < n; ++i) {
+        uint32_t id = 0; int32_t model = 0; uint64_t w = 0, h = 0;
+        if (!fc.get(id) || !fc.get(model) || !fc.get(w) || !fc.get(h)) return fc.truncated();
+        if (model < 0 || model > 10 || !kColmapModels[model].known)
+            return fail(L3D_ERR_ARG, "camera model " + (model >= 0 && model <= 10 ? std::string(kColmapModels[model].name) : std::to_string(model)) + " unknown!");
+        if (w > UINT32_MAX || h > UINT32_MAX) return fail(L3D_ERR_IO, fc.name + ": image size of camera " + std::to_string(id) + " beyond 32 bits");
+        double p[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        if (!fc.doubles(p, kColmapModels[model].n_params)) return fc.truncated();
+        ColmapCam c;
+        colmap_camera(kColmapModels[model].name, p, c);
+        c.w = (uint32_t)w; c.h = (uint32_t)h;
+        cams[id] = c;
+    }
+    if (int rc = fc.finish()) return rc;
+    if (!fi.get(n)) return fi.truncated();
+    if (n > fi.left() / 73) return fi.too_many(n, "images");            // an image with an empty name and no points
+    images.reserve(n);
+    for (uint64_t i = 0; i < n; ++i) {
+        ColmapImage r;
+        uint64_t m = 0;
+        if (!fi.get(r.id) || !fi.doubles(r.q, 4) || !fi.doubles(r.t, 3) || !fi.get(r.cam)) return fi.truncated();
+        const char* s = fi.buf.data() + fi.pos;
+        const void* z = std::memchr(s, 0, fi.left());
+        if (!z) return fi.truncated();
+        r.name.assign(s, (const char*)z);
+        fi.pos += r.name.size() + 1;
+        if (!fi.get(m)) return fi.truncated();
+        if (m > fi.left() / 24) return fi.too_many(m, "2D points");
+        r.has_points = true;
+        r.point_ids.reserve(m);
+        for (uint64_t k = 0; k < m; ++k) {
+            double xy[2]; uint64_t pid = 0;
+            if (!fi.doubles(xy, 2) || !fi.get(pid)) return fi.truncated();
+            r.point_ids.push_back(atoi_of(pid));
+        }
+        images.push_back(std::move(r));
+    }
+    if (int rc = fi.finish()) return rc;
+    if (!fp.get(n)) return fp.truncated();
+    if (n > fp.left() / 51) return fp.too_many(n, "3D points");         // a point with an empty track
+    points.reserve(n);
+    for (uint64_t i = 0; i < n; ++i) {
+        uint64_t id = 0, track = 0; double xyz[3], err = 0; uint8_t rgb[3];
+        if (!fp.get(id) || !fp.doubles(xyz, 3) || !fp.get(rgb) || !fp.get(err) || !fp.get(track)) return fp.truncated();
+        if (track > fp.left() / 8) return fp.too_many(track, "track elements");
+        fp.pos += 8 * track;
+        if (id <= UINT32_MAX) points.push_back(ColmapPoint{(uint32_t)id, xyz[0], xyz[1], xyz[2]});   // (the text reader's `>> uint32_t` fails beyond)
+    }
+    return fp.finish();
+}
+
+}  // namespace
+}  // extern "C++"
 
 int l3d_sfm_open_colmap(const char* folder, l3d_sfm** out) {
     if (!folder || !out) return fail(L3D_ERR_ARG, "null argument");
     *out = nullptr;
     const std::string dir(folder);
-    std::ifstream fc(dir + "/cameras.txt"), fi(dir + "/images.txt"), fp(dir + "/points3D.txt");
-    if (!fc || !fi || !fp) return fail(L3D_ERR_ARG, "at least one of the colmap result files does not exist in sfm folder: " + dir);
-    struct Cam { double K[9], radial[3], tangential[2]; uint32_t w, h; };
-    std::map<uint32_t, Cam> cams;
-    std::string line;
-    while (std::getline(fc, line)) {
-        if (line.substr(0, 1) == "#") continue;
-        std::stringstream s(line);
-        uint32_t id = 0, w = 0, h = 0; std::string model;
-        s >> id >> model >> w >> h;
-        double fx = 0, fy = 0, cx = 0, cy = 0, k1 = 0, k2 = 0, k3 = 0, p1 = 0, p2 = 0;
-        if (model == "SIMPLE_PINHOLE") { s >> fx >> cx >> cy; fy = fx; }
-        else if (model == "PINHOLE") s >> fx >> fy >> cx >> cy;
-        else if (model == "SIMPLE_RADIAL") { s >> fx >> cx >> cy >> k1; fy = fx; }
-        else if (model == "RADIAL") { s >> fx >> cx >> cy >> k1 >> k2; fy = fx; }
-        else if (model == "OPENCV") s >> fx >> fy >> cx >> cy >> k1 >> k2 >> p1 >> p2;
-        else if (model == "FULL_OPENCV") s >> fx >> fy >> cx >> cy >> k1 >> k2 >> p1 >> p2 >> k3;
-        else return fail(L3D_ERR_ARG, "camera model " + model + " unknown!");
-        Cam c{{fx, 0, cx, 0, fy, cy, 0, 0, 1}, {k1, k2, k3}, {p1, p2}, w, h};
-        cams[id] = c;
-    }
-    auto sfm = std::make_unique<l3d_sfm>();
-    std::map<uint32_t, size_t> by_id;                          // image id -> record (a repeated id overwrites, like the maps there)
-    std::map<uint32_t, d3> wps;                                // worldpoints seen in images.txt (origin until points3D.txt says otherwise)
-    bool first = true;
-    uint32_t img_id = 0, cam_id = 0;
-    while (std::getline(fi, line)) {
-        if (line.substr(0, 1) == "#") continue;
-        std::stringstream s(line);
-        if (first) {
-            double qw = 0, qx = 0, qy = 0, qz = 0, tx = 0, ty = 0, tz = 0; std::string name;
-            s >> img_id >> qw >> qx >> qy >> qz >> tx >> ty >> tz >> cam_id >> name;
-            auto ci = cams.find(cam_id);
-            if (ci != cams.end()) {
-                l3d_sfm::Img im;
-                im.id = img_id; im.cam = cam_id; im.name = name; im.width = ci->second.w; im.height = ci->second.h;
-                std::memcpy(im.K, ci->second.K, 72); std::memcpy(im.radial, ci->second.radial, 24); std::memcpy(im.tangential, ci->second.tangential, 16);
-                rotation_from_q(qw, qx, qy, qz, im.R);
-                im.t[0] = tx; im.t[1] = ty; im.t[2] = tz;
-                centre_from(im.R, im.t, im.C);
-                im.focal = (float)im.K[0];
-                auto it = by_id.find(img_id);
-                if (it == by_id.end()) { by_id[img_id] = sfm->imgs.size(); sfm->imgs.push_back(im); }
-                else { im.worldpoints = sfm->imgs[it->second].worldpoints; sfm->imgs[it->second] = im; sfm->imgs.push_back(im); by_id[img_id] = sfm->imgs.size() - 1; }
+    std::map<uint32_t, ColmapCam> cams;
+    std::vector<ColmapImage> images;
+    std::vector<ColmapPoint> points;
+    std::ifstream fc(dir + "/cameras.txt");
+    if (!fc) {
+        // COLMAP's binary model, its default output: taken when there is no cameras.txt and all three .bin files exist
+        const bool bin = std::ifstream(dir + "/cameras.bin").good() && std::ifstream(dir + "/images.bin").good() &&
+                         std::ifstream(dir + "/points3D.bin").good();
+        if (!bin) return fail(L3D_ERR_ARG, "at least one of the colmap result files does not exist in sfm folder: " + dir);
+        if (int rc = colmap_read_binary(dir, cams, images, points)) return rc;
+    } else {
+        std::ifstream fi(dir + "/images.txt"), fp(dir + "/points3D.txt");
+        if (!fi || !fp) return fail(L3D_ERR_ARG, "at least one of the colmap result files does not exist in sfm folder: " + dir);
+        std::string line;
+        while (std::getline(fc, line)) {
+            if (line.substr(0, 1) == "#") continue;
+            std::stringstream s(line);
+            uint32_t id = 0, w = 0, h = 0; std::string model;
+            s >> id >> model >> w >> h;
+            double p[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+            uint32_t np = 0;
+            for (const ColmapModel& m : kColmapModels)
+                if (m.known && model == m.name) np = m.n_params;
+            for (uint32_t k = 0; k < np; ++k) {
+                double v = 0;
+                s >> v;
+                p[k] = v;
             }
-            first = false;
-        } else {
-            if (cams.count(cam_id)) {
-                std::vector<uint32_t> list;
-                for (;;) {
-                    double x, y; std::string wp;
-                    s >> x >> y >> wp;
-                    if (wp.empty()) break;
-                    const int id = std::atoi(wp.c_str());
-                    if (id >= 0) { list.push_back((uint32_t)id); wps[(uint32_t)id] = d3{0, 0, 0}; }
+            ColmapCam c;
+            if (!colmap_camera(model, p, c)) return fail(L3D_ERR_ARG, "camera model " + model + " unknown!");
+            c.w = w; c.h = h;
+            cams[id] = c;
+        }
+        bool first = true;
+        uint32_t img_id = 0, cam_id = 0;                       // (outside the loop as there: a line that does not parse keeps the last camera id)
+        while (std::getline(fi, line)) {
+            if (line.substr(0, 1) == "#") continue;
+            std::stringstream s(line);
+            if (first) {
+                ColmapImage r;
+                s >> img_id >> r.q[0] >> r.q[1] >> r.q[2] >> r.q[3] >> r.t[0] >> r.t[1] >> r.t[2] >> cam_id >> r.name;
+                r.id = img_id; r.cam = cam_id;
+                images.push_back(r);
+                first = false;
+            } else {
+                ColmapImage& r = images.back();
+                if (cams.count(r.cam)) {
+                    r.has_points = true;
+                    for (;;) {
+                        double x, y; std::string wp;
+                        s >> x >> y >> wp;
+                        if (wp.empty()) break;
+                        r.point_ids.push_back(std::atoi(wp.c_str()));
+                    }
                 }
-                auto it = by_id.find(img_id);
-                if (it != by_id.end()) sfm->imgs[it->second].worldpoints = list;
+                first = true;
             }
-            first = true;
+        }
+        while (std::getline(fp, line)) {
+            std::stringstream s(line);
+            uint32_t id = 0; double X = 0, Y = 0, Z = 0;
+            s >> id >> X >> Y >> Z;
+            if (!s) continue;                                  // (a comment or malformed line)
+            points.push_back(ColmapPoint{id, X, Y, Z});
         }
     }
-    while (std::getline(fp, line)) {
-        std::stringstream s(line);
-        uint32_t id = 0; double X = 0, Y = 0, Z = 0;
-        s >> id >> X >> Y >> Z;
-        if (!s) continue;                                      // (a comment or malformed line)
-        auto it = wps.find(id);
-        if (it != wps.end()) it->second = d3{X, Y, Z};
-    }
-    // a repeated image id: img_seq holds it twice, both entries see the LAST pose and list (the maps are keyed by id)
-    for (auto& im : sfm->imgs) { const l3d_sfm::Img& last = sfm->imgs[by_id[im.id]]; if (&last != &im) im = last; }
-    for (auto& im : sfm->imgs) {
-        std::vector<float> depths;
-        for (uint32_t w : im.worldpoints) depths.push_back((float)norm(d3{im.C[0], im.C[1], im.C[2]} - wps[w]));
-        if (!depths.empty()) im.median_depth = median_of(depths);
-    }
+    auto sfm = std::make_unique<l3d_sfm>();
+    colmap_build(cams, images, points, *sfm);
     *out = sfm.release();
     return L3D_OK;
 }
@@ -310,6 +495,33 @@ int l3d_sfm_get_worldpoints(const l3d_sfm* s, uint32_t i, uint32_t* out, uint32_
 }
 
 void l3d_sfm_close(l3d_sfm* s) { delete s; }
+
+int l3d_sfm_get_camera_model(const l3d_sfm* s, uint32_t i, l3d_camera_model* out) {
+    if (!s || !out || i >= s->imgs.size()) return fail(L3D_ERR_ARG, "bad argument");
+    const l3d_sfm::Img& im = s->imgs[i];
+    *out = l3d_camera_model{};
+    std::memcpy(out->K, im.K, 72);
+    // (model, first distortion parameter in the list, their number)
+    struct { const char* name; uint32_t model, first, n; } const forms[] = {
+        {"FULL_OPENCV", L3D_CAM_FULL_OPENCV, 4, 8}, {"OPENCV_FISHEYE", L3D_CAM_OPENCV_FISHEYE, 4, 4},
+        {"SIMPLE_RADIAL_FISHEYE", L3D_CAM_SIMPLE_RADIAL_FISHEYE, 3, 1}, {"RADIAL_FISHEYE", L3D_CAM_RADIAL_FISHEYE, 3, 2},
+        {"FOV", L3D_CAM_FOV, 4, 1}};
+    for (const auto& f : forms)
+        if (im.model == f.name) {
+            out->model = f.model;
+            for (uint32_t k = 0; k < f.n; ++k) out->params[k] = im.params[f.first + k];
+        }
+    return L3D_OK;
+}
+
+const char* l3d_sfm_get_camera_params(const l3d_sfm* s, uint32_t i, double* params, uint32_t cap, uint32_t* n) {
+    if (n) *n = 0;
+    if (!s || i >= s->imgs.size() || (cap && !params)) { fail(L3D_ERR_ARG, "bad argument"); return nullptr; }
+    const l3d_sfm::Img& im = s->imgs[i];
+    if (n) *n = im.n_params;
+    for (uint32_t k = 0; k < std::min(cap, im.n_params); ++k) params[k] = im.params[k];
+    return im.model.c_str();
+}
 
 
 

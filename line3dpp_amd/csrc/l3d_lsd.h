@@ -73,4 +73,14 @@ struct UndImage {
 
 hipError_t launch_undistort(const UndImage* d_imgs, uint32_t n, uint32_t max_pix, hipStream_t st);
 
+// one image of an undistortion batch by camera model.  The UndImage part: w, ir4, ir5 and xtab are of the
+// OUTPUT image's camera matrix, fx, fy, cx, cy of the input's; k1, k2, k3, p1, p2 are FULL_OPENCV's.  model is an
+// L3D_CAM_* value, the same for a whole workgroup (grid.y = image).
+struct UndModelImage : UndImage {
+    uint32_t model;
+    double q[4];                   // FULL_OPENCV: k4 k5 k6; the fisheye family: k1 k2 k3 k4; FOV: omega, omega^2, tan(omega / 2)
+};
+
+hipError_t launch_undistort_model(const UndModelImage* d_imgs, uint32_t n, uint32_t max_pix, hipStream_t st);
+
 }  // namespace l3d

@@ -286,33 +286,29 @@ int check_undistort(const l3d_image& im, const l3d_distortion& d) {
     return L3D_OK;
 }
 
-// Line3D::undistortImage for a batch: inputs up, one k_undistort launch, outputs down
-int undistort(l3d_ctx* c, uint32_t n, const l3d_image* in, const l3d_distortion* dist, uint8_t* const* out) {
-    if (!c || (n && (!in || !dist || !out))) return fail(L3D_ERR_ARG, "null argument");
-    for (uint32_t i = 0; i < n; ++i) {
-        if (int rc = check_undistort(in[i], dist[i])) return rc;
-        if (!out[i]) return fail(L3D_ERR_ARG, "null argument");
-    }
+// The batch behind both undistortion entries: inputs up, one launch (grid.y = image), outputs down.  Rec is
+// the kernel's per-image record; fill(i, U) sets its coefficients and fx, fy, cx, cy and returns the camera matrix of
+// the OUTPUT image, from which the inverse and the column table are built here.
+template <class Rec, class Fill, class Launch>
+int undistort_batch(l3d_ctx* c, uint32_t n, const l3d_image* in, uint8_t* const* out, Fill fill, Launch launch) {
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     if (!n) return L3D_OK;
     (void)hipSetDevice(c->device);
-    std::vector<UndImage> d(n);
+    std::vector<Rec> d(n);
     std::vector<std::vector<double>> xtab(n);
     std::vector<std::array<size_t, 3>> off(n);
-    size_t bytes = align256(n * sizeof(UndImage));
+    size_t bytes = align256(n * sizeof(Rec));
     uint32_t max_pix = 0;
     for (uint32_t i = 0; i < n; ++i) {
         const l3d_image& im = in[i];
-        const l3d_distortion& D = dist[i];
-        UndImage& U = d[i];
+        Rec& U = d[i];
+        const double* Kn = fill(i, U);
         // cv::invert's closed form (DECOMP_LU, n = 3) of cvK, reduced: ir1, ir3, ir6, ir7 are +-0
-        const double fx = D.K[0], fy = D.K[4], cx = D.K[2], cy = D.K[5];
+        const double fx = Kn[0], fy = Kn[4], cx = Kn[2], cy = Kn[5];
         const double det = fx * fy, dd = 1.0 / det;
         const double ir0 = fy * dd, ir2 = (-(cx * fy)) * dd, ir8 = (fx * fy) * dd;
         U.cols = im.cols; U.rows = im.rows; U.channels = im.channels;
         U.w = 1.0 / ir8; U.ir4 = fx * dd; U.ir5 = (-(fx * cy)) * dd;
-        U.fx = fx; U.fy = fy; U.cx = cx; U.cy = cy;
-        U.k1 = D.radial[0]; U.k2 = D.radial[1]; U.k3 = D.radial[2]; U.p1 = D.tangential[0]; U.p2 = D.tangential[1];
         // OpenCV accumulates _x += ir[0] along a row; ir1 = 0, so every row starts from ir2 and one table serves all
         std::vector<double>& X = xtab[i];
         X.resize(im.cols);
@@ -328,7 +324,7 @@ int undistort(l3d_ctx* c, uint32_t n, const l3d_image* in, const l3d_distortion*
     L3D_HIP_CHECK(arena.reserve(bytes));
     char* base = arena.p;
     for (uint32_t i = 0; i < n; ++i) {
-        UndImage& U = d[i];
+        Rec& U = d[i];
         U.src = (const uint8_t*)(base + off[i][0]);
         U.dst = (uint8_t*)(base + off[i][1]);
         U.xtab = (const double*)(base + off[i][2]);
@@ -336,13 +332,93 @@ int undistort(l3d_ctx* c, uint32_t n, const l3d_image* in, const l3d_distortion*
         L3D_HIP_CHECK(hipMemcpy2DAsync((void*)U.src, row, in[i].data, in[i].row_stride, row, in[i].rows, hipMemcpyHostToDevice, c->stream));
         L3D_HIP_CHECK(hipMemcpyAsync((void*)U.xtab, xtab[i].data(), in[i].cols * sizeof(double), hipMemcpyHostToDevice, c->stream));
     }
-    L3D_HIP_CHECK(hipMemcpyAsync(base, d.data(), n * sizeof(UndImage), hipMemcpyHostToDevice, c->stream));
-    L3D_HIP_CHECK(launch_undistort((const UndImage*)base, n, max_pix, c->stream));
+    L3D_HIP_CHECK(hipMemcpyAsync(base, d.data(), n * sizeof(Rec), hipMemcpyHostToDevice, c->stream));
+    L3D_HIP_CHECK(launch((const Rec*)base, n, max_pix, c->stream));
     // after every upload in stream order: out[i] may be the memory of an input
     for (uint32_t i = 0; i < n; ++i)
         L3D_HIP_CHECK(hipMemcpyAsync(out[i], d[i].dst, (size_t)in[i].cols * in[i].rows * in[i].channels, hipMemcpyDeviceToHost, c->stream));
     L3D_HIP_CHECK(hipStreamSynchronize(c->stream));
     return L3D_OK;
+}
+
+// Line3D::undistortImage for a batch: one k_undistort launch
+int undistort(l3d_ctx* c, uint32_t n, const l3d_image* in, const l3d_distortion* dist, uint8_t* const* out) {
+    if (!c || (n && (!in || !dist || !out))) return fail(L3D_ERR_ARG, "null argument");
+    for (uint32_t i = 0; i < n; ++i) {
+        if (int rc = check_undistort(in[i], dist[i])) return rc;
+        if (!out[i]) return fail(L3D_ERR_ARG, "null argument");
+    }
+    return undistort_batch<UndImage>(c, n, in, out, [&](uint32_t i, UndImage& U) {
+        const l3d_distortion& D = dist[i];
+        U.fx = D.K[0]; U.fy = D.K[4]; U.cx = D.K[2]; U.cy = D.K[5];
+        U.k1 = D.radial[0]; U.k2 = D.radial[1]; U.k3 = D.radial[2]; U.p1 = D.tangential[0]; U.p2 = D.tangential[1];
+        return D.K;
+    }, launch_undistort);
+}
+
+// the number of distortion parameters of an l3d_camera_model's model, 0 for an unknown one
+uint32_t model_params(uint32_t model) {
+    switch (model) {
+        case L3D_CAM_FULL_OPENCV: return 8;
+        case L3D_CAM_OPENCV_FISHEYE: return 4;
+        case L3D_CAM_SIMPLE_RADIAL_FISHEYE: return 1;
+        case L3D_CAM_RADIAL_FISHEYE: return 2;
+        case L3D_CAM_FOV: return 1;
+        default: return 0;
+    }
+}
+
+bool has_new_K(const l3d_camera_model& m) {
+    for (double v : m.K_new)
+        if (!(v == 0)) return true;          // (a NaN counts as given, and is refused below)
+    return false;
+}
+
+// the checks of §12 for the model entry, before any pixel is read or any memory is allocated
+int check_undistort_model(const l3d_image& im, const l3d_camera_model& m) {
+    if (int rc = check_image(im)) return rc;
+    const uint32_t np = model_params(m.model);
+    if (!np) return fail(L3D_ERR_ARG, "undistortImage: unknown camera model " + std::to_string(m.model));
+    const bool kn = has_new_K(m);
+    double used[16] = {m.K[0], m.K[4], m.K[2], m.K[5], 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (uint32_t k = 0; k < np; ++k) used[4 + k] = m.params[k];
+    if (kn) { used[12] = m.K_new[0]; used[13] = m.K_new[4]; used[14] = m.K_new[2]; used[15] = m.K_new[5]; }
+    for (double v : used)
+        if (!std::isfinite(v)) return fail(L3D_ERR_ARG, "undistortImage: non-finite distortion coefficient or camera matrix entry");
+    if (m.K[0] * m.K[4] == 0 || (kn && m.K_new[0] * m.K_new[4] == 0))
+        return fail(L3D_ERR_ARG, "undistortImage: fx * fy == 0, the camera matrix is singular");
+    if (im.cols >= 32767 || im.rows >= 32767)
+        return fail(L3D_ERR_LIMIT, "undistortImage: image side of SHRT_MAX or more (cv::remap refuses it)");
+    return L3D_OK;
+}
+
+// undistortion by camera model for a batch: one k_undistort_model launch
+int undistort_model(l3d_ctx* c, uint32_t n, const l3d_image* in, const l3d_camera_model* cams, uint8_t* const* out) {
+    if (!c || (n && (!in || !cams || !out))) return fail(L3D_ERR_ARG, "null argument");
+    for (uint32_t i = 0; i < n; ++i) {
+        if (int rc = check_undistort_model(in[i], cams[i])) return rc;
+        if (!out[i]) return fail(L3D_ERR_ARG, "null argument");
+    }
+    return undistort_batch<UndModelImage>(c, n, in, out, [&](uint32_t i, UndModelImage& U) {
+        const l3d_camera_model& m = cams[i];
+        const double* p = m.params;
+        U.fx = m.K[0]; U.fy = m.K[4]; U.cx = m.K[2]; U.cy = m.K[5];
+        U.model = m.model;
+        U.k1 = U.k2 = U.k3 = U.p1 = U.p2 = 0;
+        U.q[0] = U.q[1] = U.q[2] = U.q[3] = 0;
+        switch (m.model) {
+            case L3D_CAM_FULL_OPENCV:
+                U.k1 = p[0]; U.k2 = p[1]; U.p1 = p[2]; U.p2 = p[3]; U.k3 = p[4];
+                U.q[0] = p[5]; U.q[1] = p[6]; U.q[2] = p[7];
+                break;
+            case L3D_CAM_FOV:                // tan(omega / 2) once per image, on the host
+                U.q[0] = p[0]; U.q[1] = p[0] * p[0]; U.q[2] = std::tan(p[0] / 2);
+                break;
+            default:                         // the fisheye family: the missing coefficients stay 0
+                for (uint32_t k = 0; k < model_params(m.model); ++k) U.q[k] = p[k];
+        }
+        return has_new_K(m) ? m.K_new : m.K;
+    }, launch_undistort_model);
 }
 
 }  // namespace
@@ -394,6 +470,11 @@ int l3d_add_view_image_worldpoints(l3d_ctx* c, uint32_t camID, const l3d_image* 
 int l3d_undistort_images(l3d_ctx* c, uint32_t n_images, const l3d_image* in, const l3d_distortion* dist,
                          uint8_t* const* out) {
     return undistort(c, n_images, in, dist, out);
+}
+
+int l3d_undistort_images_model(l3d_ctx* c, uint32_t n_images, const l3d_image* in, const l3d_camera_model* cams,
+                               uint8_t* const* out) {
+    return undistort_model(c, n_images, in, cams, out);
 }
 
 }  // extern "C"

@@ -18,7 +18,8 @@ wall-clock seconds per stage.  Pix4D gives no 3D points: its program triangulate
 
 What differs from the reference:
 - images go through the library in chunks: a chunk is read on the host, the images that need it are undistorted in ONE
-  `undistort_images` call and the chunk is added with ONE `Line3D.addImages` call, so that line-segment detection runs as
+  `undistort_images` call (those of a COLMAP camera model beyond five coefficients in ONE `undistort_images_model`
+  call) and the chunk is added with ONE `Line3D.addImages` call, so that line-segment detection runs as
   one batch per chunk (the reference does all three image by image, one image per OpenMP thread).  A chunk is bounded by
   CHUNK_BYTES of decoded pixels; the result does not depend on the chunking;
 - `-g / --use_cuda` is accepted and ignored: the library has no CPU path;
@@ -203,11 +204,27 @@ def undistort_images(images, Ks, radials, tangentials):
     return out
 
 
+def undistort_images_model(images, models, Ks, params):
+    """the default `undistort_model`: lsd.undistort_images_model, one batch; empty images as undistort_images treats them"""
+    from . import lsd
+    out = list(images)
+    real = [i for i, im in enumerate(images) if im.size]
+    if len(real) < len(out):
+        print(f"{PREFIX}ERROR: undistortImage: {len(out) - len(real)} empty image(s)")
+    if real:
+        done = lsd.undistort_images_model([images[i] for i in real], [models[i] for i in real], [Ks[i] for i in real],
+                                          [params[i] for i in real])
+        for i, im in zip(real, done):
+            out[i] = im
+    return out
+
+
 def _chunk_bytes():
     return int(os.environ.get(CHUNK_ENV, CHUNK_BYTES))
 
 
-def run_views(kind, views, s, line3d_factory=None, read_image=None, undistort=None, neighbors_by_worldpoints=True):
+def run_views(kind, views, s, line3d_factory=None, read_image=None, undistort=None, neighbors_by_worldpoints=True,
+              undistort_model=None):
     """The shared core.  `views`: what a main's image loop visits, in its order, as (camera id, image path, entry of the
     io reader); `s`: _settings; `neighbors_by_worldpoints`: what the main constructs Line3D with (main_mavmap.cpp:150-151
     hands over neighbour lists, the others worldpoint lists).  -> (Line3D object, seconds per stage)"""
@@ -223,6 +240,8 @@ def run_views(kind, views, s, line3d_factory=None, read_image=None, undistort=No
                 return None
     if undistort is None:
         undistort = undistort_images
+    if undistort_model is None:
+        undistort_model = undistort_images_model
     times = dict.fromkeys(STAGES, 0.0)
 
     def timed(stage, fn, *args):
@@ -243,6 +262,11 @@ def run_views(kind, views, s, line3d_factory=None, read_image=None, undistort=No
             done = timed("undistort", undistort, [v["image"] for v in todo], *zip(*[v["undistortion"] for v in todo]))
             for v, im in zip(todo, done):
                 v["image"] = im
+        todo = [v for v in chunk if v["camera_model"] is not None]      # COLMAP's models beyond five coefficients
+        if todo:
+            done = timed("undistort", undistort_model, [v["image"] for v in todo], *zip(*[v["camera_model"] for v in todo]))
+            for v, im in zip(todo, done):
+                v["image"] = im
         add = [v for v in chunk if v["add"]]
         if add:
             timed("add", line3d.addImages, [v["id"] for v in add], [v["image"] for v in add], [v["K"] for v in add],
@@ -256,12 +280,13 @@ def run_views(kind, views, s, line3d_factory=None, read_image=None, undistort=No
             print(f"{PREFIX}WARNING: image '{path}' could not be read!")
             image = np.zeros((0, 0), np.uint8)                 # cv::imread's empty Mat: 0 x 0 from here on, as there
         rows, cols = image.shape[:2]
-        und = io.front_end_undistortion(kind, entry, cols, rows)
+        model = io.front_end_camera_model(kind, entry, cols, rows)
+        und = io.front_end_undistortion(kind, entry, cols, rows) if model is None else None
         K = entry["K"] if "K" in entry else io.nvm_intrinsics(entry["focal"], cols, rows)   # .nvm, bundler: from the image size
         if chunk and held + image.nbytes > budget:
             flush()
             held = 0
-        chunk.append(dict(id=cam_id, image=image, entry=entry, K=K, undistortion=und,
+        chunk.append(dict(id=cam_id, image=image, entry=entry, K=K, undistortion=und, camera_model=model,
                           add=kind == "mavmap" or bool(entry["worldpoints"])))
         held += image.nbytes
     flush()
@@ -319,11 +344,16 @@ def run_colmap(argv, **pieces):
     if not os.path.exists(sfm):
         raise FrontEndError(f'colmap result folder "{sfm}" does not exist!')
     s = _settings(a, a["output_folder"] or sfm + "/Line3D++/")
-    if not all(os.path.exists(sfm + "/" + n) for n in ("cameras.txt", "images.txt", "points3D.txt")):
+    # COLMAP's binary model (its default output) is read where there is no cameras.txt and all three .bin files exist
+    binary = not os.path.exists(sfm + "/cameras.txt") and all(
+        os.path.exists(sfm + "/" + n) for n in ("cameras.bin", "images.bin", "points3D.bin"))
+    if not binary and not all(os.path.exists(sfm + "/" + n) for n in ("cameras.txt", "images.txt", "points3D.txt")):
         raise FrontEndError(f'at least one of the colmap result files does not exist in sfm folder: "{sfm}"', 2)
     try:
         images = io.read_colmap(sfm)
     except ValueError as e:                                                                           # :221-226
+        if not str(e).endswith("unknown!"):                    # a binary file that is truncated or over-long
+            raise FrontEndError(str(e), 2) from None
         raise FrontEndError(f"{e}\nplease specify its parameters in io.py (_COLMAP_MODELS) in order to proceed...", 3) from None
     # :353-410: every image of a known camera is read, and undistorted if its camera has distortion; only one with
     # worldpoints is added

@@ -324,7 +324,20 @@ _COLMAP_MODELS = {  # parameter order of cameras.txt -> (fx, fy, cx, cy, k1, k2,
     "RADIAL": lambda p: (p[0], p[0], p[1], p[2], p[3], p[4], 0, 0, 0),
     "OPENCV": lambda p: (p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], 0),
     "FULL_OPENCV": lambda p: (p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8]),
+    # beyond the reference: undistorted by camera model, the five coefficients are zero
+    "OPENCV_FISHEYE": lambda p: (p[0], p[1], p[2], p[3], 0, 0, 0, 0, 0),
+    "FOV": lambda p: (p[0], p[1], p[2], p[3], 0, 0, 0, 0, 0),
+    "SIMPLE_RADIAL_FISHEYE": lambda p: (p[0], p[0], p[1], p[2], 0, 0, 0, 0, 0),
+    "RADIAL_FISHEYE": lambda p: (p[0], p[0], p[1], p[2], 0, 0, 0, 0, 0),
 }
+# COLMAP's binary model ids, in order, with the length of each model's parameter list
+COLMAP_MODEL_IDS = (("SIMPLE_PINHOLE", 3), ("PINHOLE", 4), ("SIMPLE_RADIAL", 4), ("RADIAL", 5), ("OPENCV", 8),
+                    ("OPENCV_FISHEYE", 8), ("FULL_OPENCV", 12), ("FOV", 5), ("SIMPLE_RADIAL_FISHEYE", 4),
+                    ("RADIAL_FISHEYE", 5), ("THIN_PRISM_FISHEYE", 12))
+_COLMAP_N_PARAMS = dict(COLMAP_MODEL_IDS)
+# (index of the first distortion parameter in the list, their number) of the models l3d_undistort_images_model takes
+_COLMAP_DISTORTION = {"FULL_OPENCV": (4, 8), "OPENCV_FISHEYE": (4, 4), "SIMPLE_RADIAL_FISHEYE": (3, 1),
+                      "RADIAL_FISHEYE": (3, 2), "FOV": (4, 1)}
 
 
 def _median_depth(C, pts):
@@ -332,11 +345,19 @@ def _median_depth(C, pts):
     return d[len(d) // 2] if d else None
 
 
-def read_colmap(folder):
-    """cameras.txt / images.txt / points3D.txt as main_colmap.cpp:136-348 reads them -> list of images in file order:
-    dict(id, camera, name, width, height, K, R, t, C, radial (k1, k2, k3), tangential (p1, p2), worldpoints,
-    median_depth or None).  An image whose camera is unknown is dropped; points3D.txt lines that do not parse as
-    "id X Y Z" are ignored; a worldpoint without an entry there sits at the origin (the reference's map default)."""
+def _colmap_camera(model, p, width, height):
+    """the camera record of both parsers: p = the parameter list (padded with zeros behind its end)"""
+    p = [float(x) for x in p]
+    fx, fy, cx, cy, k1, k2, p1, p2, k3 = (float(x) for x in _COLMAP_MODELS[model](p + [0.0] * 12))
+    n = _COLMAP_N_PARAMS[model]
+    return dict(width=width, height=height, K=np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1.0]]),
+                radial=np.array([k1, k2, k3]), tangential=np.array([p1, p2]), model=model, params=(p + [0.0] * n)[:n])
+
+
+def _colmap_text(folder):
+    """cameras.txt / images.txt / points3D.txt -> (cams, image records, points): an image record is (head, ids) with head =
+    dict(id, camera, name, R, t, C) or None (an image line of an unknown camera, or one that does not parse) and ids =
+    the POINT3D_IDs of its line of 2D points"""
     import os
     def getlines(path):      # std::getline's view of a file: no extra empty line behind a final newline
         text = open(path).read()
@@ -351,44 +372,149 @@ def read_colmap(folder):
         model = tok[1] if len(tok) > 1 else ""
         if model not in _COLMAP_MODELS:
             raise ValueError(f"camera model {model} unknown!")
-        fx, fy, cx, cy, k1, k2, p1, p2, k3 = (float(x) for x in _COLMAP_MODELS[tok[1]]([float(x) for x in tok[4:]] + [0.0] * 9))
-        cams[int(tok[0])] = dict(width=int(tok[2]), height=int(tok[3]), K=np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1.0]]),
-                                 radial=np.array([k1, k2, k3]), tangential=np.array([p1, p2]))
-    imgs, by_id, wps = [], {}, {}
-    first, cur = True, None
+        cams[int(tok[0])] = _colmap_camera(model, [float(x) for x in tok[4:]], int(tok[2]), int(tok[3]))
+    records = []
+    first = True
     for line in open(os.path.join(folder, "images.txt")).read().split("\n"):
         if line[:1] == "#":
             continue
         tok = line.split()
         if first:
-            cur = None
+            head = None
             if len(tok) >= 9 and int(tok[8]) in cams:
-                cam = cams[int(tok[8])]
                 R = rotation_from_q(*(float(x) for x in tok[1:5]))
                 t = np.array([float(x) for x in tok[5:8]])
-                cur = dict(id=int(tok[0]), camera=int(tok[8]), name=tok[9] if len(tok) > 9 else "", R=R, t=t, C=R.T @ (-1.0 * t),
-                           worldpoints=[], **cam)
-                by_id[cur["id"]] = cur
-                imgs.append(cur)
+                head = dict(id=int(tok[0]), camera=int(tok[8]), name=tok[9] if len(tok) > 9 else "", R=R, t=t, C=R.T @ (-1.0 * t))
+            records.append([head, None])
             first = False
         else:
-            if cur is not None:
-                lst = []
-                for k in range(2, len(tok), 3):
-                    wp = int(tok[k])
-                    if wp >= 0:
-                        lst.append(wp); wps[wp] = np.zeros(3)
-                cur["worldpoints"] = lst
+            if records[-1][0] is not None:
+                records[-1][1] = [int(tok[k]) for k in range(2, len(tok), 3)]
             first = True
-    # a repeated IMAGE_ID: the reference's maps are keyed by the id, so BOTH entries of the image sequence see the last pose
-    # and the last worldpoint list (l3d_sfm_open_colmap does the same fix-up)
-    imgs = [im if by_id[im["id"]] is im else dict(by_id[im["id"]]) for im in imgs]
+    points = []
     for line in open(os.path.join(folder, "points3D.txt")).read().split("\n"):
         tok = line.split()
         try:
-            pid, X, Y, Z = int(tok[0]), float(tok[1]), float(tok[2]), float(tok[3])
+            points.append((int(tok[0]), float(tok[1]), float(tok[2]), float(tok[3])))
         except (ValueError, IndexError):
             continue
+    return cams, records, points
+
+
+class _Cursor:
+    """a COLMAP binary file in memory, read little-endian with a cursor that never passes its end"""
+
+    def __init__(self, folder, name):
+        import os
+        self.name = name
+        with open(os.path.join(folder, name), "rb") as f:
+            self.buf = f.read()
+        self.pos = 0
+
+    def left(self):
+        return len(self.buf) - self.pos
+
+    def get(self, fmt):
+        import struct
+        n = struct.calcsize("<" + fmt)
+        if self.left() < n:
+            raise ValueError(f"{self.name}: the file ends inside a record (truncated?)")
+        v = struct.unpack_from("<" + fmt, self.buf, self.pos)
+        self.pos += n
+        return v
+
+    def count(self, what, least):
+        """a u64 count of records of at least `least` bytes each, checked against what is left before anything is made"""
+        n, = self.get("Q")
+        if n > self.left() // least:
+            raise ValueError(f"{self.name}: {n} {what} cannot fit in the {self.left()} bytes that follow")
+        return n
+
+    def finish(self):
+        if self.left():
+            raise ValueError(f"{self.name}: {self.left()} bytes behind the last record")
+
+
+def _atoi(n):
+    """POINT3D_ID of images.bin as l3d_sfm_open_colmap's atoi sees the same number in decimal: strtol saturates at
+    LONG_MAX and the int keeps its low 32 bits, so 2^64 - 1 ("no point") is -1"""
+    n = min(n, 2 ** 63 - 1) & 0xFFFFFFFF
+    return n - 2 ** 32 if n >= 2 ** 31 else n
+
+
+def _colmap_binary(folder):
+    """cameras.bin / images.bin / points3D.bin (COLMAP's binary model) -> the records of _colmap_text"""
+    f = _Cursor(folder, "cameras.bin")
+    cams = {}
+    for _ in range(f.count("cameras", 48)):
+        cid, model_id, width, height = f.get("IiQQ")
+        known = 0 <= model_id < len(COLMAP_MODEL_IDS) and COLMAP_MODEL_IDS[model_id][0] in _COLMAP_MODELS
+        if not known:
+            raise ValueError(f"camera model {COLMAP_MODEL_IDS[model_id][0] if 0 <= model_id < len(COLMAP_MODEL_IDS) else model_id} unknown!")
+        if width >= 2 ** 32 or height >= 2 ** 32:
+            raise ValueError(f"{f.name}: image size of camera {cid} beyond 32 bits")
+        model, n = COLMAP_MODEL_IDS[model_id]
+        cams[cid] = _colmap_camera(model, list(f.get(f"{n}d")), width, height)
+    f.finish()
+    f = _Cursor(folder, "images.bin")
+    records = []
+    for _ in range(f.count("images", 73)):
+        iid, qw, qx, qy, qz, tx, ty, tz, cid = f.get("I7dI")
+        end = f.buf.find(b"\0", f.pos)
+        if end < 0:
+            raise ValueError(f"{f.name}: the file ends inside a record (truncated?)")
+        name = f.buf[f.pos:end].decode("utf-8", "surrogateescape")
+        f.pos = end + 1
+        m = f.count("2D points", 24)
+        ids = [_atoi(f.get("2dQ")[2]) for _ in range(m)]
+        head = None
+        if cid in cams:
+            R = rotation_from_q(qw, qx, qy, qz)
+            t = np.array([tx, ty, tz])
+            head = dict(id=iid, camera=cid, name=name, R=R, t=t, C=R.T @ (-1.0 * t))
+        records.append([head, ids])
+    f.finish()
+    f = _Cursor(folder, "points3D.bin")
+    points = []
+    for _ in range(f.count("3D points", 51)):
+        pid, X, Y, Z, _r, _g, _b, _err = f.get("Q3d3Bd")
+        track = f.count("track elements", 8)
+        f.pos += 8 * track
+        if pid < 2 ** 32:                    # (the text reader of the C-ABI takes the id as a uint32_t)
+            points.append((pid, X, Y, Z))
+    f.finish()
+    return cams, records, points
+
+
+def read_colmap(folder):
+    """cameras.txt / images.txt / points3D.txt as main_colmap.cpp:136-348 reads them or, where there is no cameras.txt and
+    cameras.bin, images.bin and points3D.bin all exist, COLMAP's binary form of the same -> list of images
+    in file order: dict(id, camera, name, width, height, K, R, t, C, radial (k1, k2, k3), tangential (p1, p2), model
+    (COLMAP's name), params (the model's parameter list), worldpoints, median_depth or None).  An image whose camera is
+    unknown is dropped; points3D.txt lines that do not parse as "id X Y Z" are ignored; a worldpoint without an entry
+    there sits at the origin (the reference's map default).  A binary file that is truncated, over-long or states a
+    count that cannot fit: ValueError with its name."""
+    import os
+    binary = not os.path.exists(os.path.join(folder, "cameras.txt")) and all(
+        os.path.exists(os.path.join(folder, n)) for n in ("cameras.bin", "images.bin", "points3D.bin"))
+    cams, records, points = (_colmap_binary if binary else _colmap_text)(folder)
+    imgs, by_id, wps = [], {}, {}
+    for head, ids in records:
+        if head is None:
+            continue
+        cur = dict(head, worldpoints=[], **cams[head["camera"]])
+        by_id[cur["id"]] = cur
+        imgs.append(cur)
+        if ids is not None:
+            lst = []
+            for wp in ids:
+                if wp >= 0:
+                    lst.append(wp); wps[wp] = np.zeros(3)
+            cur["worldpoints"] = lst
+    # a repeated IMAGE_ID: the reference's maps are keyed by the id, so BOTH entries of the image sequence see the last pose
+    # and the last worldpoint list (l3d_sfm_open_colmap does the same fix-up)
+    imgs = [im if by_id[im["id"]] is im else dict(by_id[im["id"]]) for im in imgs]
+    for pid, X, Y, Z in points:
         if pid in wps:
             wps[pid] = np.array([X, Y, Z])
     for im in imgs:
@@ -729,3 +855,21 @@ def front_end_undistortion(kind, entry, cols, rows):
     if kind == "mavmap":         # main_mavmap.cpp:293-326: never
         return None
     raise ValueError(f"unknown front end {kind!r}: nvm, bundler, colmap, openmvg, pix4d or mavmap")
+
+
+def front_end_camera_model(kind, entry, cols, rows):
+    """(model, K, params) for lsd.undistort_images_model when the image of `entry` has to be undistorted by its camera
+    model, else None (front_end_undistortion then says what happens to it).  Only "colmap" has such
+    cameras: the fisheye family always (with zero coefficients the image is still equidistant, not pinhole), FOV when
+    |omega| exceeds L3D_EPS, FULL_OPENCV when k4, k5 or k6 exceeds L3D_EPS in magnitude (with zeros it is the reference's
+    five coefficients).  params: the model's distortion parameters in COLMAP's order."""
+    if kind != "colmap" or entry.get("model") not in _COLMAP_DISTORTION:
+        return None
+    model = entry["model"]
+    first, n = _COLMAP_DISTORTION[model]
+    params = [float(v) for v in entry["params"][first:first + n]]
+    if model == "FOV" and not abs(params[0]) > L3D_EPS:
+        return None
+    if model == "FULL_OPENCV" and not any(abs(v) > L3D_EPS for v in params[5:8]):
+        return None
+    return model, np.array(entry["K"], np.float64), params

@@ -4,7 +4,8 @@
 LSD_REFINE_ADV), the length filter, the length order and the cap.  `Line3D.addImage` / `addImages` (api.py) run the
 same stage, with the segment cache, when they are given an image and no segments.  Detection expects undistorted
 images: `undistort_images` is Line3D::undistortImage (line3D.cc:83-109) on the GPU (k_undistort.hip), batched over images,
-which the reference's front ends call before addImage.
+which the reference's front ends call before addImage.  `undistort_images_model` is the same for COLMAP's
+camera models beyond those five coefficients: FULL_OPENCV, the fisheye family and FOV.
 """
 import ctypes as C
 
@@ -111,6 +112,52 @@ def undistort_images(images, Ks, radials, tangentials, device=0):
         rc = L.l3d_undistort_images(h, n, arr, dist, ptrs)
         if rc != 0:
             raise RuntimeError(f"l3d_undistort_images failed [{rc}]: {_lib.last_error()}")
+        return outs
+    finally:
+        L.l3d_destroy(h)
+
+
+def camera_model(model, K, params, K_new=None):
+    """l3d_camera_model: model = COLMAP's name, K 3x3 of the input image, params = the model's distortion parameters in
+    COLMAP's order (missing ones 0), K_new 3x3 of the output image (None: K)"""
+    if model not in _lib.CAMERA_MODELS:
+        raise ValueError(f"camera model {model} unknown!")
+    p = [float(v) for v in np.asarray(params, np.float64).reshape(-1)]
+    if len(p) > _lib.CAMERA_MODEL_PARAMS[model]:
+        raise ValueError(f"camera model {model} takes {_lib.CAMERA_MODEL_PARAMS[model]} distortion parameter(s), not {len(p)}")
+    m = _lib.CameraModel()
+    m.model = _lib.CAMERA_MODELS[model]
+    m.K[:] = [float(v) for v in np.asarray(K, np.float64).reshape(9)]
+    m.params[:] = p + [0.0] * (8 - len(p))
+    if K_new is not None:
+        m.K_new[:] = [float(v) for v in np.asarray(K_new, np.float64).reshape(9)]
+    return m
+
+
+def undistort_images_model(images, models, Ks, params, K_new=None, device=0):
+    """Undistortion by camera model for a list of images in one batch on the GPU (k_undistort_model) -> list
+    of uint8 ndarrays of the inputs' shapes.  Per image: COLMAP's model name (FULL_OPENCV, OPENCV_FISHEYE,
+    SIMPLE_RADIAL_FISHEYE, RADIAL_FISHEYE, FOV), K 3x3, the model's distortion parameters in COLMAP's order
+    (io.front_end_camera_model); K_new: None, or per image the camera matrix of the output image (None: K)."""
+    L = _lib.load()
+    images = list(images)
+    n = len(images)
+    K_new = [None] * n if K_new is None else list(K_new)
+    if not len(models) == len(Ks) == len(params) == len(K_new) == n:
+        raise ValueError("one model, K and parameter list per image")
+    views = [as_image(im) for im in images]
+    arr = (_lib.Image * max(n, 1))(*[v[0] for v in views])
+    cams = (_lib.CameraModel * max(n, 1))(*[camera_model(*a) for a in zip(models, Ks, params, K_new)])
+    outs = [np.empty(v[1].shape, np.uint8) for v in views]
+    ptrs = (C.c_void_p * max(n, 1))(*[o.ctypes.data for o in outs])
+    h = L.l3d_create(int(device), None)
+    if not h:
+        raise RuntimeError("l3d_create failed: " + _lib.last_error())
+    h = C.c_void_p(h)
+    try:
+        rc = L.l3d_undistort_images_model(h, n, arr, cams, ptrs)
+        if rc != 0:
+            raise RuntimeError(f"l3d_undistort_images_model failed [{rc}]: {_lib.last_error()}")
         return outs
     finally:
         L.l3d_destroy(h)
