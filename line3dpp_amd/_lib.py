@@ -36,6 +36,12 @@ class MatchParams(C.Structure):
                 ("epipolar_overlap", C.c_float), ("kNN", C.c_int32), ("const_regularization_depth", C.c_float)]
 
 
+class NvmCamera(C.Structure):
+    """l3d_nvm_camera (include/l3dpp_hip.h)"""
+    _fields_ = [("filename", C.c_char_p), ("focal", C.c_float), ("distortion", C.c_float), ("median_depth", C.c_float),
+                ("n_worldpoints", C.c_uint32), ("R", C.c_double * 9), ("t", C.c_double * 3), ("C", C.c_double * 3)]
+
+
 class SfmImage(C.Structure):
     """l3d_sfm_image (include/l3dpp_hip.h)"""
     _fields_ = [("id", C.c_uint32), ("camera", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32),

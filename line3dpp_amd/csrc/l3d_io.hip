@@ -1,5 +1,5 @@
-// l3d_io.hip -- the input side of the matching path behind the C-ABI (host code; the Python twin is
-// line3dpp_amd/io.py, and tests/test_input_formats.py holds the two against each other):
+// l3d_io.hip -- the input side of the matching path behind the C-ABI (host code; line3dpp_amd/io.py reads through it,
+// and tests/test_input_formats.py holds it against the Python model of the formats, tests/sfm_readers_model.py):
 //   * VisualSfM .nvm as main_vsfm.cpp:144-250 reads it (two ignored lines, the number of cameras, one line per camera:
 //     file name, focal length, quaternion w x y z, centre, radial distortion; an ignored line, the number of points, one
 //     line per point: position, colour, number of measurements, then camera index, feature index, x, y each) with what

@@ -354,7 +354,7 @@ def run_colmap(argv, **pieces):
     except ValueError as e:                                                                           # :221-226
         if not str(e).endswith("unknown!"):                    # a binary file that is truncated or over-long
             raise FrontEndError(str(e), 2) from None
-        raise FrontEndError(f"{e}\nplease specify its parameters in io.py (_COLMAP_MODELS) in order to proceed...", 3) from None
+        raise FrontEndError(f"{e}\nplease specify its parameters in l3d_io.hip (kColmapModels) in order to proceed...", 3) from None
     # :353-410: every image of a known camera is read, and undistorted if its camera has distortion; only one with
     # worldpoints is added
     return run_views("colmap", [(im["id"], folder + "/" + im["name"], im) for im in images], s, **pieces)

@@ -1,6 +1,7 @@
 """COLMAP's binary model (cameras.bin, images.bin, points3D.bin) and its camera models beyond the reference's six, through
-io.read_colmap and l3d_sfm_open_colmap.  The files are written here from the documented layout: no file
-written by COLMAP itself is at hand.  No GPU."""
+l3d_sfm_open_colmap, io.read_colmap that wraps it, and the Python model of the format, tests/sfm_readers_model.py (M
+below).  What is pinned on hand-computed values is pinned for the wrapper and for the model.  The files are
+written here from the documented layout: no file written by COLMAP itself is at hand.  No GPU."""
 import ctypes as C
 import os
 import struct
@@ -10,7 +11,9 @@ import pytest
 
 from line3dpp_amd import _lib as L
 from line3dpp_amd import io
+from tests import sfm_readers_model as M
 
+READERS = (io, M)          # the package's wrapper of the library, and the model
 NO_POINT = 2 ** 64 - 1
 MODEL_IDS = {name: k for k, (name, _) in enumerate(io.COLMAP_MODEL_IDS)}
 
@@ -151,28 +154,12 @@ def test_binary_and_text_read_identically(tmp_path):
     cams, images, points = scene(np.random.default_rng(8))
     write_text(tmp_path / "txt", cams, images, points)
     write_binary(tmp_path / "bin", binary_files(cams, images, points))
-    txt, bin_ = io.read_colmap(str(tmp_path / "txt")), io.read_colmap(str(tmp_path / "bin"))
-    _same_python(txt, bin_)
-    # what was read: file order, the image of camera 77 dropped, both entries of the repeated id 20 with the last pose
-    assert [g["id"] for g in bin_] == [10, 15, 20, 25, 30, 35, 40, 45, 50, 55, 20, 70]
-    assert bin_[2]["camera"] == bin_[10]["camera"] == 3 and bin_[2]["R"].tobytes() == bin_[10]["R"].tobytes()
-    assert bin_[2]["worldpoints"] == bin_[10]["worldpoints"] == [p for _, _, p in images[11][5] if p != NO_POINT]
-    by_cam = {g["camera"]: g for g in bin_}
-    for cid, model, w, h, params in cams:
-        g = by_cam[cid]
-        assert g["model"] == model and g["params"] == params and (g["width"], g["height"]) == (w, h)
-    for g, idx in zip(bin_, [0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 11, 12]):
-        want = [p for _, _, p in images[idx][5] if p != NO_POINT] if g["id"] != 20 else bin_[10]["worldpoints"]
-        assert g["worldpoints"] == want and 99999 in want or not want
-        assert (g["median_depth"] is None) == (not want)
-    assert bin_[4]["worldpoints"] == [] and bin_[7]["worldpoints"] == []
-    # the new models: K from the focal lengths and the principal point, the five coefficients zero
-    f, cx, cy = 1250.125, 960.5, 540.25
-    for cid, fy in ((6, f * 1.01), (8, f * 1.01), (9, f), (12, f)):
-        g = by_cam[cid]
-        assert np.array_equal(g["K"], [[f, 0, cx], [0, fy, cy], [0, 0, 1]]) and not g["radial"].any() and not g["tangential"].any()
-    assert np.array_equal(by_cam[7]["radial"], [-0.1, 0.02, 3e-3]) and by_cam[7]["params"][9:] == [0.01, -0.002, 0.0005]
-    # the C-ABI: text and binary identical, and equal to the Python twin
+    for reader in READERS:
+        txt, bin_ = reader.read_colmap(str(tmp_path / "txt")), reader.read_colmap(str(tmp_path / "bin"))
+        _same_python(txt, bin_)
+        _read_as_written(bin_, cams, images)
+    # the C-ABI: text and binary identical, and equal to the model
+    bin_ = M.read_colmap(str(tmp_path / "bin"))
     rc, _, ctxt = c_read(tmp_path / "txt")
     rc2, _, cbin = c_read(tmp_path / "bin")
     assert rc == 0 and rc2 == 0
@@ -197,6 +184,28 @@ def test_binary_and_text_read_identically(tmp_path):
             assert number == 0 and not any(params)
 
 
+def _read_as_written(bin_, cams, images):
+    # what was read: file order, the image of camera 77 dropped, both entries of the repeated id 20 with the last pose
+    assert [g["id"] for g in bin_] == [10, 15, 20, 25, 30, 35, 40, 45, 50, 55, 20, 70]
+    assert bin_[2]["camera"] == bin_[10]["camera"] == 3 and bin_[2]["R"].tobytes() == bin_[10]["R"].tobytes()
+    assert bin_[2]["worldpoints"] == bin_[10]["worldpoints"] == [p for _, _, p in images[11][5] if p != NO_POINT]
+    by_cam = {g["camera"]: g for g in bin_}
+    for cid, model, w, h, params in cams:
+        g = by_cam[cid]
+        assert g["model"] == model and g["params"] == params and (g["width"], g["height"]) == (w, h)
+    for g, idx in zip(bin_, [0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 11, 12]):
+        want = [p for _, _, p in images[idx][5] if p != NO_POINT] if g["id"] != 20 else bin_[10]["worldpoints"]
+        assert g["worldpoints"] == want and 99999 in want or not want
+        assert (g["median_depth"] is None) == (not want)
+    assert bin_[4]["worldpoints"] == [] and bin_[7]["worldpoints"] == []
+    # the new models: K from the focal lengths and the principal point, the five coefficients zero
+    f, cx, cy = 1250.125, 960.5, 540.25
+    for cid, fy in ((6, f * 1.01), (8, f * 1.01), (9, f), (12, f)):
+        g = by_cam[cid]
+        assert np.array_equal(g["K"], [[f, 0, cx], [0, fy, cy], [0, 0, 1]]) and not g["radial"].any() and not g["tangential"].any()
+    assert np.array_equal(by_cam[7]["radial"], [-0.1, 0.02, 3e-3]) and by_cam[7]["params"][9:] == [0.01, -0.002, 0.0005]
+
+
 def test_a_folder_with_text_and_binary_takes_the_text(tmp_path):
     rng = np.random.default_rng(9)
     cams, images, points = scene(rng)
@@ -204,13 +213,17 @@ def test_a_folder_with_text_and_binary_takes_the_text(tmp_path):
     other = scene(rng)
     write_binary(tmp_path / "both", binary_files(*other))
     write_text(tmp_path / "txt", cams, images, points)
-    _same_python(io.read_colmap(str(tmp_path / "both")), io.read_colmap(str(tmp_path / "txt")))
+    for reader in READERS:
+        _same_python(reader.read_colmap(str(tmp_path / "both")), reader.read_colmap(str(tmp_path / "txt")))
     _same_c(c_read(tmp_path / "both")[2], c_read(tmp_path / "txt")[2])
-    # one .bin file missing and no cameras.txt: today's error for the missing text file
+    # one .bin file missing and no cameras.txt: the text files are looked for.  The model fails on opening the first,
+    # the library (and so the wrapper) with the reference's message
     files = binary_files(cams, images, points)
     del files["points3D.bin"]
     write_binary(tmp_path / "two", files)
     with pytest.raises(OSError, match="cameras.txt"):
+        M.read_colmap(str(tmp_path / "two"))
+    with pytest.raises(ValueError, match="does not exist"):
         io.read_colmap(str(tmp_path / "two"))
     rc, msg, _ = c_read(tmp_path / "two")
     assert rc == -1 and "does not exist" in msg
@@ -222,8 +235,9 @@ def test_unknown_binary_model_ids(tmp_path, model):
     cams[3] = (4, model, 640, 480, [1.0] * 12)
     write_binary(tmp_path / "bad", binary_files(cams, images, points))
     name = "THIN_PRISM_FISHEYE" if model == 10 else str(model)
-    with pytest.raises(ValueError, match=f"camera model {name} unknown!"):
-        io.read_colmap(str(tmp_path / "bad"))
+    for reader in READERS:
+        with pytest.raises(ValueError, match=f"camera model {name} unknown!"):
+            reader.read_colmap(str(tmp_path / "bad"))
     rc, msg, _ = c_read(tmp_path / "bad")
     assert rc == -1 and msg == f"camera model {name} unknown!"
 
@@ -233,15 +247,17 @@ def test_unknown_text_models_keep_their_message(tmp_path):
     for name in ("THIN_PRISM_FISHEYE", "FISHEYE"):
         cams[3] = (4, name, 640, 480, [1.0] * 12)
         write_text(tmp_path / name, cams, images, points)
-        with pytest.raises(ValueError, match=f"camera model {name} unknown!"):
-            io.read_colmap(str(tmp_path / name))
+        for reader in READERS:
+            with pytest.raises(ValueError, match=f"camera model {name} unknown!"):
+                reader.read_colmap(str(tmp_path / name))
         rc, msg, _ = c_read(tmp_path / name)
         assert rc == -1 and msg == f"camera model {name} unknown!"
 
 
 def _refused(folder, file_name):
-    with pytest.raises(ValueError, match=file_name.replace(".", r"\.")):
-        io.read_colmap(str(folder))
+    for reader in READERS:
+        with pytest.raises(ValueError, match=file_name.replace(".", r"\.")):
+            reader.read_colmap(str(folder))
     rc, msg, _ = c_read(folder)
     assert rc == L.L3D_ERR_IO and file_name in msg, (rc, msg)
 
@@ -267,7 +283,7 @@ def test_truncated_and_overlong_files_are_refused_by_name(tmp_path, file_name):
         write_binary(folder, dict(files, **{file_name: struct.pack("<Q", count) + data[8:]}))
         _refused(folder, file_name)
     write_binary(tmp_path / "whole", files)
-    assert len(io.read_colmap(str(tmp_path / "whole"))) == 12 and c_read(tmp_path / "whole")[0] == 0
+    assert all(len(reader.read_colmap(str(tmp_path / "whole"))) == 12 for reader in READERS) and c_read(tmp_path / "whole")[0] == 0
 
 
 def test_inner_counts_that_exceed_the_file_are_refused(tmp_path):
@@ -286,8 +302,9 @@ def test_inner_counts_that_exceed_the_file_are_refused(tmp_path):
     write_binary(tmp_path / "w", dict(files, **{"cameras.bin": c[:16] + struct.pack("<Q", 2 ** 32) + c[24:]}))
     _refused(tmp_path / "w", "cameras.bin")
     write_binary(tmp_path / "ok", files)
-    got = io.read_colmap(str(tmp_path / "ok"))
-    assert len(got) == 1 and got[0]["worldpoints"] == [5] and got[0]["median_depth"] == np.float32(np.sqrt(3.0))
+    for reader in READERS:
+        got = reader.read_colmap(str(tmp_path / "ok"))
+        assert len(got) == 1 and got[0]["worldpoints"] == [5] and got[0]["median_depth"] == np.float32(np.sqrt(3.0))
 
 
 def test_point_ids_follow_the_text_readers_atoi(tmp_path):
@@ -309,5 +326,6 @@ def test_point_ids_follow_the_text_readers_atoi(tmp_path):
     rc2, _, cbin = c_read(tmp_path / "bin")
     assert rc == 0 and rc2 == 0 and ctxt[0]["worldpoints"] == cbin[0]["worldpoints"] == want
     _same_c(ctxt, cbin)
-    got = io.read_colmap(str(tmp_path / "bin"))
-    assert got[0]["worldpoints"] == want and float(got[0]["median_depth"]) == float(cbin[0]["median_depth"])
+    for reader in READERS:
+        got = reader.read_colmap(str(tmp_path / "bin"))
+        assert got[0]["worldpoints"] == want and float(got[0]["median_depth"]) == float(cbin[0]["median_depth"])

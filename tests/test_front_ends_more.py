@@ -19,6 +19,7 @@ from line3dpp_amd import front_end, io
 from tests import front_end_dataset as D
 from tests import front_end_dataset_more as DM
 from tests import triangulate_model as TM
+from tests.sfm_readers_model import rotation_from_q
 from tests.test_front_end_programs import Recorder, TAIL
 from tests.test_front_ends_pinned import _calls, _touch
 
@@ -472,7 +473,7 @@ def test_rotation_from_q_equals_the_reader_s():
     from line3dpp_amd.api import Line3D
     rng = np.random.default_rng(5)
     for q in list(rng.normal(size=(50, 4))) + [np.array([1.0, 0, 0, 0]), np.zeros(4), np.array([0, 0, 0, 1e-7])]:
-        assert np.array_equal(Line3D.rotationFromQ(*q), io.rotation_from_q(*q))
+        assert np.array_equal(Line3D.rotationFromQ(*q), rotation_from_q(*q))
 
 
 def _decompose_cases(sc):
@@ -506,7 +507,7 @@ def test_decompose_projection_matrix_gives_back_the_factors(dataset):
     assert Line3D.decomposeProjectionMatrix(np.zeros((4, 3))) is None
     r9 = np.zeros(9)
     assert L.l3d_rotation_from_rpy(0.1, 0.2, 0.3, ptr(r9)) == 0 and np.array_equal(r9.reshape(3, 3), io.rotation_from_rpy(0.1, 0.2, 0.3))
-    assert L.l3d_rotation_from_q(0.5, 0.5, -0.5, 0.5, ptr(r9)) == 0 and np.array_equal(r9.reshape(3, 3), io.rotation_from_q(0.5, 0.5, -0.5, 0.5))
+    assert L.l3d_rotation_from_q(0.5, 0.5, -0.5, 0.5, ptr(r9)) == 0 and np.array_equal(r9.reshape(3, 3), rotation_from_q(0.5, 0.5, -0.5, 0.5))
     assert L.l3d_rotation_from_rpy(0.1, 0.2, 0.3, None) != 0
 
 
@@ -536,4 +537,4 @@ def test_helpers_through_the_cpp_facade(dataset, tmp_path):
         assert np.array_equal(got, np.concatenate([k.reshape(-1), r.reshape(-1), tt]))
         _check_decomposition(K, R, t, got[:9].reshape(3, 3), got[9:18].reshape(3, 3), got[18:])
     for a, q, got in zip(angles, quats, out[len(cases):]):
-        assert np.array_equal(got[:9].reshape(3, 3), io.rotation_from_rpy(*a)) and np.array_equal(got[9:].reshape(3, 3), io.rotation_from_q(*q))
+        assert np.array_equal(got[:9].reshape(3, 3), io.rotation_from_rpy(*a)) and np.array_equal(got[9:].reshape(3, 3), rotation_from_q(*q))

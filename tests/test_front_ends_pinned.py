@@ -3,8 +3,8 @@ against the reference's OWN front ends: main_vsfm.cpp, main_colmap.cpp and main_
 (oracle/Makefile: oracle/_ref/libl3d_ref_front.so) against a RECORDER of the Line3D interface (oracle/ref_shim_front).
 Running a front end on an SfM result leaves the calls it makes on Line3D; what its parser hands to addImage -- camera id,
 K, R, t, median depth, worldpoint ids, and the distortion it hands to undistortImage -- is what the readers behind the
-C-ABI (l3d_nvm_*, l3d_sfm_* in line3dpp_amd/csrc/l3d_io.hip) and their Python twins (line3dpp_amd/io.py) must return.
-rotationFromQ inside the front ends is the reference's own (oracle/_ref/libl3d_ref.so).
+C-ABI (l3d_nvm_*, l3d_sfm_* in line3dpp_amd/csrc/l3d_io.hip) and line3dpp_amd/io.py, which reads through them, must
+return.  rotationFromQ inside the front ends is the reference's own (oracle/_ref/libl3d_ref.so).
 
 The reference ships no SfM result of any of the three kinds, so the FILES are generated here; the PARSERS are the
 reference's."""
@@ -74,7 +74,7 @@ def test_colmap_reader_equals_what_main_colmap_hands_to_addImage(tmp_path):
     assert rc == 0
     assert ev[0]["call"] == "Line3D" and ev[0]["output_folder"] == out and ev[0]["neighbors_by_worldpoints"] == 1
     added = _calls(ev, "addImage")
-    # ---- the Python twin ----
+    # ---- io.py, as the front ends read ----
     got = [g for g in io.read_colmap(str(tmp_path / "sfm")) if g["worldpoints"]]      # :389-410: no worldpoints, no addImage
     assert [a["camID"] for a in added] == [g["id"] for g in got] and len(got) == 5
     for a, g in zip(added, got):
@@ -151,12 +151,11 @@ def test_nvm_reader_equals_what_main_vsfm_hands_to_addImage(tmp_path):
     for u, i in zip(und, [0, 2, 3]):
         assert u["radial"] == [-float(got[i]["distortion"]), 0.0, 0.0] and u["tangential"] == [0.0, 0.0]   # :288-291
     # ---- the C-ABI ----
-    from tests.test_input_formats import _NvmCamera
     L, lib = _lib()
     h = C.c_void_p()
     assert lib.l3d_nvm_open(str(path).encode(), C.byref(h)) == 0
     for a in added:
-        c = _NvmCamera()
+        c = L.NvmCamera()
         assert lib.l3d_nvm_get_camera(h, a["camID"], C.byref(c)) == 0
         assert np.array_equal(np.array(c.R).reshape(3, 3), _m(a, "R")) and np.array_equal(np.array(c.t), a["t"])
         assert c.median_depth == np.float32(a["median_depth"]) and c.n_worldpoints == len(a["wps"])

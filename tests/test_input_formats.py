@@ -1,5 +1,8 @@
 """Input side: the segment cache of Line3D::detectLineSegments (boost binary archive of
-DataArray<float4>, dataArray.h:352-374) and the VisualSfM .nvm reader of main_vsfm.cpp:144-250 (line3dpp_amd/io.py).
+DataArray<float4>, dataArray.h:352-374), the VisualSfM .nvm reader of main_vsfm.cpp:144-250, COLMAP text results and
+bundler files.  One reader per format, the library's (line3dpp_amd/csrc/l3d_io.hip); line3dpp_amd/io.py wraps it, and
+tests/sfm_readers_model.py (M below) is the independent Python model it is held against.  Where a test pins a reader on
+hand-computed values, it does so for the wrapper and for the model ("the Python twin" in the names of the tests).
 The reference ships neither a cache file nor its vsfm_result.nvm (missing blob), so the byte layout is pinned on the
 archive rules that the reference's own BIN fixtures confirm (tests/test_bin_format.py: class header once, u64 counts) and
 on hand-built files; the camera arithmetic is pinned on the reference's formulas."""
@@ -9,18 +12,22 @@ import numpy as np
 import pytest
 
 from line3dpp_amd import io
+from tests import sfm_readers_model as M
+
+READERS = (io, M)          # the package's wrappers of the library, and the model
 
 
 @pytest.mark.parametrize("n", [0, 1, 2, 7, 3000])
 def test_segment_cache_round_trip_and_layout(tmp_path, n):
     rng = np.random.default_rng(n)
     segs = rng.uniform(0, 3000, (n, 4)).astype(np.float32)
-    raw = io.format_segment_cache(segs)
+    raw = M.format_segment_cache(segs)
     p = tmp_path / io.segment_cache_name(5, 3072, 2304)
     p.write_bytes(raw)
     assert p.name == "segments_L3D++_5_3072x2304_3000.bin"          # line3D.cc:300
-    back = io.read_segment_cache(p)
-    assert back.dtype == np.float32 and np.array_equal(back, segs)
+    for reader in READERS:
+        back = reader.read_segment_cache(p)
+        assert back.dtype == np.float32 and back.shape == (n, 4) and np.array_equal(back, segs)
     # layout: archive header (40 B), DataArray class header (5 B), 3 x u32 + 4 x u64, float4 class header, elements
     real = n + (n % 2)                                               # host rows padded to 32 B (dataArray.h:111-122)
     assert len(raw) == 40 + 5 + 12 + 32 + (5 if real else 0) + 16 * real
@@ -31,8 +38,9 @@ def test_segment_cache_round_trip_and_layout(tmp_path, n):
 def test_segment_cache_rejects_other_archives(tmp_path):
     p = tmp_path / "x.bin"
     p.write_bytes(b"not an archive at all, but long enough to be read as one........")
-    with pytest.raises(ValueError):
-        io.read_segment_cache(p)
+    for reader in READERS:
+        with pytest.raises(ValueError):
+            reader.read_segment_cache(p)
 
 
 def _write_nvm(path, cams, points):
@@ -59,11 +67,15 @@ def test_nvm_reader_follows_main_vsfm(tmp_path):
         points.append((p, [(c, k, 100.0 + k, 50.0) for c in seen]))
     path = tmp_path / "vsfm_result.nvm"
     _write_nvm(path, cams, points)
-    got = io.read_nvm(path)
+    for reader in READERS:
+        _nvm_follows_main_vsfm(reader.read_nvm(path), reader.nvm_intrinsics, cams, points)
+
+
+def _nvm_follows_main_vsfm(got, nvm_intrinsics, cams, points):
     assert len(got) == 4
     for i, (g, c) in enumerate(zip(got, cams)):
         qw, qx, qy, qz = c["q"]
-        R = io.nvm_rotation(qw, qx, qy, qz)
+        R = M.nvm_rotation(qw, qx, qy, qz)
         assert np.allclose(R @ R.T, np.eye(3), atol=1e-9) and np.isclose(np.linalg.det(R), 1.0)
         assert g["filename"] == c["filename"] and np.allclose(g["R"], R, atol=1e-9)
         assert np.allclose(g["t"], -R @ c["C"], atol=1e-8) and np.allclose(-g["R"].T @ g["t"], c["C"], atol=1e-8)
@@ -71,24 +83,21 @@ def test_nvm_reader_follows_main_vsfm(tmp_path):
         assert g["worldpoints"] == ids
         d = sorted(np.float32(np.linalg.norm(points[k][0] - c["C"])) for k in ids)
         assert g["median_depth"] == d[len(d) // 2]
-    K = io.nvm_intrinsics(got[0]["focal"], 3072, 2304)
+    K = nvm_intrinsics(got[0]["focal"], 3072, 2304)
     assert K[0, 2] == 1536.0 and K[1, 2] == 1152.0 and K[0, 0] == K[1, 1] == np.float32(2400.0)
 
 
 def test_nvm_without_cameras_is_refused(tmp_path):
     p = tmp_path / "empty.nvm"
     p.write_text("NVM_V3\n\n0\n\n0\n")
-    with pytest.raises(ValueError, match="No aligned cameras"):
-        io.read_nvm(p)
+    for reader in READERS:
+        with pytest.raises(ValueError, match="No aligned cameras"):
+            reader.read_nvm(p)
 
 
-# ---- the same readers behind the C-ABI (line3dpp_amd/csrc/l3d_io.hip): what a C++ caller of the library uses ----------
+# ---- the readers behind the C-ABI (line3dpp_amd/csrc/l3d_io.hip), call by call as a C++ caller of the library uses them,
+# against the model ----------------------------------------------------------------------------------------------------
 import ctypes as C  # noqa: E402
-
-
-class _NvmCamera(C.Structure):
-    _fields_ = [("filename", C.c_char_p), ("focal", C.c_float), ("distortion", C.c_float), ("median_depth", C.c_float),
-                ("n_worldpoints", C.c_uint32), ("R", C.c_double * 9), ("t", C.c_double * 3), ("C", C.c_double * 3)]
 
 
 def _lib():
@@ -103,12 +112,12 @@ def test_c_abi_segment_cache_equals_the_python_twin(tmp_path, n):
     segs = rng.uniform(0, 3000, (n, 4)).astype(np.float32)
     name = C.create_string_buffer(64)
     assert lib.l3d_segment_cache_name(5, 3072, 2304, 3000, name, 64) == 0
-    assert name.value.decode() == io.segment_cache_name(5, 3072, 2304) == "segments_L3D++_5_3072x2304_3000.bin"
+    assert name.value.decode() == io.segment_cache_name(5, 3072, 2304) == M.segment_cache_name(5, 3072, 2304) == "segments_L3D++_5_3072x2304_3000.bin"
     assert lib.l3d_segment_cache_name(5, 3072, 2304, 3000, name, 8) != 0
     p = tmp_path / name.value.decode()
     assert lib.l3d_write_segment_cache(str(p).encode(), L.ptr(segs) if n else None, n) == 0
-    assert p.read_bytes() == io.format_segment_cache(segs)                       # byte for byte what the twin writes
-    assert np.array_equal(io.read_segment_cache(p), segs)
+    assert p.read_bytes() == M.format_segment_cache(segs)                        # byte for byte what the model writes
+    assert np.array_equal(M.read_segment_cache(p), segs) and np.array_equal(io.read_segment_cache(p), segs)
     cnt = C.c_uint32(99)
     assert lib.l3d_read_segment_cache(str(p).encode(), None, 0, C.byref(cnt)) == 0 and cnt.value == n
     back = np.zeros((max(n, 1), 4), np.float32)
@@ -121,15 +130,16 @@ def test_c_abi_segment_cache_equals_the_python_twin(tmp_path, n):
 def test_c_abi_segment_cache_rejects_what_the_twin_rejects(tmp_path):
     L, lib = _lib()
     cnt = C.c_uint32(0)
-    good = io.format_segment_cache(np.ones((3, 4), np.float32))
+    good = M.format_segment_cache(np.ones((3, 4), np.float32))
     cases = {"junk": b"not an archive at all, but long enough to be read as one........", "short": good[:50],
              "long": good + b"\0", "two_rows": good[:49] + struct.pack("<I", 2) + good[53:],
              "sizes": good[:32] + bytes([4, 4, 4, 8, 1, 0, 0, 0]) + good[40:]}
     for name, raw in cases.items():
         p = tmp_path / (name + ".bin")
         p.write_bytes(raw)
-        with pytest.raises(ValueError):
-            io.read_segment_cache(p)
+        for reader in READERS:
+            with pytest.raises(ValueError):
+                reader.read_segment_cache(p)
         assert lib.l3d_read_segment_cache(str(p).encode(), None, 0, C.byref(cnt)) != 0, name
     assert lib.l3d_read_segment_cache(str(tmp_path / "missing.bin").encode(), None, 0, C.byref(cnt)) != 0
 
@@ -147,11 +157,11 @@ def test_c_abi_nvm_reader_equals_the_python_twin(tmp_path):
         points.append((rng.normal(size=3) * 3, [(c, k, 100.0 + k, 50.0) for c in seen]))
     path = tmp_path / "vsfm_result.nvm"
     _write_nvm(path, cams, points)
-    want = io.read_nvm(path)
+    want = M.read_nvm(path)
     h = C.c_void_p()
     assert lib.l3d_nvm_open(str(path).encode(), C.byref(h)) == 0 and lib.l3d_nvm_num_cameras(h) == 6
     for i, w in enumerate(want):
-        cam = _NvmCamera()
+        cam = L.NvmCamera()
         assert lib.l3d_nvm_get_camera(h, i, C.byref(cam)) == 0
         assert cam.filename.decode() == w["filename"] and cam.focal == w["focal"] and cam.distortion == w["distortion"]
         assert np.array_equal(np.array(cam.R).reshape(3, 3), w["R"]) and np.array_equal(np.array(cam.C), w["C"])
@@ -164,11 +174,11 @@ def test_c_abi_nvm_reader_equals_the_python_twin(tmp_path):
             assert cam.n_worldpoints == 0 and cam.median_depth == 0.0 and i == 5
         else:
             assert abs(cam.median_depth - w["median_depth"]) <= 2e-7 * w["median_depth"]
-    assert lib.l3d_nvm_get_camera(h, 6, C.byref(_NvmCamera())) != 0
+    assert lib.l3d_nvm_get_camera(h, 6, C.byref(L.NvmCamera())) != 0
     lib.l3d_nvm_close(h)
     K = np.zeros(9)
     lib.l3d_nvm_intrinsics(C.c_float(want[0]["focal"]), 3073, 2305, L.ptr(K))
-    assert np.array_equal(K.reshape(3, 3), io.nvm_intrinsics(want[0]["focal"], 3073, 2305))
+    assert np.array_equal(K.reshape(3, 3), M.nvm_intrinsics(want[0]["focal"], 3073, 2305))
     empty = tmp_path / "empty.nvm"
     empty.write_text("NVM_V3\n\n0\n\n0\n")
     assert lib.l3d_nvm_open(str(empty).encode(), C.byref(h)) == -6 and b"No aligned cameras" in lib.l3d_last_error()
@@ -203,7 +213,7 @@ def test_nvm_to_neighbours_end_to_end_on_the_host(tmp_path):
     assert lib.l3d_nvm_open(str(path).encode(), C.byref(h)) == 0
     ids, Ks, Rs, ts, wps = [], [], [], [], []
     for i in range(lib.l3d_nvm_num_cameras(h)):
-        cam = _NvmCamera(); lib.l3d_nvm_get_camera(h, i, C.byref(cam))
+        cam = L.NvmCamera(); lib.l3d_nvm_get_camera(h, i, C.byref(cam))
         w = np.zeros(cam.n_worldpoints, np.uint32); lib.l3d_nvm_get_worldpoints(h, i, L.ptr(w), cam.n_worldpoints)
         K = np.zeros(9); lib.l3d_nvm_intrinsics(cam.focal, sc.views[i].width, sc.views[i].height, L.ptr(K))
         ids.append(i); Ks.append(K.reshape(3, 3)); Rs.append(np.array(cam.R).reshape(3, 3)); ts.append(np.array(cam.t)); wps.append(w.tolist())
@@ -227,7 +237,7 @@ def test_c_abi_nvm_reader_tolerates_what_the_stream_parser_tolerates(tmp_path):
     p.write_text("NVM_V3\n\n2\n   a.jpg   1000   1 0 0 0   0 0 0   0 0\nb.jpg 1200 1 0 0 0 1 0 0 0.5 0\n\n3\n"
                  "0 0 5 1 2 3 2 0 0 1 1 1 0 2 2\n0 1 6 1 2 3 1 1 7 3 3\n")          # third point missing: file ends early
     assert lib.l3d_nvm_open(str(p).encode(), C.byref(h)) == 0 and lib.l3d_nvm_num_cameras(h) == 2
-    cam = _NvmCamera()
+    cam = L.NvmCamera()
     assert lib.l3d_nvm_get_camera(h, 0, C.byref(cam)) == 0 and cam.n_worldpoints == 1 and cam.focal == 1000.0
     assert lib.l3d_nvm_get_camera(h, 1, C.byref(cam)) == 0 and cam.n_worldpoints == 2 and cam.distortion == 0.5
     assert np.array_equal(np.array(cam.R).reshape(3, 3), np.eye(3)) and list(cam.t) == [-1.0, 0.0, 0.0]
@@ -235,14 +245,14 @@ def test_c_abi_nvm_reader_tolerates_what_the_stream_parser_tolerates(tmp_path):
     assert lib.l3d_nvm_get_worldpoints(h, 1, L.ptr(ids), 2) == 0 and ids.tolist() == [0, 1]
     assert lib.l3d_nvm_get_worldpoints(h, 1, L.ptr(ids), 1) == -9                     # L3D_ERR_LIMIT
     lib.l3d_nvm_close(h)
-    got = io.read_nvm(p)
-    assert [len(c["worldpoints"]) for c in got] == [1, 2]
+    for reader in READERS:
+        assert [len(c["worldpoints"]) for c in reader.read_nvm(p)] == [1, 2]
     bad = tmp_path / "bad.nvm"
     bad.write_text("NVM_V3\n\n1\na.jpg 1000 1 0 0 0 0 0 0 0 0\n\n1\n0 0 5 1 2 3 1 4 0 1 1\n")   # camera 4 of 1
     assert lib.l3d_nvm_open(str(bad).encode(), C.byref(h)) != 0 and b"malformed" in lib.l3d_last_error()
 
 
-# ---- COLMAP text results and bundler files (round 4: main_colmap.cpp:136-348, main_bundler.cpp:147-252) ----------------
+# ---- COLMAP text results and bundler files (main_colmap.cpp:136-348, main_bundler.cpp:147-252) --------------------------
 def _write_colmap(folder, cams, images, points, comments=True):
     folder.mkdir(exist_ok=True)
     with open(folder / "cameras.txt", "w") as f:
@@ -287,7 +297,16 @@ def test_colmap_reader_follows_main_colmap(tmp_path):
     rng = np.random.default_rng(4)
     cams, images, points = _colmap_scene(rng)
     _write_colmap(tmp_path / "sfm", cams, images, points)
-    got = io.read_colmap(str(tmp_path / "sfm"))
+    for reader in READERS:
+        _colmap_follows_main_colmap(reader.read_colmap(str(tmp_path / "sfm")), images, points)
+    # an unknown camera model is an error (main_colmap.cpp:221-226)
+    _write_colmap(tmp_path / "bad", [(1, "THIN_PRISM_FISHEYE", 100, 100, [1.0] * 12)], [], [])
+    for reader in READERS:
+        with pytest.raises(ValueError, match="unknown"):
+            reader.read_colmap(str(tmp_path / "bad"))
+
+
+def _colmap_follows_main_colmap(got, images, points):
     assert [g["id"] for g in got] == [10, 15, 20, 25, 30, 35]          # file order; the image of camera 9 is gone
     pts = dict(points)
     for g, (iid, q, t, cid, name, pl) in zip(got, images):
@@ -313,10 +332,6 @@ def test_colmap_reader_follows_main_colmap(tmp_path):
     assert np.array_equal(k[3]["radial"], [-0.05, 0, 0]) and np.array_equal(k[4]["radial"], [-0.05, 0.01, 0])
     assert np.array_equal(k[5]["radial"], [-0.05, 0.01, 0]) and np.array_equal(k[5]["tangential"], [1e-3, -2e-3])
     assert np.array_equal(k[7]["radial"], [-0.05, 0.01, 3e-4]) and np.array_equal(k[7]["tangential"], [1e-3, -2e-3])
-    # an unknown camera model is an error (main_colmap.cpp:221-226)
-    _write_colmap(tmp_path / "bad", [(1, "THIN_PRISM_FISHEYE", 100, 100, [1.0] * 12)], [], [])
-    with pytest.raises(ValueError, match="unknown"):
-        io.read_colmap(str(tmp_path / "bad"))
 
 
 def _check_sfm_handle(L, lib, h, want, colmap):
@@ -352,7 +367,7 @@ def test_c_abi_colmap_reader_equals_the_python_twin(tmp_path):
         cams, images, points = _colmap_scene(rng, n_img=9)
         folder = tmp_path / f"sfm{int(comments)}"
         _write_colmap(folder, cams, images, points, comments)
-        want = io.read_colmap(str(folder))
+        want = M.read_colmap(str(folder))
         h = C.c_void_p()
         assert lib.l3d_sfm_open_colmap(str(folder).encode(), C.byref(h)) == 0
         _check_sfm_handle(L, lib, h, want, True)
@@ -361,7 +376,7 @@ def test_c_abi_colmap_reader_equals_the_python_twin(tmp_path):
     assert lib.l3d_sfm_open_colmap(str(tmp_path / "nowhere").encode(), C.byref(h)) != 0 and b"does not exist" in lib.l3d_last_error()
     _write_colmap(tmp_path / "bad", [(1, "THIN_PRISM_FISHEYE", 100, 100, [1.0] * 12)], [], [])
     assert lib.l3d_sfm_open_colmap(str(tmp_path / "bad").encode(), C.byref(h)) != 0 and b"unknown" in lib.l3d_last_error()
-    # two quirks of main_colmap.cpp that both readers must share:
+    # two quirks of main_colmap.cpp that the library and the model must share:
     # (1) a repeated IMAGE_ID -- the reference's maps are keyed by the id, so both entries of the image sequence end up
     #     with the LAST pose and the LAST worldpoint list
     cams, images, points = _colmap_scene(rng, n_img=5)
@@ -370,11 +385,12 @@ def test_c_abi_colmap_reader_equals_the_python_twin(tmp_path):
     images.append((iid0, q, rng.normal(size=3) * 6, 2, "again.jpg", [(7.0, 8.0, points[3][0]), (9.0, 10.0, points[5][0])]))
     folder = tmp_path / "dup"
     _write_colmap(folder, cams, images, points)
-    want = io.read_colmap(str(folder))
-    assert [w["id"] for w in want].count(iid0) == 2
-    a, b = [w for w in want if w["id"] == iid0]
-    assert a["name"] == b["name"] == "again.jpg" and a["worldpoints"] == b["worldpoints"] == [points[3][0], points[5][0]]
-    assert np.array_equal(a["R"], b["R"]) and a["camera"] == b["camera"] == 2
+    want = M.read_colmap(str(folder))
+    for got in (want, io.read_colmap(str(folder))):
+        assert [w["id"] for w in got].count(iid0) == 2
+        a, b = [w for w in got if w["id"] == iid0]
+        assert a["name"] == b["name"] == "again.jpg" and a["worldpoints"] == b["worldpoints"] == [points[3][0], points[5][0]]
+        assert np.array_equal(a["R"], b["R"]) and a["camera"] == b["camera"] == 2
     assert lib.l3d_sfm_open_colmap(str(folder).encode(), C.byref(h)) == 0
     _check_sfm_handle(L, lib, h, want, True)
     lib.l3d_sfm_close(h)
@@ -383,8 +399,9 @@ def test_c_abi_colmap_reader_equals_the_python_twin(tmp_path):
     _write_colmap(folder, cams, images[:2], points)
     txt = (folder / "cameras.txt").read_text().split("\n")
     (folder / "cameras.txt").write_text("\n".join(txt[:3] + [""] + txt[3:]))
-    with pytest.raises(ValueError, match="unknown"):
-        io.read_colmap(str(folder))
+    for reader in READERS:
+        with pytest.raises(ValueError, match="unknown"):
+            reader.read_colmap(str(folder))
     assert lib.l3d_sfm_open_colmap(str(folder).encode(), C.byref(h)) != 0 and b"unknown" in lib.l3d_last_error()
 
 
@@ -414,15 +431,18 @@ def test_bundler_reader_follows_main_bundler_and_the_c_abi_equals_the_twin(tmp_p
         points.append((rng.normal(size=3) * 5, [(c, 7 * k, 10.0 + k, -3.5) for c in seen]))
     path = tmp_path / "bundle.rd.out"
     _write_bundler(path, cams, points)
-    want = io.read_bundler(str(path))
     flip = np.diag([1.0, -1.0, -1.0])
-    for w, c in zip(want, cams):
-        assert np.array_equal(w["R"], flip @ c["R"]) and np.array_equal(w["t"], flip @ c["t"])   # y / z rows negated (:192-212)
-        assert np.allclose(w["R"] @ w["C"] + w["t"], 0, atol=1e-12)
-        assert np.allclose(w["C"], -c["R"].T @ c["t"], atol=1e-12)                              # the centre does not change
-        assert w["focal"] == np.float32(c["f"]) and w["radial"][0] == np.float32(c["k1"]) and w["radial"][2] == 0
-    assert want[4]["median_depth"] is None and want[4]["worldpoints"] == []
-    assert want[0]["worldpoints"] == [k for k, (_, v) in enumerate(points) if any(c == 0 for c, *_ in v)]
+    for reader in READERS:
+        got = reader.read_bundler(str(path))
+        assert len(got) == len(cams)
+        for w, c in zip(got, cams):
+            assert np.array_equal(w["R"], flip @ c["R"]) and np.array_equal(w["t"], flip @ c["t"])   # y / z rows negated (:192-212)
+            assert np.allclose(w["R"] @ w["C"] + w["t"], 0, atol=1e-12)
+            assert np.allclose(w["C"], -c["R"].T @ c["t"], atol=1e-12)                              # the centre does not change
+            assert w["focal"] == np.float32(c["f"]) and w["radial"][0] == np.float32(c["k1"]) and w["radial"][2] == 0
+        assert got[4]["median_depth"] is None and got[4]["worldpoints"] == []
+        assert got[0]["worldpoints"] == [k for k, (_, v) in enumerate(points) if any(c == 0 for c, *_ in v)]
+    want = M.read_bundler(str(path))
     h = C.c_void_p()
     assert lib.l3d_sfm_open_bundler(str(path).encode(), C.byref(h)) == 0
     _check_sfm_handle(L, lib, h, want, False)
@@ -430,8 +450,9 @@ def test_bundler_reader_follows_main_bundler_and_the_c_abi_equals_the_twin(tmp_p
     empty = tmp_path / "empty.out"
     empty.write_text("# Bundle file v0.3\n0 0\n")
     assert lib.l3d_sfm_open_bundler(str(empty).encode(), C.byref(h)) == -6 and b"No cameras" in lib.l3d_last_error()
-    with pytest.raises(ValueError, match="No cameras"):
-        io.read_bundler(str(empty))
+    for reader in READERS:
+        with pytest.raises(ValueError, match="No cameras"):
+            reader.read_bundler(str(empty))
     assert lib.l3d_sfm_open_bundler(str(tmp_path / "missing.out").encode(), C.byref(h)) != 0
 
 

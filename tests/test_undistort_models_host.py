@@ -8,6 +8,7 @@ from line3dpp_amd import io
 from tests import undistort_model as M12
 from tests import undistort_models_cases as CASES
 from tests import undistort_models_model as M
+from tests.sfm_readers_model import _colmap_camera
 
 
 def _eq(a, b):
@@ -118,7 +119,7 @@ def test_the_agreement_cap_is_robust_on_the_gpu_tests_inputs(model):
 
 # ---- io.front_end_camera_model -----------------------------------------------------------------------------------------
 def _entry(model, params):
-    cam = io._colmap_camera(model, list(params), 640, 480)
+    cam = _colmap_camera(model, list(params), 640, 480)
     return dict(id=1, camera=1, name="a.jpg", worldpoints=[1, 2], **cam)
 
 
