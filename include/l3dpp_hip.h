@@ -550,7 +550,10 @@ int l3d_set_timing_level(l3d_ctx*, int level);
  * "csr_global_launches": launches of the global-cursor form of k_pair_csr (views beyond 32 768 segments, or
  * L3D_CSR_GLOBAL=1); "knn_replay_calls": l3d_match_begin calls whose kNN exceeded the LDS tables of the match kernel
  * (every row then takes the exact replay path); "lsd_images_detected": images LSD ran on; "lsd_cache_loads": images
- * whose segments came from the segment cache.  Unknown name: ~0. */
+ * whose segments came from the segment cache; "seam_support_wave_lists", "seam_support_group_staged_lists",
+ * "seam_support_sort_only_lists", "seam_support_all_pairs_lists": lists l3d_score_matches sent down each of the four paths
+ * of its support kernel (by list length; empty lists are not counted), "seam_score_unstaged_lists": lists it scored on the
+ * unstaged path of the scoring kernel.  Unknown name: ~0. */
 unsigned long long l3d_debug_counter(const char* name);
 
 /* ---- (2) seam layer ------------------------------------------------------------------ */
@@ -586,7 +589,11 @@ int l3d_save_result_obj(l3d_ctx*, const char* output_folder, int max_image_width
  * semantics of Line3D::scoringCPU (line3D.cc:1208-1294): score3D of every match of one view.  Host pointers,
  * arrays as scoringGPU marshals them: matches4[n] = (src segment, target camera, depth_p1, depth_p2), grouped per
  * segment and by target camera inside a segment (sortMatches); ranges2[M] = (first, last) inclusive, (-1,-1) if
- * none; reg_tgt2[n] = View::regularizerFrom3Dpoint of the two 3D end points in the target view; k = View::k(). */
+ * none; reg_tgt2[n] = View::regularizerFrom3Dpoint of the two 3D end points in the target view; k = View::k().
+ * The ranges have to partition the matches in segment order, every match inside the range of segment s has to name s as
+ * its source segment (matches4[i].x == s exactly), and every target camera has to be a finite, non-negative integer value
+ * below 2^32: anything else returns L3D_ERR_ARG with a message that names the first offending match, before any device
+ * work, and leaves `scores` untouched. */
 int l3d_score_matches(int device, const float* lines4, uint32_t M, const float* matches4, const int32_t* ranges2,
                       const float* reg_tgt2, uint32_t n, const double RtKinv[9], const double C[3], float two_sigA_sqr,
                       float k, float* scores);
@@ -601,8 +608,10 @@ int l3d_find_collinear_segments(int device, const float* lines4, uint32_t M, flo
  * replicator_dynamics_diffusion_GPU (cudawrapper.h:74-75, cudawrapper.cu:708-766: row normalisation + 10
  * diffusion steps P' = P o (P W)^T with the reference's lockstep row/column walk) + the min(w12, w21)
  * symmetrisation.  Host pointers in and out; `edges` in any order with ids < n_rows; `out` receives n_edges
- * CLEdges in (i, j) ascending order (the order performRDD rebuilds A_ in).  iterations = L3D_DEF_RDD_MAX_ITER (10)
- * in the reference.  l3d_reconstruct_3d_lines(perform_diffusion != 0) runs the same kernels on the context's
+ * CLEdges in (i, j) ascending order (the order performRDD rebuilds A_ in).  The pattern has to be symmetric, as A_
+ * always is: an edge (i, j) without (j, i) returns L3D_ERR_ARG before any device work (the reference reads out of
+ * bounds on such input when a row is left empty, and otherwise returns more entries than it was given).
+ * iterations = L3D_DEF_RDD_MAX_ITER (10) in the reference.  l3d_reconstruct_3d_lines(perform_diffusion != 0) runs the same kernels on the context's
  * device-resident affinity matrix. */
 int l3d_diffuse_affinity(int device, const l3d_cledge* edges, uint32_t n_edges, uint32_t n_rows, uint32_t iterations,
                          l3d_cledge* out);

@@ -16,8 +16,9 @@
 //
 // Column c of W sorted by row is, entry for entry, { A[r,c] : r in N(c) } = the TRANSPOSED values of row c of the
 // CSR (the pattern of A_ is symmetric: computingAffinityMatrix always pushes (i,j) and (j,i)), so no second,
-// column-sorted copy exists.  A missing transposed entry (foreign input) behaves as in the reference: nothing is
-// stored for it and the symmetrisation keeps w12.
+// column-sorted copy exists.  That identity needs the symmetric pattern: l3d_diffuse_affinity, the one entry that takes
+// foreign input, turns a pattern without its transpose away on the host (L3D_ERR_ARG; the reference has no defined result
+// for it either, l3d_seam.hip), so tpos is never kEmpty here and the guards on it below are belt and braces.
 //
 // Roofline: per iteration every entry reads min(deg i, deg j) pairs of 4-byte values that neighbouring entries
 // of the same row re-read (L2 hits) -- compulsory HBM traffic is 3 value arrays + indices = ~20 B per entry and

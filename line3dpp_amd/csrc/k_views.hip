@@ -167,6 +167,9 @@ __device__ __forceinline__ float sim_value(const d3 dira, float adp1, float adp2
 constexpr uint32_t kStageCap = 192;
 constexpr uint32_t kPoolFloats = 1632;                    // per-wave LDS pool: 8.5 floats per staged hypothesis
 constexpr float kDirSlack = 2e-6f;
+// capacities of a group of wpl waves: staged lists, and lists whose sort keys alone fit (3.5 floats per entry)
+__host__ __device__ constexpr uint32_t support_stage_cap(uint32_t wpl) { return kStageCap * wpl; }
+__host__ __device__ constexpr uint32_t support_sort_cap(uint32_t wpl) { return (kPoolFloats * wpl * 2 / 7) & ~1u; }
 
 // words per segment: (L+1) * ceil(L/64); lists longer than kStageCap are appended to long_list
 __global__ void k_bits_len(uint32_t G, const uint32_t* __restrict__ off, uint32_t* __restrict__ len,
@@ -197,8 +200,8 @@ void k_support(uint32_t G, const uint32_t* __restrict__ off, const uint32_t* __r
                const uint32_t* __restrict__ long_list) {
     __shared__ __attribute__((aligned(16))) float s_pool[4 * kPoolFloats];
     constexpr uint32_t GS = 64 * WPL;                                   // threads per list
-    constexpr uint32_t kStage = kStageCap * WPL;                        // staged capacity of the group's pool
-    constexpr uint32_t kSort = (kPoolFloats * WPL * 2 / 7) & ~1u;       // sort-only capacity (3.5 floats per entry)
+    constexpr uint32_t kStage = support_stage_cap(WPL);                 // staged capacity of the group's pool
+    constexpr uint32_t kSort = support_sort_cap(WPL);                   // sort-only capacity
     const uint32_t wave = threadIdx.x >> 6;
     const uint32_t t = WPL == 1 ? lane_id() : threadIdx.x;              // thread index within the group
     uint32_t g;
@@ -353,6 +356,17 @@ void k_support(uint32_t G, const uint32_t* __restrict__ off, const uint32_t* __r
 //   support:  fresh hypothesis i is positive iff S_i intersects the presence mask
 
 constexpr uint32_t kScoreCap = 192;   // per-wave LDS staging of a list: 50 B per hypothesis
+// Which path a list of L hypotheses takes through k_support (k_bits_len sends the lists beyond kStageCap to the
+// four-wave group) and k_score_all, from the limits above: what l3d_score_matches counts for l3d_debug_counter.
+ListTier list_tier(uint32_t L) {
+    ListTier t{};
+    t.support = L == 0 ? kSupportNone
+              : L <= support_stage_cap(1) ? kSupportWave
+              : L <= support_stage_cap(4) ? kSupportGroupStaged
+              : L <= support_sort_cap(4) ? kSupportSortOnly : kSupportAllPairs;
+    t.score_unstaged = L > kScoreCap;
+    return t;
+}
 // scores of all views (batched): for every existing hypothesis i walk the existing supporters (S_i & P) in
 // canonical order with the reference's per-camera replace/subtract accumulation (line3D.cc:1255-1274); a zero
 // similarity never changes that accumulation, so visiting only the supporters gives the same float result.

@@ -11,6 +11,12 @@ namespace l3d {
 extern std::atomic<uint64_t> g_knn_replay_calls;      // l3d_api.hip
 extern std::atomic<uint64_t> g_keep_all_repeats;      // l3d_api.hip
 extern std::atomic<uint64_t> g_csr_global_launches;   // k_lists.hip, test hook read through l3d_debug_counter
+// l3d_seam.hip, test hooks: lists l3d_score_matches sent down each path of k_support / k_score_all (k_views.hip)
+extern std::atomic<uint64_t> g_seam_support_lists[4];  // indexed by SupportTier - 1
+extern std::atomic<uint64_t> g_seam_score_unstaged_lists;
+enum SupportTier : uint32_t { kSupportNone = 0, kSupportWave, kSupportGroupStaged, kSupportSortOnly, kSupportAllPairs };
+struct ListTier { SupportTier support; bool score_unstaged; };
+ListTier list_tier(uint32_t L);   // k_views.hip, next to the limits it is derived from
 
 constexpr int kMatchRows = 64;   // source rows per work item of k_match_pairs (one wave64): the ROW form (keep-all modes, brute-force
                                  // hook, the accelerator seam, L3D_MATCH_TILE=0)

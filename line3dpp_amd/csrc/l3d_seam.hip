@@ -5,6 +5,11 @@
 
 using namespace l3d;
 
+namespace l3d {
+std::atomic<uint64_t> g_seam_support_lists[4];        // test hooks (l3d_debug_counter): lists of l3d_score_matches per path
+std::atomic<uint64_t> g_seam_score_unstaged_lists{0};
+}  // namespace l3d
+
 extern "C" {
 
 // seam layer: match_lines_GPU replacement (cudawrapper.h:54-63) with CPU-path semantics
@@ -15,6 +20,20 @@ int l3d_diffuse_affinity(int device, const l3d_cledge* edges, uint32_t n_edges, 
     for (uint32_t k = 0; k < n_edges; ++k)
         if (edges[k].i_ < 0 || edges[k].j_ < 0 || (uint32_t)edges[k].i_ >= n_rows || (uint32_t)edges[k].j_ >= n_rows)
             return fail(L3D_ERR_ARG, "edge index outside [0, n_rows)");
+    // The kernels read column c of W off row c of the one CSR structure (k_rdd.hip), which holds only for a pattern that
+    // has (j, i) wherever it has (i, j) -- what computingAffinityMatrix builds.  The reference itself has no defined
+    // result for anything else: a row that is empty while its column is not makes K_sparseMat_diffusion_step read
+    // P[-1] (cudawrapper.cu:499-503, 524-528), and performRDD hands back MORE entries than it was given (it adds the
+    // missing (j, i), line3D.cc:2039-2070), which `out` has no room for.  Such input is turned away.
+    {
+        std::vector<uint64_t> keys(n_edges);
+        for (uint32_t k = 0; k < n_edges; ++k) keys[k] = ((uint64_t)(uint32_t)edges[k].i_ << 32) | (uint32_t)edges[k].j_;
+        std::sort(keys.begin(), keys.end());
+        for (uint32_t k = 0; k < n_edges; ++k)
+            if (!std::binary_search(keys.begin(), keys.end(), ((uint64_t)(uint32_t)edges[k].j_ << 32) | (uint32_t)edges[k].i_))
+                return fail(L3D_ERR_ARG, "l3d_diffuse_affinity: edge " + std::to_string(k) + " = (" + std::to_string(edges[k].i_) +
+                                         ", " + std::to_string(edges[k].j_) + ") has no transposed entry: the pattern has to be symmetric");
+    }
     if (hipSetDevice(device) != hipSuccess) return fail(L3D_ERR_HIP, "hipSetDevice failed: no usable HIP device");
     DevBuf<l3d_cledge> din, dout; DevBuf<char> ws;
     const size_t wb = rdd_workspace_bytes(n_edges, n_rows);
@@ -96,6 +115,18 @@ int l3d_score_matches(int device, const float* lines4, uint32_t M, const float* 
         off[M] = next;
         if (next != n) return fail(L3D_ERR_ARG, "ranges do not cover the matches");
     }
+    // k_seam_entries indexes the view's segments with matches4[i].x: it has to be the segment whose range holds match i
+    // (one comparison turns away values at or beyond M, negatives, NaN and fractions); the camera has to be an id
+    for (uint32_t s = 0; s < M; ++s)
+        for (uint32_t i = off[s]; i < off[s + 1]; ++i) {
+            const float x = matches4[4 * (size_t)i], y = matches4[4 * (size_t)i + 1];
+            if (!((double)x == (double)s))
+                return fail(L3D_ERR_ARG, "l3d_score_matches: match " + std::to_string(i) + " lies in the range of segment " +
+                                         std::to_string(s) + " but names source segment " + std::to_string(x));
+            if (!(y >= 0.0f && y < 4294967296.0f && y == std::floor(y)))
+                return fail(L3D_ERR_ARG, "l3d_score_matches: match " + std::to_string(i) + " of segment " + std::to_string(s) +
+                                         " names target camera " + std::to_string(y) + ", which is no camera id");
+        }
     if (hipSetDevice(device) != hipSuccess) return fail(L3D_ERR_HIP, "hipSetDevice failed: no usable HIP device");
     DevBuf<float4> seg4, m4; DevBuf<float2> rt; DevBuf<SegF> segf; DevBuf<SegX> segx; DevBuf<ViewDev> dv;
     DevBuf<uint32_t> d_off, d_boff, d_len, d_scal, d_gv, d_long, d_max; DevBuf<unsigned long long> d_tmp; DevBuf<DEntry> dents; DevBuf<uint64_t> bits;
@@ -140,6 +171,12 @@ int l3d_score_matches(int device, const float* lines4, uint32_t M, const float* 
         return L3D_OK;
     }();
     cleanup();
+    if (rc == L3D_OK)
+        for (uint32_t s = 0; s < M; ++s) {
+            const ListTier t = list_tier(off[s + 1] - off[s]);
+            if (t.support != kSupportNone) g_seam_support_lists[t.support - 1].fetch_add(1, std::memory_order_relaxed);
+            if (t.score_unstaged) g_seam_score_unstaged_lists.fetch_add(1, std::memory_order_relaxed);
+        }
     return rc;
 }
 

@@ -118,7 +118,9 @@ def lib(reference=False):
         L.lo_set_collinearity.argtypes = [vp, f32]
         L.lo_get_collinear.argtypes = [vp, u32, vp, vp, u32]; L.lo_get_collinear.restype = u32
         if not reference:
+            L.lo_find_collinear.argtypes = [vp, u32, f32]
             L.lo_rdd.argtypes = [vp, u32, u32, u32, vp]; L.lo_rdd.restype = u32
+            L.lo_score_lists.argtypes = [vp, u32, vp, vp, vp, u32, f32, f32, vp, vp, vp]; L.lo_score_lists.restype = u64
         if reference:
             L.lo_ref_view_matrices.argtypes = [vp, u32, vp, vp]
             L.lo_ref_fundamental.argtypes = [vp, u32, u32, vp]
@@ -220,6 +222,11 @@ class Oracle:
         """collinearity_t_ of reconstruct3Dlines (line3D.cc:1725); > 0 adds the collinear-segment links"""
         self.L.lo_set_collinearity(self.h, float(t))
 
+    def find_collinear(self, cam, dist_t):
+        """View::findCollinearSegments(dist_t) of view `cam` alone (restatement only); read the lists with collinear()"""
+        assert not self.reference
+        self.L.lo_find_collinear(self.h, int(cam), float(dist_t))
+
     def collinear(self, cam, M):
         """View::collinearSegments for every segment of view `cam` as CSR (offsets[M+1], idx)"""
         off = np.zeros(M + 1, np.uint32)
@@ -254,6 +261,26 @@ class Oracle:
 
     def scored(self, cam):
         return self._rows(self.L.lo_get_scored, cam)
+
+    def score_lists(self, cam, matches4, ranges2, reg_tgt2, k, two_sigA_sqr, return_regs=False, replaced_per_seg=None):
+        """scoringCPU's loops on caller-supplied lists of view `cam`, arrays as l3d_score_matches takes them (restatement
+        only; see l3d_oracle.cpp lo_score_lists).  reg_tgt2 = None: the target-side regularisers come from the context's
+        views in their current frame.  replaced_per_seg: optional uint64 array [M] that receives the replace-branch count of
+        every segment's list.  -> (scores [n], times the replace branch ran[, regularisers used [n, 2]])"""
+        assert not self.reference, "score_lists exists in the restatement only"
+        m = np.ascontiguousarray(matches4, np.float32).reshape(-1, 4)
+        r = np.ascontiguousarray(ranges2, np.int32).reshape(-1, 2)
+        assert len(r) == self.M[cam], "one range per segment of the view"
+        g = None if reg_tgt2 is None else np.ascontiguousarray(reg_tgt2, np.float32).reshape(-1, 2)
+        assert g is None or len(g) == len(m)
+        assert replaced_per_seg is None or (replaced_per_seg.dtype == np.uint64 and len(replaced_per_seg) == len(r))
+        scores = np.zeros(len(m), np.float32)
+        regs = np.zeros((len(m), 2), np.float32)
+        rep = self.L.lo_score_lists(self.h, int(cam), _p(m), _p(r), None if g is None else _p(g), len(m), float(k),
+                                    float(two_sigA_sqr), _p(scores), _p(regs),
+                                    None if replaced_per_seg is None else _p(replaced_per_seg))
+        assert rep != 2**64 - 1, "a range leaves the matches"
+        return (scores, int(rep), regs) if return_regs else (scores, int(rep))
 
     def best(self):
         n = self.L.lo_num_best(self.h)
