@@ -616,6 +616,74 @@ int l3d_find_collinear_segments(int device, const float* lines4, uint32_t M, flo
 int l3d_diffuse_affinity(int device, const l3d_cledge* edges, uint32_t n_edges, uint32_t n_rows, uint32_t iterations,
                          l3d_cledge* out);
 
+/* ---- projection of the 3D lines into cameras (GPU: k_project.hip) ---------------------------------------
+ * No reference counterpart: the reference's only projection is the file-local helper of filterTinySegments
+ * (line3D.cc:2414-2452).  Three stages, each a function of the one before it alone: 2D segments clipped at the near
+ * plane and at the image rectangle; a line-id plane and an inverse-depth plane per camera; the lines drawn over an image.
+ * A pinhole camera without distortion: x ~ K (R X + t), row-major K and R, the image is width x height pixels. */
+typedef struct l3d_camera {
+    double K[9], R[9], t[3];
+    uint32_t width, height;
+} l3d_camera;
+/* one visible 3D segment in one camera (32 bytes): end points in pixels, 1 / depth at both, the index of its 3D line and
+ * its own index in the flat segment array.  The two top bits of `segment` are flags: L3D_PROJ_CLIPPED_NEAR (bit 31) = an
+ * end point was moved onto the near plane, L3D_PROJ_CLIPPED_RECT (bit 30) = an end point was moved onto the border of
+ * the image; `segment & L3D_PROJ_SEGMENT_MASK` is the index. */
+typedef struct l3d_projected_segment {
+    float x1, y1, x2, y2;
+    float inv_depth1, inv_depth2;
+    uint32_t line;
+    uint32_t segment;
+} l3d_projected_segment;
+#define L3D_PROJ_CLIPPED_NEAR 0x80000000u
+#define L3D_PROJ_CLIPPED_RECT 0x40000000u
+#define L3D_PROJ_SEGMENT_MASK 0x3FFFFFFFu
+/* Argument checks of every entry below, L3D_ERR_ARG with a message and the outputs untouched: near <= 0 or not finite; an
+ * even or zero thickness; alpha > 255; a camera with a zero side or a non-finite entry; a non-finite 3D end point or
+ * record; an image whose size differs from its camera's (or that is not 8-bit with 1 or 3 channels); a null pointer where
+ * one is needed.  L3D_ERR_LIMIT likewise: more than 2^30 segments, a line index of 2^31 or more, a thickness beyond 255,
+ * a camera or image side of more than 65535 pixels.  A (camera, segment) whose projection is not finite in float32 (a K
+ * whose third row gives 0 there, an overflow) is not visible.  Zero cameras or zero segments: L3D_OK, counts zeroed,
+ * planes empty (-1 / 0), images copied.  Host pointers in and out. */
+/* Stage 1.  segments[n_segments]: P1 and P2 are read (world frame, as l3d_get_3d_lines returns them); line_of_segment[i] =
+ * the 3D line of segment i.  counts[n_cams] = visible segments per camera; their records camera after camera, in
+ * ascending segment order inside a camera, to out (may be NULL or shorter: the first `cap` are written); *n = their
+ * number over all cameras. */
+int l3d_project_segments(int device, uint32_t n_cams, const l3d_camera* cams, uint32_t n_segments,
+                         const l3d_segment3d* segments, const uint32_t* line_of_segment, double near_plane,
+                         uint32_t* counts, l3d_projected_segment* out, uint64_t cap, uint64_t* n);
+/* Stage 2.  records: n_records_per_cam[c] records of camera c, camera after camera (of the cameras only width and height
+ * are read).  line_id_planes[c]: height x width int32, the line drawn at a pixel or -1; inv_depth_planes[c] (the array or
+ * single entries may be NULL): height x width float, its 1 / depth there or 0.  Where lines cross the nearest wins, of
+ * equal depths the smaller line index; thickness = odd number of pixels across the line. */
+int l3d_render_line_maps(int device, uint32_t n_cams, const l3d_camera* cams, const uint32_t* n_records_per_cam,
+                         const l3d_projected_segment* records, uint32_t thickness, int32_t* const* line_id_planes,
+                         float* const* inv_depth_planes);
+/* Stage 3.  images[c]: 8-bit, 1 or 3 channels, of the size of line_id_planes[c] (row_stride >= cols * channels);
+ * out_rgb[c] receives rows x cols x 3 bytes, packed.  Where line_id >= 0 the pixel is blended with the line's colour,
+ * (alpha * colour + (255 - alpha) * source + 127) / 255; elsewhere it is copied.  colors: n_lines RGB triples, or NULL
+ * for the fixed palette of DESIGN §16 (which a line index >= n_lines takes as well). */
+int l3d_draw_line_maps(int device, uint32_t n_cams, const l3d_image* images, const int32_t* const* line_id_planes,
+                       uint32_t n_lines, const uint8_t* colors, uint32_t alpha, uint8_t* const* out_rgb);
+/* The same over the lines the last l3d_reconstruct_3d_lines left in the context (none: L3D_ERR_STATE); `line` is the index
+ * of the FinalLine3D in l3d_get_3d_lines' order, `segment` the index in its flat segment array.
+ * l3d_view_camera: K, R, t and the image size of an added view (original frame), ready for the calls below.  t is the
+ * view's own: after matchImages it is -R C of a centre that was moved by the scene translation and back
+ * (line3D.cc:500-545), a few roundings from the t handed to addImage.  L3D_ERR_STATE while a split call is open. */
+int l3d_view_camera(l3d_ctx*, uint32_t camID, l3d_camera* cam);
+int l3d_project_lines(l3d_ctx*, uint32_t n_cams, const l3d_camera* cams, double near_plane, uint32_t* counts);
+/* records of the last l3d_project_lines on this context, as l3d_project_segments hands them out */
+int l3d_get_projected_lines(l3d_ctx*, l3d_projected_segment* out, uint64_t cap, uint64_t* n);
+int l3d_render_lines(l3d_ctx*, uint32_t n_cams, const l3d_camera* cams, double near_plane, uint32_t thickness,
+                     int32_t* const* line_id_planes, float* const* inv_depth_planes);
+/* l3d_draw_lines: colors is NULL (the palette) or holds one RGB triple for EVERY 3D line of the context, n_lines of
+ * l3d_num_3d_lines: the entry is not given the table's length and reads 3 * n_lines bytes. */
+int l3d_draw_lines(l3d_ctx*, uint32_t n_cams, const l3d_camera* cams, const l3d_image* images, double near_plane,
+                   uint32_t thickness, uint32_t alpha, const uint8_t* colors, uint8_t* const* out_rgb);
+/* test hook: the device-memory budget under which the context forms above cut the cameras into groups (0: the default of
+ * 256 MiB); a small one makes many groups.  The results do not depend on it. */
+int l3d_set_projection_budget(l3d_ctx*, uint64_t bytes);
+
 #ifdef __cplusplus
 }
 #endif

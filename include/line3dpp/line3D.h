@@ -8,6 +8,8 @@
 //     addImage(camID, image, K, R, t, median_depth, wps_or_neighbors, line_segments)
 //     matchImages(sigma_position, sigma_angle, num_neighbors, epipolar_overlap, kNN, const_regularization_depth)
 //     computeAffinityMatrix()            // the affinity part of reconstruct3Dlines()
+//     projectLines(camID | K, R, t, width, height, out)    (no reference counterpart: the 3D lines as a camera sees them)
+//     drawLines(camID | K, R, t, inImg, outImg, thickness, alpha)      (... drawn over an image)
 //
 // Same names, argument order, defaults (commons.h:40-70) and error behaviour as the reference: errors
 // are printed with the "[L3D++] ERROR:" prefix and the call returns (void), no exceptions
@@ -430,9 +432,87 @@ public:
         for (uint32_t i = 0; i < nr; ++i) local2global[(int)i] = l[i];
     }
 
+    // The 3D lines of the last reconstruct3Dlines as a camera sees them (no reference counterpart; DESIGN §16,
+    // k_project.hip): one l3d_projected_segment per visible 3D segment, clipped at the near plane and at the image, in
+    // ascending segment order.  The camera is an added view (camID) or any K, R, t with an image size.  Errors are
+    // printed and leave `out` empty.
+    template <class Mat3, class Vec3>
+    void projectLines(const Mat3& K, const Mat3& R, const Vec3& t, const unsigned int width, const unsigned int height,
+                      std::vector<l3d_projected_segment>& out, const double near_plane = 1e-6) {
+        project_camera(make_camera(K, R, t, width, height), out, near_plane);
+    }
+    void projectLines(const unsigned int camID, std::vector<l3d_projected_segment>& out, const double near_plane = 1e-6) {
+        out.clear();
+        l3d_camera cam{};
+        if (l3d_view_camera(ctx_, camID, &cam) != L3D_OK) {
+            std::cout << prefix_err_ << "projectLines [" << camID << "]: " << l3d_last_error() << std::endl;
+            return;
+        }
+        project_camera(cam, out, near_plane);
+    }
+
+    // The 3D lines drawn over inImg (cv::Mat, Image8U or ImageBuf8U, 8-bit with 1 or 3 channels, of the camera's size):
+    // outImg.create(rows, cols, 16) -- RGB -- as undistortImage makes its output; thickness in pixels (odd), alpha 0..255,
+    // one colour per line from a fixed palette.  Errors are printed and leave outImg empty.
+    template <class InImage, class OutImage>
+    void drawLines(const unsigned int camID, const InImage& inImg, OutImage& outImg, const unsigned int thickness = 1,
+                   const unsigned int alpha = 255) {
+        l3d_camera cam{};
+        if (l3d_view_camera(ctx_, camID, &cam) != L3D_OK) {
+            std::cout << prefix_err_ << "drawLines [" << camID << "]: " << l3d_last_error() << std::endl;
+            outImg.release();
+            return;
+        }
+        draw_camera(cam, inImg, outImg, thickness, alpha);
+    }
+    template <class Mat3, class Vec3, class InImage, class OutImage>
+    void drawLines(const Mat3& K, const Mat3& R, const Vec3& t, const InImage& inImg, OutImage& outImg,
+                   const unsigned int thickness = 1, const unsigned int alpha = 255) {
+        draw_camera(make_camera(K, R, t, (unsigned int)inImg.cols, (unsigned int)inImg.rows), inImg, outImg, thickness, alpha);
+    }
+
     l3d_ctx* handle() { return ctx_; }
 
 private:
+    template <class Mat3, class Vec3>
+    static l3d_camera make_camera(const Mat3& K, const Mat3& R, const Vec3& t, unsigned int width, unsigned int height) {
+        l3d_camera cam{};
+        for (int i = 0; i < 3; ++i) {
+            for (int j = 0; j < 3; ++j) { cam.K[3 * i + j] = K(i, j); cam.R[3 * i + j] = R(i, j); }
+            cam.t[i] = t(i);
+        }
+        cam.width = width; cam.height = height;
+        return cam;
+    }
+    void project_camera(const l3d_camera& cam, std::vector<l3d_projected_segment>& out, double near_plane) {
+        out.clear();
+        uint32_t count = 0;
+        uint64_t n = 0;
+        if (l3d_project_lines(ctx_, 1, &cam, near_plane, &count) != L3D_OK) {
+            std::cout << prefix_err_ << "projectLines: " << l3d_last_error() << std::endl;
+            return;
+        }
+        out.resize(count);
+        l3d_get_projected_lines(ctx_, out.data(), out.size(), &n);
+    }
+    template <class InImage, class OutImage>
+    void draw_camera(const l3d_camera& cam, const InImage& inImg, OutImage& outImg, unsigned int thickness, unsigned int alpha) {
+        const int ty = inImg.type();
+        const l3d_image in{(const uint8_t*)inImg.data, (uint32_t)inImg.cols, (uint32_t)inImg.rows, ty == 0 ? 1u : ty == 16 ? 3u : 0u,
+                           (uint32_t)(size_t)inImg.step};
+        const size_t row = 3 * (size_t)in.cols;
+        std::vector<uint8_t> tmp(row * in.rows);      // (the input may be the output: composed here, copied when done)
+        uint8_t* dst = tmp.data();
+        if (l3d_draw_lines(ctx_, 1, &cam, &in, 1e-6, thickness, alpha, nullptr, &dst) != L3D_OK) {
+            std::cout << prefix_err_ << "drawLines: " << l3d_last_error() << std::endl;
+            outImg.release();
+            return;
+        }
+        outImg.create((int)in.rows, (int)in.cols, 16);
+        for (uint32_t r = 0; r < in.rows; ++r)
+            std::memcpy((uint8_t*)outImg.data + r * (size_t)outImg.step, tmp.data() + r * row, row);
+    }
+
     template <class InImage, class OutImage, class Params, class Mat3>
     static void undistort_model(const InImage& inImg, OutImage& outImg, uint32_t model, const Params& params, const Mat3& K,
                                 const Mat3* K_new) {

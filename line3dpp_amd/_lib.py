@@ -25,7 +25,12 @@ SLOT_DTYPE = np.dtype([
     ("tgt_seg", "<u4"), ("overlap", "<f4"), ("d_p1", "<f4"), ("d_p2", "<f4"), ("d_q1", "<f4"), ("d_q2", "<f4"),
     ("score3D", "<f4"), ("flags", "<u4")])
 FLOAT4_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("w", "<f4")])
+# l3d_projected_segment: a 3D segment as a camera sees it; flag bits in `segment`
+PROJECTED_SEGMENT_DTYPE = np.dtype([("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"), ("y2", "<f4"), ("inv_depth1", "<f4"),
+                                    ("inv_depth2", "<f4"), ("line", "<u4"), ("segment", "<u4")])
+PROJ_CLIPPED_NEAR, PROJ_CLIPPED_RECT, PROJ_SEGMENT_MASK = 0x80000000, 0x40000000, 0x3FFFFFFF
 assert MATCH_DTYPE.itemsize == 40 and SLOT_DTYPE.itemsize == 32 and SEGMENT3D_DTYPE.itemsize == 80
+assert PROJECTED_SEGMENT_DTYPE.itemsize == 32
 EMPTY = 0xFFFFFFFF
 L3D_ERR_NO_SEGMENTS = -5
 L3D_ERR_IO = -11
@@ -98,6 +103,18 @@ class CameraModel(C.Structure):
                 ("K_new", C.c_double * 9)]
 
 
+class Camera(C.Structure):
+    """l3d_camera (include/l3dpp_hip.h): a pinhole camera of the projection stages, K and R row-major"""
+    _fields_ = [("K", C.c_double * 9), ("R", C.c_double * 9), ("t", C.c_double * 3), ("width", C.c_uint32),
+                ("height", C.c_uint32)]
+
+
+class ProjectedSegment(C.Structure):
+    """l3d_projected_segment (include/l3dpp_hip.h) = PROJECTED_SEGMENT_DTYPE"""
+    _fields_ = [("x1", C.c_float), ("y1", C.c_float), ("x2", C.c_float), ("y2", C.c_float), ("inv_depth1", C.c_float),
+                ("inv_depth2", C.c_float), ("line", C.c_uint32), ("segment", C.c_uint32)]
+
+
 class DetectStats(C.Structure):
     """l3d_detect_stats (include/l3dpp_hip.h)"""
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("raw_segments", C.c_uint32), ("segments", C.c_uint32),
@@ -127,6 +144,8 @@ EXPORTS = [
     "l3d_add_view_image", "l3d_add_view_image_worldpoints", "l3d_undistort_images",
     "l3d_undistort_images_model", "l3d_sfm_get_camera_model", "l3d_sfm_get_camera_params",
     "l3d_triangulate_points", "l3d_rotation_from_rpy", "l3d_rotation_from_q", "l3d_decompose_projection_matrix",
+    "l3d_project_segments", "l3d_render_line_maps", "l3d_draw_line_maps", "l3d_view_camera", "l3d_project_lines",
+    "l3d_get_projected_lines", "l3d_render_lines", "l3d_draw_lines", "l3d_set_projection_budget",
 ]
 
 _lib = None
@@ -242,6 +261,15 @@ def load():
     L.l3d_rotation_from_rpy.argtypes = [f64, f64, f64, vp]
     L.l3d_rotation_from_q.argtypes = [f64, f64, f64, f64, vp]
     L.l3d_decompose_projection_matrix.argtypes = [vp, vp, vp, vp]
+    L.l3d_project_segments.argtypes = [i32, u32, vp, u32, vp, vp, f64, vp, vp, u64, C.POINTER(u64)]
+    L.l3d_render_line_maps.argtypes = [i32, u32, vp, vp, vp, u32, vp, vp]
+    L.l3d_draw_line_maps.argtypes = [i32, u32, vp, vp, u32, vp, u32, vp]
+    L.l3d_view_camera.argtypes = [vp, u32, C.POINTER(Camera)]
+    L.l3d_project_lines.argtypes = [vp, u32, vp, f64, vp]
+    L.l3d_get_projected_lines.argtypes = [vp, vp, u64, C.POINTER(u64)]
+    L.l3d_render_lines.argtypes = [vp, u32, vp, f64, u32, vp, vp]
+    L.l3d_draw_lines.argtypes = [vp, u32, vp, vp, f64, u32, u32, vp, vp]
+    L.l3d_set_projection_budget.argtypes = [vp, u64]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("l3d_last_error", "l3d_build_info", "l3d_create", "l3d_destroy"):

@@ -15,8 +15,8 @@ import threading
 import numpy as np
 
 from . import _lib, lsd
-from ._lib import (CLEDGE_DTYPE, EMPTY, FLOAT4_DTYPE, MATCH_DTYPE, SEGMENT2D_DTYPE, SEGMENT3D_DTYPE, SLOT_DTYPE,
-                   MatchParams, Timings, ptr)
+from ._lib import (CLEDGE_DTYPE, EMPTY, FLOAT4_DTYPE, MATCH_DTYPE, PROJECTED_SEGMENT_DTYPE, SEGMENT2D_DTYPE,
+                   SEGMENT3D_DTYPE, SLOT_DTYPE, MatchParams, Timings, ptr)
 
 # commons.h:40-70
 L3D_DEF_MATCHING_NEIGHBORS = 10
@@ -357,6 +357,87 @@ class Line3D:
         return [dict(collinear3Dsegments=segs[so[i]:so[i + 1]], residuals=res[ro[i]:ro[i + 1]],
                      cluster_line=cl[i], reference_view=int(rv[i])) for i in range(nl.value)]
 
+    # ---- the 3D lines projected into cameras (no reference counterpart) -----------------------------------
+    def viewCamera(self, camID):
+        """l3d_view_camera: K, R, t and the image size of an added view as a dict (None after an error)"""
+        cam = _lib.Camera()
+        if not self._check(self.L.l3d_view_camera(self.h, int(camID), C.byref(cam)), f"viewCamera [{camID}]"):
+            return None
+        return camera_dict(cam)
+
+    def _cameras(self, cams_or_camIDs):
+        """a list of camera IDs of added views and / or cameras (dicts as viewCamera returns them) -> l3d_camera array"""
+        cams = []
+        for c in cams_or_camIDs:
+            if isinstance(c, (int, np.integer)):
+                c = self.viewCamera(c)
+                if c is None:
+                    return None
+            cams.append(c)
+        return camera_array(cams)
+
+    def projectLines(self, cams_or_camIDs, near=1e-6):
+        """the 3D lines of the last reconstruct3Dlines as every camera sees them: one PROJECTED_SEGMENT_DTYPE array per
+        camera, ascending segment index (None after an error)"""
+        arr = self._cameras(cams_or_camIDs)
+        if arr is None:
+            return None
+        counts = np.zeros(max(len(arr), 1), np.uint32)
+        if not self._check(self.L.l3d_project_lines(self.h, len(cams_or_camIDs), arr, float(near), ptr(counts)), "projectLines"):
+            return None
+        n = C.c_uint64(0)
+        self.L.l3d_get_projected_lines(self.h, None, 0, C.byref(n))
+        rec = np.zeros(max(n.value, 1), PROJECTED_SEGMENT_DTYPE)
+        self._check(self.L.l3d_get_projected_lines(self.h, ptr(rec), n.value, C.byref(n)), "projectLines")
+        return split_records(rec, counts[:len(cams_or_camIDs)])
+
+    def renderLines(self, cams_or_camIDs, thickness=1, near=1e-6):
+        """-> [(line_id int32 [h, w], inv_depth float32 [h, w])] per camera: the index of the 3D line drawn at a pixel
+        (-1: none; the nearest where lines cross) and its 1 / depth there (None after an error)"""
+        arr = self._cameras(cams_or_camIDs)
+        if arr is None:
+            return None
+        n = len(cams_or_camIDs)
+        ids = [np.empty((arr[i].height, arr[i].width), np.int32) for i in range(n)]
+        izs = [np.empty((arr[i].height, arr[i].width), np.float32) for i in range(n)]
+        if not self._check(self.L.l3d_render_lines(self.h, n, arr, float(near), int(thickness), pointer_array(ids),
+                                                   pointer_array(izs)), "renderLines"):
+            return None
+        return list(zip(ids, izs))
+
+    def drawLines(self, cams_or_camIDs, images, thickness=1, alpha=255, colors=None, near=1e-6):
+        """the 3D lines drawn over `images` (uint8 HxW or HxWx3, one per camera, of the camera's size) -> list of uint8
+        HxWx3.  colors: one RGB triple per 3D line, None: a fixed palette (None after an error)"""
+        arr = self._cameras(cams_or_camIDs)
+        if arr is None:
+            return None
+        n = len(cams_or_camIDs)
+        try:
+            imgs, keep = lsd.image_array(list(images))
+        except TypeError as e:
+            print(f"{self.PREFIX}ERROR: drawLines: {e}")
+            return None
+        if len(keep) != n:
+            print(f"{self.PREFIX}ERROR: drawLines: one image per camera")
+            return None
+        outs = [np.empty((imgs[i].rows, imgs[i].cols, 3), np.uint8) for i in range(n)]
+        col = None if colors is None else np.ascontiguousarray(colors, np.uint8).reshape(-1, 3)
+        nl = C.c_uint32(); ns = C.c_uint32(); nr = C.c_uint32()
+        # l3d_draw_lines reads one triple per 3D line and is not told the table's length: it is checked here
+        if col is not None and not self._check(self.L.l3d_num_3d_lines(self.h, C.byref(nl), C.byref(ns), C.byref(nr)), "drawLines"):
+            return None
+        if col is not None and len(col) < nl.value:
+            print(f"{self.PREFIX}ERROR: drawLines: fewer colors than 3D lines")
+            return None
+        if not self._check(self.L.l3d_draw_lines(self.h, n, arr, imgs, float(near), int(thickness), int(alpha), ptr(col),
+                                                 pointer_array(outs)), "drawLines"):
+            return None
+        return outs
+
+    def set_projection_budget(self, n_bytes):
+        """test hook: device-memory budget of a group of cameras in the three calls above (0: the default)"""
+        self.L.l3d_set_projection_budget(self.h, int(n_bytes))
+
     def set_brute_force(self, on):
         self.L.l3d_set_brute_force(self.h, int(on))
 
@@ -468,6 +549,104 @@ class Line3D:
         t = Timings()
         self.L.l3d_get_timings(self.h, C.byref(t))
         return {f: getattr(t, f) for f, _ in Timings._fields_}
+
+
+def camera_dict(cam):
+    return dict(K=np.array(cam.K[:]).reshape(3, 3), R=np.array(cam.R[:]).reshape(3, 3), t=np.array(cam.t[:]),
+                width=int(cam.width), height=int(cam.height))
+
+
+def camera_array(cams):
+    """cameras as dicts (K, R, t, width, height) or l3d_camera -> ctypes array of l3d_camera"""
+    arr = (_lib.Camera * max(len(cams), 1))()
+    for i, c in enumerate(cams):
+        if isinstance(c, _lib.Camera):
+            arr[i] = c
+            continue
+        arr[i].K[:] = [float(v) for v in np.asarray(c["K"], np.float64).reshape(9)]
+        arr[i].R[:] = [float(v) for v in np.asarray(c["R"], np.float64).reshape(9)]
+        arr[i].t[:] = [float(v) for v in np.asarray(c["t"], np.float64).reshape(3)]
+        arr[i].width, arr[i].height = int(c["width"]), int(c["height"])
+    return arr
+
+
+def pointer_array(arrays):
+    return (C.c_void_p * max(len(arrays), 1))(*[a.ctypes.data for a in arrays])
+
+
+def split_records(rec, counts):
+    out, o = [], 0
+    for c in counts:
+        out.append(rec[o:o + int(c)].copy())
+        o += int(c)
+    return out
+
+
+def project_segments(cams, P1, P2, line_of_segment, near=1e-6, device=0):
+    """l3d_project_segments (stage 1): 3D segments P1, P2 [n, 3] of the lines line_of_segment [n] as the
+    cameras (dicts K, R, t, width, height) see them -> one PROJECTED_SEGMENT_DTYPE array per camera: clipped at the near
+    plane and at the image, ascending segment index"""
+    L = _lib.load()
+    P1 = np.ascontiguousarray(P1, np.float64).reshape(-1, 3); P2 = np.ascontiguousarray(P2, np.float64).reshape(-1, 3)
+    line = np.ascontiguousarray(line_of_segment, np.uint32).reshape(-1)
+    if not len(P1) == len(P2) == len(line):
+        raise ValueError("one P1, P2 and line index per segment")
+    segs = np.zeros(max(len(P1), 1), SEGMENT3D_DTYPE)
+    segs["P1"][:len(P1)] = P1; segs["P2"][:len(P1)] = P2
+    arr = camera_array(list(cams))
+    counts = np.zeros(max(len(cams), 1), np.uint32)
+    n = C.c_uint64(0)
+    args = (int(device), len(cams), arr, len(P1), ptr(segs), ptr(line), float(near), ptr(counts))
+    # one call with room for every (camera, segment) while that is small (64 MiB); beyond it a call for the number first
+    cap = len(cams) * len(P1) if 32 * len(cams) * len(P1) <= (64 << 20) else 0
+    rec = np.zeros(max(cap, 1), PROJECTED_SEGMENT_DTYPE)
+    rc = L.l3d_project_segments(*args, ptr(rec) if cap else None, cap, C.byref(n))
+    if rc == 0 and n.value > cap:
+        rec = np.zeros(n.value, PROJECTED_SEGMENT_DTYPE)
+        rc = L.l3d_project_segments(*args, ptr(rec), n.value, C.byref(n))
+    if rc != 0:
+        raise RuntimeError(f"l3d_project_segments failed [{rc}]: {_lib.last_error()}")
+    return split_records(rec, counts[:len(cams)])
+
+
+def render_line_maps(cams, records, thickness=1, device=0):
+    """l3d_render_line_maps (stage 2): records = one PROJECTED_SEGMENT_DTYPE array per camera (of the cameras, width and
+    height are read) -> [(line_id int32 [h, w], inv_depth float32 [h, w])]"""
+    L = _lib.load()
+    arr = camera_array(list(cams))
+    n = len(cams)
+    if len(records) != n:
+        raise ValueError("one record array per camera")
+    counts = np.array([len(r) for r in records] + [0], np.uint32)
+    rec = np.ascontiguousarray(np.concatenate([np.asarray(r, PROJECTED_SEGMENT_DTYPE).reshape(-1) for r in records] +
+                                              [np.zeros(1, PROJECTED_SEGMENT_DTYPE)]))
+    ids = [np.empty((arr[i].height, arr[i].width), np.int32) for i in range(n)]
+    izs = [np.empty((arr[i].height, arr[i].width), np.float32) for i in range(n)]
+    rc = L.l3d_render_line_maps(int(device), n, arr, ptr(counts), ptr(rec), int(thickness), pointer_array(ids), pointer_array(izs))
+    if rc != 0:
+        raise RuntimeError(f"l3d_render_line_maps failed [{rc}]: {_lib.last_error()}")
+    return list(zip(ids, izs))
+
+
+def draw_line_maps(images, line_ids, alpha=255, colors=None, device=0):
+    """l3d_draw_line_maps (stage 3): images uint8 HxW or HxWx3, line_ids int32 HxW per image -> list of uint8 HxWx3;
+    colors: RGB triples by line index, None: the fixed palette"""
+    L = _lib.load()
+    imgs, keep = lsd.image_array(list(images))
+    n = len(keep)
+    if len(line_ids) != n:
+        raise ValueError("one line-id plane per image")
+    ids = [np.ascontiguousarray(p, np.int32) for p in line_ids]
+    for i in range(n):
+        if ids[i].shape != (imgs[i].rows, imgs[i].cols):
+            raise ValueError(f"line-id plane {i} is not of its image's size")
+    col = None if colors is None else np.ascontiguousarray(colors, np.uint8).reshape(-1, 3)
+    outs = [np.empty((imgs[i].rows, imgs[i].cols, 3), np.uint8) for i in range(n)]
+    rc = L.l3d_draw_line_maps(int(device), n, imgs, pointer_array(ids), 0 if col is None else len(col), ptr(col), int(alpha),
+                              pointer_array(outs))
+    if rc != 0:
+        raise RuntimeError(f"l3d_draw_line_maps failed [{rc}]: {_lib.last_error()}")
+    return outs
 
 
 def match_lines(lines_src, lines_tgt, F, RtKinv_src, RtKinv_tgt, C_src, C_tgt, width, height, epi_overlap=0.25,

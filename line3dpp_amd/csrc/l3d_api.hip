@@ -426,6 +426,7 @@ void l3d_destroy(l3d_ctx* c) {
     c->d_flag.release(); c->d_epos.release(); c->d_first_touch.release(); c->d_touch_flag.release();
     c->d_touch_rank.release(); c->d_edges.release(); c->d_l2g.release();
     c->d_lopt.release(); c->h_lopt.release();
+    c->proj.release();
     for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : c->lo_ev) if (e) (void)hipEventDestroy(e);
     delete c;

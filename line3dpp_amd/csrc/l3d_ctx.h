@@ -114,6 +114,15 @@ int line_opt(::l3d_ctx* c, const std::map<uint32_t, const HostView*>& views, std
 bool line_to_cayley(const d3& P1, const d3& P2, double x[4]);
 bool cayley_to_segment(const double x[4], const d3& P1_old, const d3& P2_old, d3& P1, d3& P2);
 
+// l3d_project.hip: work space of the projection stages, the context's or a stateless call's own
+struct ProjWork {
+    PinnedBuf<char> h;                       // small tables up, camera bounds down
+    DevBuf<char> d;                          // tables, records, planes, images of one group of cameras
+    DevBuf<unsigned long long> keys, scan_ws;   // key planes of the group; k_scan.hip's work space (all-zero between scans)
+    size_t budget = 0;                       // device-memory budget of a group of cameras; 0: l3d_project.hip's kProjBudget
+    void release() { h.release(); d.release(); keys.release(); scan_ws.release(); }
+};
+
 }  // namespace l3d
 
 // shared by l3d_api.hip and l3d_phase_b.hip (C linkage: defined inside their extern "C" blocks)
@@ -298,4 +307,7 @@ struct l3d_ctx {
     std::vector<float> det_segs;
     std::vector<uint32_t> det_counts;
     std::vector<l3d_detect_stats> det_stats;
+    // the last l3d_project_lines (l3d_project.hip): visible records of every camera, camera after camera
+    ProjWork proj;
+    std::vector<l3d_projected_segment> proj_records;
 };

@@ -214,4 +214,46 @@ struct TriArgs {
 constexpr size_t kTriLdsBytes = 32 * 1024;   // projection matrices up to this size (341 cameras) are staged in LDS
 hipError_t launch_triangulate(const TriArgs& t, hipStream_t st);
 
+// ---- k_project.hip: the 3D lines projected into cameras (host side: l3d_project.hip) ----
+struct ProjRecord { float x1, y1, x2, y2, iz1, iz2; uint32_t line, segment; };   // = l3d_projected_segment
+constexpr uint32_t kProjNear = 0x80000000u, kProjRect = 0x40000000u;              // flag bits in ProjRecord::segment
+struct ProjCam { double K[9], R[9], t[3], xmax, ymax; };   // xmax = width - 1, ymax = height - 1
+struct ProjArgs {
+    const ProjCam* cams;      // [n_cams]
+    uint32_t n_cams, n_seg;
+    const double* P;          // [n_seg x 6] P1, P2
+    const uint32_t* line;     // [n_seg]
+    double near_plane;
+    ProjRecord* rec;          // [n_cams x n_seg] the record of (camera, segment), written where visible
+    uint32_t* vis;            // [n_cams x n_seg + 1] 1 where visible; scanned in place by the caller
+    ProjRecord* out;          // [n_cams x n_seg] the visible records, compacted in (camera, segment) order
+    uint32_t* bounds;         // [n_cams + 1] first record of every camera in out; [n_cams] = the number of records
+};
+hipError_t launch_project_lines(const ProjArgs& a, hipStream_t st);     // fills rec and vis
+hipError_t launch_project_compact(const ProjArgs& a, hipStream_t st);   // vis holds its exclusive scan: rec -> out
+// a camera of a group of the map stages: its records, its pixels in the group's planes, its image
+struct MapCam {
+    uint32_t width, height;
+    uint32_t rec0;            // first record of the camera in the group's record array
+    uint32_t img_stride, img_channels, pad;
+    uint64_t pix0;            // first pixel of the camera in the group's planes
+    uint64_t img_off;         // first byte of its source image in the group's image block
+    uint64_t rgb_off;         // first byte of its output image
+};
+struct MapArgs {
+    const MapCam* cams; uint32_t n_cams;
+    const ProjRecord* rec; uint32_t n_rec;
+    uint32_t* steps;                    // [n_rec + 1] major-axis steps per record; scanned in place by the caller
+    uint32_t thickness;
+    unsigned long long* keys;           // [pixels of the group] zeroed by the caller
+    uint64_t n_pix; uint32_t max_pix;   // pixels of the group / of its largest camera
+    int32_t* line_id; float* inv_depth; // [pixels of the group]
+    const uint8_t* img; uint8_t* rgb;   // overlay: source images, packed RGB out
+    const uint8_t* colors; uint32_t n_lines, alpha;
+};
+hipError_t launch_raster_count(const MapArgs& a, hipStream_t st);
+hipError_t launch_raster_lines(const MapArgs& a, uint32_t blocks, hipStream_t st);   // steps holds its exclusive scan
+hipError_t launch_map_decode(const MapArgs& a, hipStream_t st);                      // keys -> line_id, inv_depth
+hipError_t launch_overlay(const MapArgs& a, hipStream_t st);                         // line_id + img -> rgb
+
 }  // namespace l3d
