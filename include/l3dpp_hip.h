@@ -506,6 +506,19 @@ int l3d_decompose_projection_matrix(const double P12[12], double K9[9], double R
  * (single divisions, paired divisions, square roots) -- all zero on a correct build */
 int l3d_selftest_arith(int device, uint64_t n, uint64_t seed, uint64_t counts[3]);
 
+/* test hook (device): the single-launch scan (k_scan.hip) on its own.  in: n_in elements of element_bytes (4: uint32; 8:
+ * two packed 32-bit counters whose totals stay below 2^32).  Call k = 0 .. n_calls-1 scans in[0 .. n[k]) through
+ * launch_scan / launch_scan64: all calls back to back on one stream and ONE work space (zeroed once, when it is
+ * allocated), no host synchronisation between them.  Every call writes n[k] + 1 elements to a region of its own; `out`
+ * receives the regions one after the other (sum of n[k] + 1 elements).  in_place != 0: the input is copied into the region
+ * on the stream and scanned there.  pass_total != 0: the launcher is given a pointer for the total, totals[k] (n_calls
+ * elements) receives what it stored; otherwise the launcher gets NULL and totals may be NULL.  After one
+ * synchronisation: *ws_nonzero = 64-bit words of the work space that are not zero, *guard_changed = how many of the guard
+ * words the hook put behind the work space no longer hold their pattern -- both 0 for a correct scan.
+ * L3D_ERR_ARG before any device call: element_bytes other than 4 or 8, a null pointer, an n[k] above n_in. */
+int l3d_selftest_scan(int device, uint32_t element_bytes, const void* in, uint32_t n_in, uint32_t n_calls, const uint32_t* n,
+                      int in_place, int pass_total, void* out, void* totals, uint64_t* ws_nonzero, uint64_t* guard_changed);
+
 /* test hook: route every segment pair through the exact double-precision test (no fp32 pre-filter);
  * used by the tests to prove that the pre-filter never loses a match */
 int l3d_set_brute_force(l3d_ctx*, int on);

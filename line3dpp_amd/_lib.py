@@ -145,7 +145,7 @@ EXPORTS = [
     "l3d_undistort_images_model", "l3d_sfm_get_camera_model", "l3d_sfm_get_camera_params",
     "l3d_triangulate_points", "l3d_rotation_from_rpy", "l3d_rotation_from_q", "l3d_decompose_projection_matrix",
     "l3d_project_segments", "l3d_render_line_maps", "l3d_draw_line_maps", "l3d_view_camera", "l3d_project_lines",
-    "l3d_get_projected_lines", "l3d_render_lines", "l3d_draw_lines", "l3d_set_projection_budget",
+    "l3d_get_projected_lines", "l3d_render_lines", "l3d_draw_lines", "l3d_set_projection_budget", "l3d_selftest_scan",
 ]
 
 _lib = None
@@ -243,6 +243,7 @@ def load():
     L.l3d_cayley_to_segment.argtypes = [vp, vp, vp, vp, vp]
     L.l3d_line_opt_eval.argtypes = [i32, u32, vp, vp, vp, vp, vp, vp, vp]
     L.l3d_selftest_arith.argtypes = [i32, u64, u64, vp]
+    L.l3d_selftest_scan.argtypes = [i32, u32, vp, u32, u32, vp, i32, i32, vp, vp, C.POINTER(u64), C.POINTER(u64)]
     L.l3d_detect_segments.argtypes = [vp, u32, vp, i32, u32, vp]
     L.l3d_detect_view_segments.argtypes = [vp, u32, vp, vp, C.POINTER(DetectOptions), vp]
     L.l3d_get_detected_segments.argtypes = [vp, vp, u64, C.POINTER(u64)]

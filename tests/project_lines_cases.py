@@ -1,5 +1,7 @@
 """Inputs shared by the tests of the projection stages: the cameras and 3D segments that take every branch of
 stage 1, the records that take every branch of stage 2, and the sanity property of the context forms."""
+import functools
+
 import numpy as np
 
 from tests import project_lines_model as M
@@ -104,6 +106,99 @@ def stage2_records(width, height, seed):
         z = rng.choice([0.125, 0.25, 0.5, 1.0], 2) if k % 3 == 0 else rng.uniform(0.05, 2.0, 2)
         r.append(rec(a[0], a[1], b[0], b[1], z[0], z[1], 23 + k % 41, k))
     return np.array(r, M.RECORD_DTYPE)
+
+
+def stage2_multi_camera():
+    """three cameras of different sizes with records and a fourth without -> (cameras, one record array per camera)"""
+    sizes = [(200, 75), (97, 61), (33, 130)]
+    cams = [dict(K=np.eye(3), R=np.eye(3), t=np.zeros(3), width=w, height=h) for w, h in sizes]
+    recs = [stage2_records(200, 75, 5), stage2_records(97, 61, 6), stage2_records(97, 61, 7)[23:]]
+    recs[2]["x1"] *= 0.3; recs[2]["x2"] *= 0.3; recs[2]["y1"] *= 2.1; recs[2]["y2"] *= 2.1
+    recs.append(recs[0][:0])                                       # a camera without records
+    cams.append(dict(cams[1]))
+    return cams, recs
+
+
+# ---- the large cases: past one scan tile (4096 elements) and past one grid (2048 blocks of 256 lanes) -------------------
+STAGE1_LARGE_EMPTY = (0, 33, 69)
+
+
+@functools.lru_cache(maxsize=None)
+def stage1_large():
+    """70 cameras x 4001 segments = 280 070 visibility flags: 69 scan tiles of 4096, so the compaction reads offsets of
+    tiles whose look-back needs a second window of 64 predecessors (tile index 65 and up); 4001 is no multiple of 256 or
+    4096, so cameras begin inside blocks and tiles.  The cameras cycle through the four of stage1_cameras() with t
+    perturbed by N(0, 0.05); cameras 0, 33 and 69 look away from the scene and see nothing (an empty camera at the front,
+    in the middle and at the end of a group).  Segments: the random recipe of stage1_segments(), seed 20261019.
+    The model gives (tests assert the conditions, not the figures): STAGE1_LARGE_FIGURES below.
+    -> (cameras, P1 [4001, 3], P2 [4001, 3], line_of_segment [4001]); shared between tests, not to be modified"""
+    rng = np.random.default_rng(20261019)
+    n = 4001
+    c = rng.uniform(-1.5, 1.5, (n, 3)) + [0, 0, 2.0]
+    d = rng.normal(size=(n, 3)) * rng.uniform(0.05, 2.0, (n, 1))
+    P1, P2 = c - d, c + d
+    line = (np.arange(n) * 7 // 3).astype(np.uint32)
+    base = stage1_cameras()
+    cams = []
+    for k in range(70):
+        cam = dict(base[k % 4])
+        cam["t"] = np.asarray(cam["t"], np.float64) + rng.normal(0.0, 0.05, 3)
+        if k in STAGE1_LARGE_EMPTY:
+            cam["R"] = rot(np.pi, 0, 0) @ np.asarray(cam["R"], np.float64)
+            cam["t"] = np.array([0.0, 0.0, -10.0])
+        cams.append(cam)
+    for a in (P1, P2, line):
+        a.setflags(write=False)
+    return cams, P1, P2, line
+
+
+# what tests/project_lines_model_vec.py gives for stage1_large() (CPU): visible share of the 280 070 (camera, segment)
+# pairs, fewest and most records of a camera that is not empty, records with each clip flag
+STAGE1_LARGE_FIGURES = dict(visible_share=0.5521, min_records=762, max_records=3812, clipped_near=10414, clipped_rect=120249)
+
+
+def stage2_large_records(width, height, n, seed):
+    """n records for a width x height image: centres uniform in the image, half-lengths N(0, 1)^2 * one of 0.4 / 3 / 40 /
+    300 pixels, clipped to the image and rounded to float32; every third record has inverse depths from {1/8, 1/4, 1/2, 1}
+    so that equal depths meet; line ids k % 997.  Records 0, n/2 - 1 .. n/2 + 1 and n - 1 are shorter than a pixel and lie
+    between integer coordinates (no step: a record without steps first, last and in a run of three); records 10 and 11
+    cross at (x, y) = (0.4 w, 0.5 h) at the same depth, nearer than every random record."""
+    w1, h1 = width - 1, height - 1
+    rng = np.random.default_rng(seed)
+    r = []
+    for k in range(n):
+        c = rng.uniform([0, 0], [w1, h1])
+        d = rng.normal(size=2) * rng.choice([0.4, 3.0, 40.0, 300.0])
+        a, b = np.clip(c - d, 0, [w1, h1]), np.clip(c + d, 0, [w1, h1])
+        z = rng.choice([0.125, 0.25, 0.5, 1.0], 2) if k % 3 == 0 else rng.uniform(0.05, 2.0, 2)
+        r.append(rec(a[0], a[1], b[0], b[1], z[0], z[1], k % 997, k))
+    for k in (0, n // 2 - 1, n // 2, n // 2 + 1, n - 1):
+        x, y = float(int(0.3 * w1)) + 0.25, float(int(0.7 * h1)) + 0.25
+        r[k] = rec(x, y, x + 0.5, y + 0.25, 1.0, 1.0, k % 997, k)
+    cx, cy = float(int(0.4 * width)), float(int(0.5 * height))
+    r[10] = rec(cx - 0.25 * cy, cy, cx + 0.25 * cy, cy, 4.0, 4.0, 10, 10)
+    r[11] = rec(cx, 0.5 * cy, cx, 1.5 * cy, 4.0, 4.0, 11, 11)
+    return np.array(r, M.RECORD_DTYPE)
+
+
+@functools.lru_cache(maxsize=None)
+def stage2_large(seed=7):
+    """Three cameras in one call: 33 x 130 WITHOUT records (a leading empty camera: two cameras share rec0 = 0), 1100 x 500
+    with 6000 records of stage2_large_records (550 000 pixels: the per-pixel kernels stride past their 2048 x 256 lanes;
+    two scan tiles of records; more than 524 288 major-axis steps: the work-item loop strides), 97 x 61 with
+    stage2_records(97, 61, seed).  The model gives: STAGE2_LARGE_FIGURES below.
+    -> (cameras, one record array per camera); shared between tests, not to be modified"""
+    sizes = [(33, 130), (1100, 500), (97, 61)]
+    cams = [dict(K=np.eye(3), R=np.eye(3), t=np.zeros(3), width=w, height=h) for w, h in sizes]
+    recs = [np.zeros(0, M.RECORD_DTYPE), stage2_large_records(1100, 500, 6000, seed), stage2_records(97, 61, seed)]
+    for a in recs:
+        a.setflags(write=False)
+    return cams, recs
+
+
+# what the model gives for the 1100 x 500 camera of stage2_large(7) (CPU): major-axis steps, records without steps, the
+# longest run of them, the longest record, pixels where the winner ties in depth with another line (thickness 1)
+STAGE2_LARGE_FIGURES = dict(steps=854157, zero_step_records=384, longest_zero_run=4, longest_record=1100, tie_pixels=353)
 
 
 # The sanity property of the context forms on the golden scene, taken on the CPU first

@@ -1,5 +1,6 @@
 """The 3D lines projected into cameras on the MI355X (k_project.hip, l3d_project.hip): the three stages
-against the numpy model of tests/project_lines_model.py with tolerance 0, the context forms on the golden scene against
+against the numpy model of tests/project_lines_model.py with tolerance 0 (past one scan tile and one grid: against its
+array form, tests/project_lines_model_vec.py), the context forms on the golden scene against
 the stateless forms and the model, the argument checks, and the C++ facade."""
 import ctypes as C
 import os
@@ -13,6 +14,7 @@ from line3dpp_amd import _lib, api
 from line3dpp_amd.api import Line3D
 from tests import project_lines_cases as Cs
 from tests import project_lines_model as M
+from tests import project_lines_model_vec as V
 
 pytestmark = pytest.mark.gpu
 
@@ -103,12 +105,7 @@ def test_stage2_equals_the_model(width, height, thickness):
 
 
 def test_stage2_cameras_share_launches_and_order_does_not_matter():
-    sizes = [(200, 75), (97, 61), (33, 130)]
-    cams = [dict(K=np.eye(3), R=np.eye(3), t=np.zeros(3), width=w, height=h) for w, h in sizes]
-    recs = [Cs.stage2_records(200, 75, 5), Cs.stage2_records(97, 61, 6), Cs.stage2_records(97, 61, 7)[23:]]
-    recs[2]["x1"] *= 0.3; recs[2]["x2"] *= 0.3; recs[2]["y1"] *= 2.1; recs[2]["y2"] *= 2.1
-    recs.append(recs[0][:0])                                       # a camera without records
-    cams.append(dict(cams[1]))
+    cams, recs = Cs.stage2_multi_camera()                          # (the fourth camera has no records)
     got = api.render_line_maps(cams, recs, 3)
     for k in range(4):
         want = M.render_line_maps(recs[k], cams[k]["width"], cams[k]["height"], 3)
@@ -133,6 +130,100 @@ def test_stage3_equals_the_model(alpha):
             want = M.draw_line_map(img, ids[k], alpha, colors)
             assert got[k].shape == want.shape and np.array_equal(got[k], want), f"image {k}, colors {'table' if colors is not None else 'palette'}"
     assert api.draw_line_maps([], [], alpha) == []
+
+
+# ---- past one scan tile and one grid: the large cases against the array form of the model --------------------------------
+# (tests/project_lines_model_vec.py, shown byte-identical to the loop model by tests/test_project_host.py)
+@pytest.fixture(scope="module")
+def large1():
+    cams, P1, P2, line = Cs.stage1_large()
+    return dict(cams=cams, P1=P1, P2=P2, line=line, want=V.project_segments(cams, P1, P2, line))
+
+
+def test_stage1_large_crosses_scan_tiles_and_look_back_windows(large1):
+    """70 cameras x 4001 segments: the flags fill 69 scan tiles, cameras begin inside tiles, three cameras see nothing."""
+    G = large1
+    cams, want = G["cams"], G["want"]
+    counts = np.array([len(r) for r in want])
+    flags = np.concatenate([r["segment"] for r in want]) & ~np.uint32(M.SEGMENT_MASK)
+    n_flags = len(cams) * len(G["P1"])
+    share = counts.sum() / n_flags
+    print(f"stage1_large: {n_flags} flags = {-(-n_flags // 4096)} scan tiles, visible share {share:.4f}, records per non-empty camera "
+          f"{counts[counts > 0].min()} .. {counts.max()}, clipped near {int(((flags & M.CLIPPED_NEAR) != 0).sum())}, "
+          f"clipped at the rectangle {int(((flags & M.CLIPPED_RECT) != 0).sum())}")
+    # conditions on the input
+    assert n_flags > 65 * 4096 + 1 and len(G["P1"]) % 256 and len(G["P1"]) % 4096
+    assert tuple(np.flatnonzero(counts == 0)) == Cs.STAGE1_LARGE_EMPTY
+    assert 0.3 <= share <= 0.8
+    assert counts[counts > 0].min() >= 500
+    assert ((flags & M.CLIPPED_NEAR) != 0).any() and ((flags & M.CLIPPED_RECT) != 0).any()
+    got = api.project_segments(cams, G["P1"], G["P2"], G["line"])
+    assert [len(r) for r in got] == list(counts)
+    for c in range(len(cams)):
+        same_records(got[c], want[c], f"camera {c}")
+    # grouping changes nothing; the slices begin with an empty camera, are one, and end with one
+    for a, b in ((0, 23), (23, 24), (24, 70), (33, 34), (33, 36)):
+        part = api.project_segments(cams[a:b], G["P1"], G["P2"], G["line"])
+        assert sum(len(r) for r in part) == counts[a:b].sum(), f"cameras {a}:{b}: total"
+        for c in range(a, b):
+            same_records(part[c - a], want[c], f"camera {c} in the slice {a}:{b}")
+
+
+@pytest.fixture(scope="module")
+def large2():
+    cams, recs = Cs.stage2_large()
+    want = {t: [V.render_line_maps(recs[k], cams[k]["width"], cams[k]["height"], t) for k in range(3)] for t in (1, 3)}
+    return dict(cams=cams, recs=recs, want=want)
+
+
+def test_stage2_large_input_conditions(large2):
+    cams, recs = large2["cams"], large2["recs"]
+    w, h = cams[1]["width"], cams[1]["height"]
+    count, _ = V.raster_steps(recs[1], w, h)
+    zero = np.concatenate([[0], (count == 0).astype(np.int64), [0]])
+    edges = np.flatnonzero(np.diff(zero))
+    longest_run = int((edges[1::2] - edges[0::2]).max())
+    pix, key = V.record_keys(recs[1], w, h, 1)
+    winner = V.key_plane(recs[1], w, h, 1)[pix]
+    tie = ((key >> np.uint64(32)) == (winner >> np.uint64(32))) & (key < winner)     # same depth, the larger line index lost
+    print(f"stage2_large: {w * h} pixels, {len(recs[1])} records = {-(-len(recs[1]) // 4096)} scan tiles, {int(count.sum())} steps, "
+          f"{int((count == 0).sum())} records without steps (longest run {longest_run}), longest record {int(count.max())} steps, "
+          f"{len(np.unique(pix[tie]))} pixels with a tie in depth")
+    assert len(recs[0]) == 0 and w * h > 524288 and len(recs[1]) > 4096
+    assert count.sum() > 524288
+    assert (count == 0).sum() >= 100 and longest_run >= 3 and count[0] == 0 and count[-1] == 0
+    assert tie.any()
+    assert (0xFFFFFFFF - (winner[tie] & np.uint64(0xFFFFFFFF)) < 0xFFFFFFFF - (key[tie] & np.uint64(0xFFFFFFFF))).all()
+
+
+@pytest.mark.parametrize("thickness", [1, 3])
+def test_stage2_large_strides_the_grid_and_starts_with_an_empty_camera(large2, thickness):
+    cams, recs, want = large2["cams"], large2["recs"], large2["want"][thickness]
+    got = api.render_line_maps(cams, recs, thickness)
+    for k in range(3):
+        assert np.array_equal(got[k][0], want[k][0]), f"camera {k}: {(got[k][0] != want[k][0]).sum()} pixels with another line"
+        assert np.array_equal(got[k][1].view(np.uint32), want[k][1].view(np.uint32)), f"camera {k}: inverse depths"
+    assert (got[0][0] == -1).all() and not got[0][1].view(np.uint32).any()
+    assert (want[1][0] >= 0).sum() > 300000 and (want[2][0] >= 0).sum() > 1000
+    back = api.render_line_maps(cams, [recs[0], recs[1][::-1].copy(), recs[2]], thickness)
+    for k in range(3):
+        assert np.array_equal(back[k][0], got[k][0]) and np.array_equal(back[k][1].view(np.uint32), got[k][1].view(np.uint32)), f"camera {k}: reversed"
+
+
+def test_stage3_large_strides_the_grid(large2):
+    ids = [w[0] for w in large2["want"][3]]
+    rng = np.random.default_rng(12)
+    imgs = [rng.integers(0, 256, (130, 64), np.uint8)[:, :33],                      # grey, padded stride
+            rng.integers(0, 256, (500, 1111, 3), np.uint8)[:, :1100],              # RGB, padded stride
+            rng.integers(0, 256, (61, 97), np.uint8)]                               # grey, contiguous
+    assert not imgs[0].flags["C_CONTIGUOUS"] and not imgs[1].flags["C_CONTIGUOUS"] and imgs[2].flags["C_CONTIGUOUS"]
+    table = rng.integers(0, 256, (40, 3), np.uint8)                                 # shorter than the ids: the rest take the palette
+    assert max(int(p.max()) for p in ids) >= 40 and (ids[0] == -1).all()
+    got = api.draw_line_maps(imgs, ids, 128, table)
+    for k in range(3):
+        want = V.draw_line_map(imgs[k], ids[k], 128, table)
+        assert got[k].shape == want.shape and np.array_equal(got[k], want), f"image {k}"
+    assert np.array_equal(got[0], np.repeat(imgs[0][:, :, None], 3, 2))
 
 
 # ---- the context forms on the golden scene ----------------------------------------------------------------------------

@@ -1,5 +1,6 @@
 """CPU tests of the projection stages: the numpy model's own properties, the layout of the two new structs
-and the new symbols of the built library.  No device call is made here."""
+and the new symbols of the built library, and the array forms of the model (tests/project_lines_model_vec.py) against
+its loops, byte for byte.  No device call is made here."""
 import ctypes as C
 
 import numpy as np
@@ -7,6 +8,7 @@ import numpy as np
 from line3dpp_amd import _lib
 from tests import project_lines_cases as Cs
 from tests import project_lines_model as M
+from tests import project_lines_model_vec as V
 
 NEW_SYMBOLS = ["l3d_project_segments", "l3d_render_line_maps", "l3d_draw_line_maps", "l3d_view_camera", "l3d_project_lines",
                "l3d_get_projected_lines", "l3d_render_lines", "l3d_draw_lines", "l3d_set_projection_budget"]
@@ -163,3 +165,93 @@ def test_palette_and_blend():
     rgb = np.arange(12, dtype=np.uint8).reshape(2, 2, 3)
     assert np.array_equal(M.draw_line_map(rgb, np.full((2, 2), -1, np.int32)), rgb)
     assert M.draw_line_map(rgb, ids, 0).tolist() == rgb.tolist()                                  # alpha 0 changes nothing
+
+
+# ---- the vectorised model (tests/project_lines_model_vec.py) is the loop model, byte for byte ---------------------------
+def same_bytes(got, want, what):
+    assert got.dtype == want.dtype and got.shape == want.shape, what
+    assert got.tobytes() == want.tobytes(), what
+
+
+def same_planes(records, width, height, thickness, what):
+    want = M.render_line_maps(records, width, height, thickness)
+    got = V.render_line_maps(records, width, height, thickness)
+    same_bytes(got[0], want[0], f"{what}: line ids")
+    same_bytes(got[1], want[1], f"{what}: inverse depths")
+    return want
+
+
+def test_vectorised_stage1_equals_the_loop_model_on_the_existing_cases():
+    cams = Cs.stage1_cameras()
+    P1, P2, line = Cs.stage1_segments()
+    flat = dict(cams[0]); flat["K"] = np.array(cams[0]["K"], np.float64).copy(); flat["K"][2] = 0.0
+    for what, cam_list, near in (("the four cameras", cams, 1e-6), ("near = 0.75", cams[:1], 0.75), ("flat K", [flat, cams[1]], 1e-6),
+                                 ("near = 1e-45", cams[:1], 1e-45)):
+        want = M.project_segments(cam_list, P1, P2, line, near=near)
+        got = V.project_segments(cam_list, P1, P2, line, near=near)
+        for c in range(len(cam_list)):
+            same_bytes(got[c], want[c], f"{what}, camera {c}")
+    assert len(V.project_segments([flat], P1, P2, line)[0]) == 0
+    assert len(V.project_segments(cams, P1[:0], P2[:0], line[:0])[2]) == 0
+
+
+def test_vectorised_stage1_equals_the_loop_model_on_a_sample_of_the_large_case():
+    cams, P1, P2, line = Cs.stage1_large()
+    pick = np.arange(5, 4001, 11)                      # 364 segments
+    assert len(pick) >= 300
+    seen = 0
+    for c in (5, 6, 7, 33, 34):                        # one of each of the four kinds and an empty one
+        want = M.project_segments([cams[c]], P1[pick], P2[pick], line[pick])[0]
+        same_bytes(V.project_segments([cams[c]], P1[pick], P2[pick], line[pick])[0], want, f"camera {c}")
+        seen += len(want)
+        # the sample's records are the sampled records of the whole camera: rows of the array form do not see each other
+        whole = V.project_camera(cams[c], P1, P2, line)
+        part = whole[np.isin(whole["segment"] & M.SEGMENT_MASK, pick)].copy()
+        part["segment"] = (part["segment"] & ~np.uint32(M.SEGMENT_MASK)) | np.searchsorted(pick, part["segment"] & M.SEGMENT_MASK).astype(np.uint32)
+        same_bytes(part, want, f"camera {c}: sample of the whole")
+    assert seen > 500
+
+
+def test_vectorised_stage2_equals_the_loop_model_on_the_existing_cases():
+    for width, height in ((200, 75), (97, 61)):
+        rec = Cs.stage2_records(width, height, seed=width)
+        for thickness in (1, 3):
+            want = same_planes(rec, width, height, thickness, f"{width} x {height}, thickness {thickness}")
+            assert (want[0] >= 0).sum() > 1500
+    cams, recs = Cs.stage2_multi_camera()
+    for k in range(4):
+        want = same_planes(recs[k], cams[k]["width"], cams[k]["height"], 3, f"camera {k} of four")
+    assert (want[0] == -1).all() and not want[1].any()                               # the camera without records
+    rec = Cs.stage2_records(40, 29, seed=3)                                          # coordinates outside the image
+    same_planes(rec, 40, 29, 3, "records of a larger image")
+
+
+def test_vectorised_stage2_equals_the_loop_model_on_the_large_recipe():
+    crop = Cs.stage2_large_records(200, 75, 400, seed=7)
+    for thickness in (1, 3):
+        want = same_planes(crop, 200, 75, thickness, f"200 x 75 by the large recipe, thickness {thickness}")
+        assert (want[0] >= 0).sum() > 3000
+    assert want[0][37, 80] == 10                                                     # the hand-made tie: the smaller id
+    cams, recs = Cs.stage2_large()
+    sample = recs[1][3::20]                                                          # 300 of the 6000 records at 1100 x 500
+    assert len(sample) == 300
+    for thickness in (1, 3):
+        want = same_planes(sample, 1100, 500, thickness, f"sample at 1100 x 500, thickness {thickness}")
+    assert (want[0] >= 0).sum() > 20000
+    count, _ = V.raster_steps(sample, 1100, 500)
+    assert count.sum() == sum(len(M.record_pixels(r, 1100, 500)) for r in sample) and (count == 0).sum() > 5 and count.max() > 500
+
+
+def test_vectorised_stage3_equals_the_loop_model():
+    rng = np.random.default_rng(11)
+    ids = [M.render_line_maps(Cs.stage2_records(97, 61, 8), 97, 61, 3)[0], M.render_line_maps(Cs.stage2_records(200, 75, 9), 200, 75, 1)[0],
+           V.render_line_maps(Cs.stage2_large_records(200, 75, 400, 7), 200, 75, 3)[0]]
+    imgs = [rng.integers(0, 256, (61, 128), np.uint8)[:, :97], rng.integers(0, 256, (75, 211, 3), np.uint8)[:, :200],
+            rng.integers(0, 256, (75, 200), np.uint8)]
+    table = rng.integers(0, 256, (40, 3), np.uint8)
+    for alpha in (255, 128, 0):
+        for colors in (None, table):
+            for k in range(3):
+                same_bytes(V.draw_line_map(imgs[k], ids[k], alpha, colors), M.draw_line_map(imgs[k], ids[k], alpha, colors),
+                           f"image {k}, alpha {alpha}, colors {'table' if colors is not None else 'palette'}")
+    assert (ids[2] >= 40).any() and (ids[2] >= 0).any() and (ids[2] < 40).any()
