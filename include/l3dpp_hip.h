@@ -566,7 +566,9 @@ int l3d_set_timing_level(l3d_ctx*, int level);
  * whose segments came from the segment cache; "seam_support_wave_lists", "seam_support_group_staged_lists",
  * "seam_support_sort_only_lists", "seam_support_all_pairs_lists": lists l3d_score_matches sent down each of the four paths
  * of its support kernel (by list length; empty lists are not counted), "seam_score_unstaged_lists": lists it scored on the
- * unstaged path of the scoring kernel.  Unknown name: ~0. */
+ * unstaged path of the scoring kernel; "live_device_blocks", "live_pinned_blocks": blocks of device / pinned host memory
+ * the library's buffers hold right now (blocks lying in its cache are not counted): equal before and after a stateless
+ * call, and before l3d_create and after l3d_destroy.  Unknown name: ~0. */
 unsigned long long l3d_debug_counter(const char* name);
 
 /* ---- (2) seam layer ------------------------------------------------------------------ */

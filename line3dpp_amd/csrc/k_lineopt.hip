@@ -192,7 +192,7 @@ hipError_t launch_lineopt(const LoArgs& a, hipStream_t st) {
 extern "C" int l3d_line_opt_eval(int device, uint32_t n, const double x[4], const double* obs, const double* cams,
                                  double* cost, double* residuals, double* jacobians, int32_t* ok) {
     if (!x || !obs || !cams || !cost || !residuals || !jacobians || !ok || !n) return fail(L3D_ERR_ARG, "null argument");
-    if (hipSetDevice(device) != hipSuccess) return fail(L3D_ERR_HIP, "hipSetDevice failed: no usable HIP device");
+    if (int rc = set_device(device)) return rc;
     std::vector<LoCam> hc(n);
     std::vector<LoObs> ho(n);
     for (uint32_t i = 0; i < n; ++i) {
@@ -204,8 +204,9 @@ extern "C" int l3d_line_opt_eval(int device, uint32_t n, const double x[4], cons
         ho[i] = LoObs{o[0], o[1], o[2], o[3], o[4], o[5], i, 0};
     }
     const size_t b_c = n * sizeof(LoCam), b_o = n * sizeof(LoObs), b_r = 2 * (size_t)n * 8, b_j = 8 * (size_t)n * 8, b_h = (size_t)n * 8;
-    char* d = nullptr;
-    L3D_HIP_CHECK(hipMalloc((void**)&d, 32 + b_c + b_o + b_r + b_j + b_h + 4 * (size_t)n));
+    DevBuf<char> buf;
+    L3D_HIP_CHECK(buf.reserve(32 + b_c + b_o + b_r + b_j + b_h + 4 * (size_t)n));
+    char* d = buf.p;
     double* dx = (double*)d;
     LoCam* dc = (LoCam*)(d + 32);
     LoObs* dob = (LoObs*)(d + 32 + b_c);
@@ -225,7 +226,6 @@ extern "C" int l3d_line_opt_eval(int device, uint32_t n, const double x[4], cons
     if (e == hipSuccess) e = hipMemcpy(jacobians, dj, b_j, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(rho.data(), dh, b_h, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(ok, dk, 4 * (size_t)n, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
     if (e != hipSuccess) return fail(L3D_ERR_HIP, std::string("l3d_line_opt_eval: ") + hipGetErrorString(e));
     double s = 0.0;
     for (uint32_t i = 0; i < n; ++i) s += rho[i];

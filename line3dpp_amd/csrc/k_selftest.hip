@@ -53,15 +53,15 @@ __global__ void k_selftest_arith(uint64_t n, uint64_t seed, unsigned long long* 
 // counts[3]: single divisions, paired divisions (shared reciprocal), square roots whose bits differ from the compiler's
 extern "C" int l3d_selftest_arith(int device, uint64_t n, uint64_t seed, uint64_t counts[3]) {
     if (!counts) return fail(L3D_ERR_ARG, "null argument");
-    if (hipSetDevice(device) != hipSuccess) return fail(L3D_ERR_HIP, "hipSetDevice failed: no usable HIP device");
-    unsigned long long* d = nullptr;
-    L3D_HIP_CHECK(hipMalloc((void**)&d, 24));
+    if (int rc = set_device(device)) return rc;
+    l3d::DevBuf<unsigned long long> buf;
+    L3D_HIP_CHECK(buf.reserve(3));
+    unsigned long long* d = buf.p;
     L3D_HIP_CHECK(hipMemset(d, 0, 24));
     hipLaunchKernelGGL(l3d::k_selftest_arith, dim3(2048), dim3(256), 0, 0, n, seed, d);
     L3D_HIP_CHECK(hipGetLastError());
     unsigned long long h[3];
     L3D_HIP_CHECK(hipMemcpy(h, d, 24, hipMemcpyDeviceToHost));
-    (void)hipFree(d);
     counts[0] = h[0]; counts[1] = h[1]; counts[2] = h[2];
     return L3D_OK;
 }
@@ -84,38 +84,33 @@ extern "C" int l3d_selftest_scan(int device, uint32_t element_bytes, const void*
     }
     *ws_nonzero = 0; *guard_changed = 0;
     if (!n_calls) return L3D_OK;
-    if (hipSetDevice(device) != hipSuccess) return fail(L3D_ERR_HIP, "hipSetDevice failed: no usable HIP device");
+    if (int rc = set_device(device)) return rc;
     const size_t eb = element_bytes, words = l3d::scan_ws_words(n_max, element_bytes);
     l3d::DevBuf<char> d_in, d_out, d_tot; l3d::DevBuf<unsigned long long> ws;
     std::vector<unsigned long long> h_ws(words + kGuard, kPattern);
-    const int rc = [&]() -> int {
-        L3D_HIP_CHECK(d_in.reserve(std::max<size_t>(1, n_in) * eb)); L3D_HIP_CHECK(d_out.reserve(n_out * eb));
-        L3D_HIP_CHECK(d_tot.reserve((size_t)n_calls * eb));
-        L3D_HIP_CHECK(ws.reserve_zeroed(words + kGuard, 0));
-        L3D_HIP_CHECK(hipMemcpy(ws.p + words, h_ws.data(), kGuard * 8, hipMemcpyHostToDevice));
-        if (n_in) L3D_HIP_CHECK(hipMemcpy(d_in.p, in, (size_t)n_in * eb, hipMemcpyHostToDevice));
-        L3D_HIP_CHECK(hipMemset(d_out.p, 0xEE, n_out * eb)); L3D_HIP_CHECK(hipMemset(d_tot.p, 0xEE, (size_t)n_calls * eb));
-        size_t at = 0;
-        for (uint32_t k = 0; k < n_calls; at += (size_t)n[k] + 1, ++k) {
-            char* o = d_out.p + at * eb; char* t = pass_total ? d_tot.p + (size_t)k * eb : nullptr;
-            const char* src = d_in.p;
-            if (in_place) {
-                if (n[k]) L3D_HIP_CHECK(hipMemcpyAsync(o, d_in.p, (size_t)n[k] * eb, hipMemcpyDeviceToDevice, 0));
-                src = o;
-            }
-            if (element_bytes == 4)
-                L3D_HIP_CHECK(l3d::launch_scan((const uint32_t*)src, n[k], (uint32_t*)o, ws.p, (uint32_t*)t, 0));
-            else
-                L3D_HIP_CHECK(l3d::launch_scan64((const unsigned long long*)src, n[k], (unsigned long long*)o, ws.p, (unsigned long long*)t, 0));
+    L3D_HIP_CHECK(d_in.reserve(std::max<size_t>(1, n_in) * eb)); L3D_HIP_CHECK(d_out.reserve(n_out * eb));
+    L3D_HIP_CHECK(d_tot.reserve((size_t)n_calls * eb));
+    L3D_HIP_CHECK(ws.reserve_zeroed(words + kGuard, 0));
+    L3D_HIP_CHECK(hipMemcpy(ws.p + words, h_ws.data(), kGuard * 8, hipMemcpyHostToDevice));
+    if (n_in) L3D_HIP_CHECK(hipMemcpy(d_in.p, in, (size_t)n_in * eb, hipMemcpyHostToDevice));
+    L3D_HIP_CHECK(hipMemset(d_out.p, 0xEE, n_out * eb)); L3D_HIP_CHECK(hipMemset(d_tot.p, 0xEE, (size_t)n_calls * eb));
+    size_t at = 0;
+    for (uint32_t k = 0; k < n_calls; at += (size_t)n[k] + 1, ++k) {
+        char* o = d_out.p + at * eb; char* t = pass_total ? d_tot.p + (size_t)k * eb : nullptr;
+        const char* src = d_in.p;
+        if (in_place) {
+            if (n[k]) L3D_HIP_CHECK(hipMemcpyAsync(o, d_in.p, (size_t)n[k] * eb, hipMemcpyDeviceToDevice, 0));
+            src = o;
         }
-        L3D_HIP_CHECK(hipDeviceSynchronize());
-        L3D_HIP_CHECK(hipMemcpy(out, d_out.p, n_out * eb, hipMemcpyDeviceToHost));
-        if (pass_total) L3D_HIP_CHECK(hipMemcpy(totals, d_tot.p, (size_t)n_calls * eb, hipMemcpyDeviceToHost));
-        L3D_HIP_CHECK(hipMemcpy(h_ws.data(), ws.p, (words + kGuard) * 8, hipMemcpyDeviceToHost));
-        return L3D_OK;
-    }();
-    d_in.release(); d_out.release(); d_tot.release(); ws.release();
-    if (rc != L3D_OK) return rc;
+        if (element_bytes == 4)
+            L3D_HIP_CHECK(l3d::launch_scan((const uint32_t*)src, n[k], (uint32_t*)o, ws.p, (uint32_t*)t, 0));
+        else
+            L3D_HIP_CHECK(l3d::launch_scan64((const unsigned long long*)src, n[k], (unsigned long long*)o, ws.p, (unsigned long long*)t, 0));
+    }
+    L3D_HIP_CHECK(hipDeviceSynchronize());
+    L3D_HIP_CHECK(hipMemcpy(out, d_out.p, n_out * eb, hipMemcpyDeviceToHost));
+    if (pass_total) L3D_HIP_CHECK(hipMemcpy(totals, d_tot.p, (size_t)n_calls * eb, hipMemcpyDeviceToHost));
+    L3D_HIP_CHECK(hipMemcpy(h_ws.data(), ws.p, (words + kGuard) * 8, hipMemcpyDeviceToHost));
     for (size_t i = 0; i < words; ++i) *ws_nonzero += h_ws[i] != 0;
     for (size_t i = 0; i < kGuard; ++i) *guard_changed += h_ws[words + i] != kPattern;
     return L3D_OK;

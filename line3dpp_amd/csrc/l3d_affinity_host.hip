@@ -245,10 +245,8 @@ int l3d_compute_affinity(l3d_ctx* c) {
     if (c->aff_shard_open) return fail(L3D_ERR_STATE, "a sharded affinity fill is open: l3d_affinity_shard_finish (or _abort) first");
     // translate()/untranslate() (line3D.cc:1749,1820) only move camera centres, which the affinity terms never
     // read; they are applied to keep the host state identical to the reference's.
-    translate(*c);
-    const int rc = affinity_core(c);
-    untranslate(*c);
-    return rc;
+    const Translated frame(*c);
+    return affinity_core(c);
 }
 
 // ---- the affinity fill sharded by views (N > 1 ranks; SURVEY.md 8e "Affinity": independent per hypothesis) ----------------
@@ -267,16 +265,17 @@ int l3d_affinity_shard_begin(l3d_ctx* c, uint32_t rank, uint32_t world, void** s
         return fail(L3D_ERR_STATE, "l3d_affinity_shard_begin follows a call closed by l3d_tail_shard_commit with the same world size");
     if (c->collinearity_t > (float)kEps)
         return fail(L3D_ERR_LIMIT, "the links to collinear segments are sequential by definition (line3D.cc:1904-1974): use l3d_compute_affinity");
-    translate(*c);
+    Translated frame(*c);
     int rc = affinity_prepare(c);
     if (rc == L3D_OK) rc = affinity_sim(c, c->tail_base_n[rank], c->tail_base_n[rank + 1]);
     // (the caller posts the exchange of the similarities right away, possibly on another stream or through a backend that
     // does not order itself after this stream: the part must be complete in device memory on return -- ADVICE round 5)
     if (rc == L3D_OK && !c->exch_ordered && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(L3D_ERR_HIP, "l3d_affinity_shard_begin: stream synchronisation failed");
-    if (rc != L3D_OK) { untranslate(*c); return rc; }
+    if (rc != L3D_OK) return rc;
     *simv = c->d_simv.p;
     for (uint32_t r = 0; r < world; ++r) { first[r] = c->tail_base_n[r]; count[r] = c->tail_base_n[r + 1] - c->tail_base_n[r]; }
     c->aff_shard_open = true;
+    frame.keep();   // the views stay translated until l3d_affinity_shard_finish / _abort (or the next l3d_match_begin)
     return L3D_OK;
 }
 
@@ -285,10 +284,9 @@ int l3d_affinity_shard_finish(l3d_ctx* c) {
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     if (c->state != l3d_ctx::MATCHED || !c->aff_shard_open)
         return fail(L3D_ERR_STATE, "l3d_affinity_shard_finish follows l3d_affinity_shard_begin and the exchange of the similarities");
+    const Translated frame(*c, true);   // translated by l3d_affinity_shard_begin
     c->aff_shard_open = false;
-    const int rc = affinity_rest(c);
-    untranslate(*c);
-    return rc;
+    return affinity_rest(c);
 }
 
 // closes an open sharded fill WITHOUT the bookkeeping pass (a rank whose peer failed: the other ranks' similarities never
@@ -297,9 +295,9 @@ int l3d_affinity_shard_abort(l3d_ctx* c) {
     if (!c) return fail(L3D_ERR_ARG, "null argument");
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     if (!c->aff_shard_open) return L3D_OK;
+    const Translated frame(*c, true);   // translated by l3d_affinity_shard_begin
     c->aff_shard_open = false;
     (void)hipStreamSynchronize(c->stream);
-    untranslate(*c);
     return L3D_OK;
 }
 
@@ -317,13 +315,13 @@ int l3d_reconstruct_3d_lines(l3d_ctx* c, uint32_t visibility_t, int perform_diff
     const unsigned vis = std::max<unsigned>(visibility_t, 3);
     c->visibility_t = vis; c->perform_rdd = perform_diffusion != 0;
     c->lines3D.clear();
-    translate(*c);
+    const Translated frame(*c);
     int rc = affinity_core(c);
     // matrix diffusion (performRDD, line3D.cc:1787-1791) on the device-resident A_
     if (rc == L3D_OK && perform_diffusion && c->aff_n_edges) {
         const uint32_t nnz = c->aff_n_edges, n_rows = c->aff_n_rows;
         rc = ensure_affinity_host(c);       // l2g; the edge list is replaced below
-        if (rc) { untranslate(*c); return rc; }
+        if (rc) return rc;
         const size_t wb = rdd_workspace_bytes(nnz, n_rows);
         DevBuf<char> ws; DevBuf<l3d_cledge> out;
         hipError_t e = ws.reserve(wb);
@@ -333,8 +331,7 @@ int l3d_reconstruct_3d_lines(l3d_ctx* c, uint32_t visibility_t, int perform_diff
         c->edges.resize(nnz);
         if (e == hipSuccess) e = hipMemcpyAsync(c->edges.data(), out.p, (size_t)nnz * sizeof(l3d_cledge), hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        ws.release(); out.release();
-        if (e != hipSuccess) { untranslate(*c); return fail(L3D_ERR_HIP, std::string("matrix diffusion: ") + hipGetErrorString(e)); }
+        if (e != hipSuccess) return fail(L3D_ERR_HIP, std::string("matrix diffusion: ") + hipGetErrorString(e));
     }
     if (rc == L3D_OK) rc = ensure_affinity_host(c);
     if (rc == L3D_OK) {
@@ -343,17 +340,15 @@ int l3d_reconstruct_3d_lines(l3d_ctx* c, uint32_t visibility_t, int perform_diff
         in.edges = c->edges;
         in.l2g = c->l2g;
         in.hyps.resize(c->n_hyps);
-        if (hipMemcpy(in.hyps.data(), c->d_hyps.p, in.hyps.size() * sizeof(HypRec), hipMemcpyDeviceToHost) != hipSuccess) {
-            untranslate(*c);
+        if (hipMemcpy(in.hyps.data(), c->d_hyps.p, in.hyps.size() * sizeof(HypRec), hipMemcpyDeviceToHost) != hipSuccess)
             return fail(L3D_ERR_HIP, "copying the 3D hypotheses failed");
-        }
         for (size_t i = 0; i < in.hyps.size(); ++i) in.entry_map[{in.hyps[i].m.src_cam, in.hyps[i].m.src_seg}] = i;
         for (auto* v : c->order) in.views[v->cam] = v;
         uint32_t ncl = 0, nvalid = 0;
         std::vector<ReconCluster> clusters;
         cluster_lines(in, clusters, &ncl, &nvalid);
         if (use_CERES) rc = line_opt(c, in.views, clusters, max_iter_CERES);                    // optimizeClusters, :1800-1805
-        if (rc != L3D_OK) { untranslate(*c); return rc; }
+        if (rc != L3D_OK) return rc;
         final_lines(in, clusters, c->lines3D);
         // untranslate the lines (performTranslation(translation_), line3D.cc:559-574)
         const d3 t = c->translation;
@@ -361,7 +356,6 @@ int l3d_reconstruct_3d_lines(l3d_ctx* c, uint32_t visibility_t, int perform_diff
         for (auto& L : c->lines3D) { for (auto& s : L.collinear) shift(s); shift(L.cluster_seg); }
         c->lines_done = true;
     }
-    untranslate(*c);
     return rc;
 }
 

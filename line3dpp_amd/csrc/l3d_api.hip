@@ -12,6 +12,13 @@ void set_error(const std::string& s) { g_err = s; }
 const char* last_error_cstr() { return g_err.c_str(); }
 
 int fail(int code, const std::string& msg) { set_error(msg); return code; }
+int set_device(int device) {
+    if (hipSetDevice(device) != hipSuccess) {
+        (void)hipGetLastError();       // the runtime keeps the error for the next hipGetLastError: a later launch would report it
+        return fail(L3D_ERR_HIP, "hipSetDevice failed: no usable HIP device");
+    }
+    return L3D_OK;
+}
 
 // View::View, view.cc:6-42
 void init_view(HostView& v, const double K[9], const double R[9], const double t[3]) {
@@ -244,6 +251,9 @@ size_t cache_max_device_bytes() {
     return cap;
 }
 }  // namespace
+std::atomic<uint64_t> g_live_blocks[2];   // test hook (l3d_debug_counter): blocks held by DevBuf [0] / PinnedBuf [1] objects
+void live_block_taken(bool pinned) { g_live_blocks[pinned].fetch_add(1, std::memory_order_relaxed); }
+void live_block_given(bool pinned) { g_live_blocks[pinned].fetch_sub(1, std::memory_order_relaxed); }
 ReleaseSynced::ReleaseSynced() { ++g_release_synced; }
 ReleaseSynced::~ReleaseSynced() { --g_release_synced; }
 void* block_cache_take(bool pinned, size_t bytes, size_t* got_bytes) {
@@ -386,7 +396,7 @@ l3d_ctx* l3d_create(int device, void* stream) {
         // handed to the cache as "drained")
         const bool drained_ok = hipStreamSynchronize(st) == hipSuccess;
         ok = ok && drained_ok;
-        { const ReleaseSynced drained; d.release(); h.release(); }
+        { const ReleaseSynced drained; d.release(); h.release(); }   // (by hand: at the end of their scope each would wait for the device again)
         if (!ok) { set_error("start-up launches failed: no usable HIP device"); l3d_destroy(c); return nullptr; }
         { std::lock_guard<std::mutex> lk(warm_mu); warmed.insert(device); }
     }
@@ -398,37 +408,6 @@ void l3d_destroy(l3d_ctx* c) {
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     const ReleaseSynced drained;   // everything this context enqueued has been waited for: its blocks may change hands
-    for (auto& kv : c->views) {
-        HostView& v = *kv.second;
-        v.d_seg4.release(); v.d_segf.release();
-    }
-    c->d_views.release(); c->d_pairs.release(); c->d_work.release(); c->d_slots.release(); c->d_slot_idx.release();
-    c->h_views.release(); c->h_pairs.release(); c->h_cull.release(); c->h_work.release();
-    c->h_segb.release(); c->h_cnt.release(); c->h_fin.release();
-    c->d_poff.release(); c->d_csr_dummy.release(); c->d_pair_present.release(); c->d_cnt64.release(); c->d_off64s.release(); c->d_scan_ws.release();
-    c->d_huge_u64.release(); c->d_inv_refs.release(); c->d_lzero.release(); c->d_list2.release(); c->d_list4.release(); c->d_listH.release();
-    c->d_seg_of_g.release(); c->d_huge_u32.release(); c->d_huge_f32.release(); c->d_ledges.release(); c->d_lhyps.release();
-    c->d_lsegs.release(); c->d_lcands.release(); c->d_lchdrs.release(); c->d_ltab.release(); c->h_ltab.release();
-    c->d_cull.release(); c->d_src_perm.release(); c->d_tgt_perm.release(); c->d_src_band.release();
-    c->d_chunk_band.release(); c->d_cull_keys.release(); c->d_tgt_sf.release(); c->d_tgt_band.release(); c->d_tgt_s4.release(); c->d_tgt_sd.release();
-    c->d_row_counts.release(); c->d_keep_rec.release(); c->d_row_start.release(); c->d_slot_row.release(); c->d_keep_info.release(); c->d_row_pair.release(); c->d_blk_row.release(); c->h_keep_info.release();
-    c->d_seg_base.release(); c->d_gseg_view.release();
-    c->d_scal.release();
-    c->d_surv_off.release(); c->d_hyp_off.release();
-    c->d_surv_tg.release(); c->d_surv_sg.release();
-    c->d_inv_tgt.release(); c->d_hyp_p.release(); c->d_hyp_q.release(); c->d_gsegx.release(); c->d_gsegd32.release();
-    c->d_tie_count.release(); c->d_tie_list.release(); c->d_tie_heap.release(); c->d_item_bucket.release(); c->d_item_order.release(); c->d_order_done.release();
-    c->d_coll_cnt.release(); c->d_coll_off.release(); c->d_coll_idx.release(); c->d_item_cnt.release();
-    c->d_item_off.release(); c->d_item_seg.release(); c->d_item_sim.release();
-    c->d_surv.release();
-    c->d_hyp_of_seg.release(); c->d_depths.release(); c->d_med = nullptr; c->d_hyps.release();
-    c->d_vaff.release(); c->d_simv.release(); c->h_vaff.release(); c->d_ca.release(); c->d_cb.release();
-    c->d_flag.release(); c->d_epos.release(); c->d_first_touch.release(); c->d_touch_flag.release();
-    c->d_touch_rank.release(); c->d_edges.release(); c->d_l2g.release();
-    c->d_lopt.release(); c->h_lopt.release();
-    c->proj.release();
-    for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
-    for (auto& e : c->lo_ev) if (e) (void)hipEventDestroy(e);
     delete c;
 }
 

@@ -77,13 +77,25 @@ hipError_t warm_rdd(hipStream_t); hipError_t warm_scan(hipStream_t); hipError_t 
 
 // ---- host helpers shared by the translation units (defined in l3d_api.hip) ----
 int fail(int code, const std::string& msg);
+int set_device(int device);        // L3D_ERR_HIP with the one message of every entry; clears the error the runtime keeps
 const char* last_error_cstr();
 void init_view(HostView& v, const double K[9], const double R[9], const double t[3]);
 void translate_view(HostView& v, const d3& d);
 d3 scene_translation(const std::vector<HostView*>& order);
 void neighbors_from_worldpoints(const std::map<uint32_t, HostView*>& views, uint32_t num_neighbors);   // l3d_neighbors.hip
 void translate(::l3d_ctx& c);      // Line3D::translate, line3D.cc:500-536
-void untranslate(::l3d_ctx& c);    // line3D.cc:539-545
+void untranslate(::l3d_ctx& c);    // line3D.cc:539-545: NOT idempotent (it adds the vector back)
+// The translated frame as a scope: translate() here, untranslate() on every way out.  l3d_match_begin / abort_match /
+// l3d_match_finish keep their explicit calls: their translation spans several calls of the C-ABI.
+struct Translated {
+    ::l3d_ctx& c;
+    bool on = true;
+    explicit Translated(::l3d_ctx& ctx, bool adopt = false) : c(ctx) { if (!adopt) translate(c); }   // adopt: ctx is translated already
+    Translated(const Translated&) = delete;
+    Translated& operator=(const Translated&) = delete;
+    ~Translated() { if (on) untranslate(c); }
+    void keep() { on = false; }    // hands the translated state on to a later call
+};
 void make_cull(const double F[9], double ws, double hs, double wt, double ht, PairCull& pc);
 void pair_baseline(const d3& Cs, const d3& Ct, PairDesc& pd);
 void orientation_thresholds(double& lo, double& hi);
@@ -120,7 +132,6 @@ struct ProjWork {
     DevBuf<char> d;                          // tables, records, planes, images of one group of cameras
     DevBuf<unsigned long long> keys, scan_ws;   // key planes of the group; k_scan.hip's work space (all-zero between scans)
     size_t budget = 0;                       // device-memory budget of a group of cameras; 0: l3d_project.hip's kProjBudget
-    void release() { h.release(); d.release(); keys.release(); scan_ws.release(); }
 };
 
 }  // namespace l3d
@@ -310,4 +321,16 @@ struct l3d_ctx {
     // the last l3d_project_lines (l3d_project.hip): visible records of every camera, camera after camera
     ProjWork proj;
     std::vector<l3d_projected_segment> proj_records;
+    // Run by l3d_destroy inside a ReleaseSynced scope.  The views' blocks go FIRST, in ascending camID and d_seg4 before
+    // d_segf, as they always have: the cache takes 512 blocks, so a scene of 256 views or more fills it with view blocks
+    // and the context's own return to the runtime -- which decides what the next context of the process finds there
+    // (bench.py: value_second_scene of C2 / C3).  The members then go in reverse order of declaration, which is NOT the
+    // order of the list l3d_destroy used to keep: where views and members together exceed the cache (about 196 to 255
+    // views, or the pinned cap of 1 GiB) it is now the members declared first -- the match buffers -- that find it full.
+    ~l3d_ctx() {
+        order.clear();
+        for (auto& kv : views) kv.second.reset();
+        for (auto& e : ev) if (e) (void)hipEventDestroy(e);
+        for (auto& e : lo_ev) if (e) (void)hipEventDestroy(e);
+    }
 };

@@ -1,5 +1,15 @@
 // l3d_host.h -- host-side state of libl3dpp_hip.so (the part of class L3DPP::Line3D / L3DPP::View
-// the hot path needs), plus small RAII helpers for HIP memory.
+// the hot path needs), plus the owners of HIP memory.
+//
+// Who releases what, and when.  DevBuf<T> / PinnedBuf<T> OWN their block: the destructor gives it up (to the cache
+// below, else to the runtime), a buffer can be moved but not copied, and nothing has to be released by hand.
+//   * a buffer local to a call goes at the end of its scope, on every way out -- an early `return fail(...)` or
+//     L3D_HIP_CHECK included;
+//   * a member of l3d_ctx or of a HostView goes with its owner: ~l3d_ctx (l3d_ctx.h) lets the views' buffers go first,
+//     then its own, and l3d_destroy runs it inside a ReleaseSynced scope after it has waited for the stream;
+//   * release() stays public for the buffers that give their block up mid-life (reserve() calls it when a buffer grows).
+// No DevBuf / PinnedBuf may have static storage duration: the cache's own statics (l3d_api.hip) could be gone before such
+// a buffer is destroyed.  None has.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -9,6 +19,7 @@
 #include <map>
 #include <set>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/l3dpp_hip.h"
@@ -27,7 +38,7 @@ void set_error(const std::string& s);
         }                                                                                         \
     } while (0)
 
-// Blocks released by a context (l3d_destroy, a buffer that grows) go to a process-wide cache and are handed to the next
+// Blocks released by a buffer (its destructor, a buffer that grows) go to a process-wide cache and are handed to the next
 // reservation of similar size on the same device instead of back to the runtime: hipFree costs ~0.2 ms and
 // hipHostMalloc up to milliseconds on MI355X (tools/alloc_bench.hip), so a process that serves one Line3D object per
 // scene would otherwise pay ~10 ms per scene for memory it had a moment ago.  Bounded (blocks; bytes: a quarter of the
@@ -46,56 +57,59 @@ size_t block_cache_trim(int kind);                                      // 0 dev
 struct ReleaseSynced {   // RAII: releases on this thread inside the scope need no device synchronisation
     ReleaseSynced(); ~ReleaseSynced();
 };
+// blocks held by the DevBuf / PinnedBuf objects of the process (l3d_debug_counter: "live_device_blocks",
+// "live_pinned_blocks"): a buffer obtained one, a buffer gave one up; blocks lying in the cache are not live
+void live_block_taken(bool pinned);
+void live_block_given(bool pinned);
 
-// device buffer that grows but never shrinks (its block returns to the cache with the context)
-template <class T>
-struct DevBuf {
+// A block of device memory (DevBuf) or of pinned host memory (PinnedBuf: async H2D copies from it do not stall the
+// stream, pageable sources are copied synchronously) that grows but never shrinks.  The buffer OWNS the block.
+template <class T, bool Pinned>
+struct Block {
     T* p = nullptr;
     size_t cap = 0;          // elements
     size_t bytes_ = 0;       // size of the block behind p (a cached block may be larger than asked for)
+    Block() = default;
+    Block(const Block&) = delete;
+    Block& operator=(const Block&) = delete;
+    Block(Block&& o) noexcept { take(o); }
+    Block& operator=(Block&& o) noexcept { if (this != &o) { release(); take(o); } return *this; }
+    ~Block() { release(); }
     hipError_t reserve(size_t n) {
         if (n <= cap) return hipSuccess;
         release();
         size_t got = 0;
-        if (void* q = block_cache_take(false, n * sizeof(T), &got)) { p = (T*)q; bytes_ = got; cap = got / sizeof(T); return hipSuccess; }
-        hipError_t e = hipMalloc((void**)&p, n * sizeof(T));
-        if (e != hipSuccess && block_cache_trim(0)) { (void)hipGetLastError(); e = hipMalloc((void**)&p, n * sizeof(T)); }
-        if (e == hipSuccess) { cap = n; bytes_ = n * sizeof(T); } else p = nullptr;
+        if (void* q = block_cache_take(Pinned, n * sizeof(T), &got)) { p = (T*)q; bytes_ = got; cap = got / sizeof(T); live_block_taken(Pinned); return hipSuccess; }
+        hipError_t e = alloc(n * sizeof(T));
+        if (e != hipSuccess && block_cache_trim(Pinned ? 1 : 0)) { (void)hipGetLastError(); e = alloc(n * sizeof(T)); }
+        if (e == hipSuccess) { cap = n; bytes_ = n * sizeof(T); live_block_taken(Pinned); } else p = nullptr;
         return e;
     }
     // work space that its kernels leave all-zero between launches (k_scan.hip): zeroed when it is (re)allocated
     hipError_t reserve_zeroed(size_t n, hipStream_t st) {
+        static_assert(!Pinned, "reserve_zeroed is for device work space");
         if (n <= cap) return hipSuccess;
         hipError_t e = reserve(n);
         if (e == hipSuccess) e = hipMemsetAsync(p, 0, cap * sizeof(T), st);
         return e;
     }
     void release() {
-        if (p && !block_cache_give(false, p, bytes_)) (void)hipFree(p);
+        if (p) live_block_given(Pinned);
+        if (p && !block_cache_give(Pinned, p, bytes_)) (void)(Pinned ? hipHostFree(p) : hipFree(p));
         p = nullptr; cap = 0; bytes_ = 0;
     }
+private:
+    hipError_t alloc(size_t b) { return Pinned ? hipHostMalloc((void**)&p, b, hipHostMallocDefault) : hipMalloc((void**)&p, b); }
+    void take(Block& o) { p = o.p; cap = o.cap; bytes_ = o.bytes_; o.p = nullptr; o.cap = 0; o.bytes_ = 0; }   // *this is empty
 };
-
-// pinned host staging: async H2D copies from it do not stall the stream (pageable sources are copied synchronously)
-template <class T>
-struct PinnedBuf {
-    T* p = nullptr;
-    size_t cap = 0, bytes_ = 0;
-    hipError_t reserve(size_t n) {
-        if (n <= cap) return hipSuccess;
-        release();
-        size_t got = 0;
-        if (void* q = block_cache_take(true, n * sizeof(T), &got)) { p = (T*)q; bytes_ = got; cap = got / sizeof(T); return hipSuccess; }
-        hipError_t e = hipHostMalloc((void**)&p, n * sizeof(T), hipHostMallocDefault);
-        if (e != hipSuccess && block_cache_trim(1)) { (void)hipGetLastError(); e = hipHostMalloc((void**)&p, n * sizeof(T), hipHostMallocDefault); }
-        if (e == hipSuccess) { cap = n; bytes_ = n * sizeof(T); } else p = nullptr;
-        return e;
-    }
-    void release() {
-        if (p && !block_cache_give(true, p, bytes_)) (void)hipHostFree(p);
-        p = nullptr; cap = 0; bytes_ = 0;
-    }
-};
+template <class T> using DevBuf = Block<T, false>;
+template <class T> using PinnedBuf = Block<T, true>;
+static_assert(!std::is_copy_constructible<DevBuf<char>>::value && !std::is_copy_assignable<DevBuf<char>>::value &&
+              !std::is_copy_constructible<PinnedBuf<char>>::value && !std::is_copy_assignable<PinnedBuf<char>>::value,
+              "a buffer owns its block: never copied");
+static_assert(std::is_nothrow_move_constructible<DevBuf<char>>::value && std::is_nothrow_move_assignable<DevBuf<char>>::value &&
+              std::is_nothrow_move_constructible<PinnedBuf<char>>::value && std::is_nothrow_move_assignable<PinnedBuf<char>>::value,
+              "a buffer is moved without throwing (the source is left empty)");
 
 // Host -> device through a pinned staging buffer, left out when the device array already holds these very bytes: the
 // view table, the pair list and the small tables of phase B are the same from one matchImages call to the next as
@@ -177,9 +191,9 @@ struct HostView {
     bool by_worldpoints = false;        // added with a worldpoint list (neighbors_by_worldpoints_): neighbours are found
     std::vector<uint32_t> worldpoints;  // from the worldpoint overlap at every matchImages (views2worldpoints_[cam])
     FlatSet visual_nbrs;                // visual_neighbors_[cam]
-    // device
-    DevBuf<float4> d_seg4;
+    // device (destroyed in reverse order: d_seg4's block is released before d_segf's, as l3d_destroy always did)
     DevBuf<SegF> d_segf;
+    DevBuf<float4> d_seg4;
     // pairs touching this view (indices into Ctx::pairs)
     std::vector<uint32_t> out_pairs;    // this view is src, ascending tgt
     std::vector<uint32_t> in_pairs;     // this view is tgt and src < this (inverse matches), ascending src

@@ -10,6 +10,7 @@ namespace l3d {
 
 extern std::atomic<uint64_t> g_knn_replay_calls;      // l3d_api.hip
 extern std::atomic<uint64_t> g_keep_all_repeats;      // l3d_api.hip
+extern std::atomic<uint64_t> g_live_blocks[2];        // l3d_api.hip
 extern std::atomic<uint64_t> g_csr_global_launches;   // k_lists.hip, test hook read through l3d_debug_counter
 // l3d_seam.hip, test hooks: lists l3d_score_matches sent down each path of k_support / k_score_all (k_views.hip)
 extern std::atomic<uint64_t> g_seam_support_lists[4];  // indexed by SupportTier - 1

@@ -100,8 +100,9 @@ int run_lsd(l3d_ctx* c, const std::vector<const l3d_image*>& ims, const std::vec
         max_small = std::max(max_small, (uint32_t)sm);
         max_scaled = std::max(max_scaled, (uint32_t)sc);
     }
+    // (arena's destructor waits for the device -- block_cache_give outside a ReleaseSynced scope, or hipFree: that wait
+    // is what protects the caller's raw on the L3D_HIP_CHECK returns below; never call this inside a ReleaseSynced scope)
     DevBuf<char> arena;
-    struct Guard { DevBuf<char>& a; hipStream_t st; ~Guard() { (void)hipStreamSynchronize(st); a.release(); } } guard{arena, c->stream};
     L3D_HIP_CHECK(arena.reserve(bytes));
     char* base = arena.p;
     LsdImage* d_imgs = (LsdImage*)base;
@@ -146,7 +147,10 @@ int run_lsd(l3d_ctx* c, const std::vector<const l3d_image*>& ims, const std::vec
     L3D_HIP_CHECK(hipMemcpyAsync(res.data(), d_res, n * sizeof(LsdResult), hipMemcpyDeviceToHost, c->stream));
     L3D_HIP_CHECK(hipStreamSynchronize(c->stream));
     for (uint32_t i = 0; i < n; ++i) {
-        if (res[i].overflow) return fail(L3D_ERR_LIMIT, "line-segment detection: output capacity exceeded");
+        if (res[i].overflow) {
+            (void)hipStreamSynchronize(c->stream);   // the copies into raw[0 .. i) are still queued: the caller drops raw
+            return fail(L3D_ERR_LIMIT, "line-segment detection: output capacity exceeded");
+        }
         raw[i].resize(res[i].n);
         if (res[i].n)
             L3D_HIP_CHECK(hipMemcpyAsync(raw[i].data(), d[i].out, res[i].n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
@@ -320,7 +324,6 @@ int undistort_batch(l3d_ctx* c, uint32_t n, const l3d_image* in, uint8_t* const*
         max_pix = std::max(max_pix, im.cols * im.rows);
     }
     DevBuf<char> arena;
-    struct Guard { DevBuf<char>& a; hipStream_t st; ~Guard() { (void)hipStreamSynchronize(st); a.release(); } } guard{arena, c->stream};
     L3D_HIP_CHECK(arena.reserve(bytes));
     char* base = arena.p;
     for (uint32_t i = 0; i < n; ++i) {

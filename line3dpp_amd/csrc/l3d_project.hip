@@ -69,13 +69,6 @@ int check_images(uint32_t n, const l3d_image* images, const std::vector<std::pai
     }
     return L3D_OK;
 }
-int set_device(int device) {
-    if (hipSetDevice(device) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(L3D_ERR_HIP, "hipSetDevice failed: no usable HIP device");
-    }
-    return L3D_OK;
-}
 
 // ---- stage 1 --------------------------------------------------------------------------------------------------------
 // P6: n_seg x (P1, P2); counts[n_cams]; out: the visible records, camera after camera.  Arguments already checked.
@@ -303,9 +296,7 @@ int l3d_project_segments(int device, uint32_t n_cams, const l3d_camera* cams, ui
     if (n_cams && n_segments) {
         if (int rc = set_device(device)) return rc;
         ProjWork w;
-        const int rc = project_core(w, 0, n_cams, cams, n_segments, P6.data(), line_of_segment, near_plane, cnt.data(), rec);
-        w.release();
-        if (rc) return rc;
+        if (int rc = project_core(w, 0, n_cams, cams, n_segments, P6.data(), line_of_segment, near_plane, cnt.data(), rec)) return rc;
     }
     for (uint32_t c = 0; c < n_cams; ++c) counts[c] = cnt[c];
     *n = rec.size();
@@ -333,9 +324,7 @@ int l3d_render_line_maps(int device, uint32_t n_cams, const l3d_camera* cams, co
     j.n_cams = n_cams; j.size = camera_sizes(n_cams, cams); j.raster = true; j.n_rec = n_records_per_cam; j.rec = records;
     j.thickness = thickness; j.ids_out = line_id_planes; j.iz_out = inv_depth_planes;
     ProjWork w;
-    const int rc = maps_core(w, 0, j);
-    w.release();
-    return rc;
+    return maps_core(w, 0, j);
 }
 
 int l3d_draw_line_maps(int device, uint32_t n_cams, const l3d_image* images, const int32_t* const* line_id_planes, uint32_t n_lines,
@@ -351,9 +340,7 @@ int l3d_draw_line_maps(int device, uint32_t n_cams, const l3d_image* images, con
     for (uint32_t c = 0; c < n_cams; ++c) j.size[c] = {images[c].cols, images[c].rows};
     j.ids_in = line_id_planes; j.images = images; j.colors = n_lines ? colors : nullptr; j.n_lines = n_lines; j.alpha = alpha; j.rgb_out = out_rgb;
     ProjWork w;
-    const int rc = maps_core(w, 0, j);
-    w.release();
-    return rc;
+    return maps_core(w, 0, j);
 }
 
 int l3d_view_camera(l3d_ctx* c, uint32_t camID, l3d_camera* cam) {

@@ -39,36 +39,29 @@ int l3d_triangulate_points(int device, uint32_t n_cameras, const double* P12, ui
     for (uint64_t o = 0; o < n_obs; ++o)
         if (obs_camera[o] >= n_cameras) return fail(L3D_ERR_ARG, "observation of a camera >= n_cameras");
     if (n_points >= (1ull << 32) || n_obs >= (1ull << 32)) return fail(L3D_ERR_LIMIT, "more than 2^32 points or observations");
-    if (hipSetDevice(device) != hipSuccess) {
-        (void)hipGetLastError();       // the runtime keeps the error for the next hipGetLastError: a later launch would report it
-        return fail(L3D_ERR_HIP, "hipSetDevice failed: no usable HIP device");
-    }
+    if (int rc = set_device(device)) return rc;
     // one packed upload: projection matrices | CSR | cameras | pixels; then the results: positions | flags
     const size_t b_P = 96 * (size_t)n_cameras, b_off = 8 * ((size_t)n_points + 1), b_cam = 4 * (size_t)n_obs, b_xy = 16 * (size_t)n_obs;
     const size_t o_P = 0, o_off = up64(o_P + b_P), o_cam = up64(o_off + b_off), o_xy = up64(o_cam + b_cam);
     const size_t in_bytes = o_xy + b_xy, o_X = up64(in_bytes), o_val = o_X + 24 * (size_t)n_points;
     const size_t total = o_val + (size_t)n_points;
     PinnedBuf<char> hb; DevBuf<char> db;
-    const int rc = [&]() -> int {
-        if (hb.reserve(total) != hipSuccess || db.reserve(total) != hipSuccess)
-            return fail(L3D_ERR_HIP, "l3d_triangulate_points: allocation failed");
-        char* h = hb.p; char* d = db.p;
-        if (b_P) std::memcpy(h + o_P, P12, b_P);
-        std::memcpy(h + o_off, obs_offsets, b_off);
-        if (n_obs) { std::memcpy(h + o_cam, obs_camera, b_cam); std::memcpy(h + o_xy, obs_xy, b_xy); }
-        const TriArgs a{(const double*)(d + o_P), n_cameras, n_points, (const uint64_t*)(d + o_off), (const uint32_t*)(d + o_cam),
-                        (const double*)(d + o_xy), (double*)(d + o_X), (uint8_t*)(d + o_val)};
-        hipError_t e = hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, 0);
-        if (e == hipSuccess) e = launch_triangulate(a, 0);
-        if (e == hipSuccess) e = hipMemcpyAsync(h + o_X, d + o_X, total - o_X, hipMemcpyDeviceToHost, 0);
-        if (e == hipSuccess) e = hipStreamSynchronize(0);
-        if (e != hipSuccess) return fail(L3D_ERR_HIP, std::string("l3d_triangulate_points: ") + hipGetErrorString(e));
-        std::memcpy(X3, h + o_X, 24 * (size_t)n_points);
-        std::memcpy(valid, h + o_val, (size_t)n_points);
-        return L3D_OK;
-    }();
-    hb.release(); db.release();
-    return rc;
+    if (hb.reserve(total) != hipSuccess || db.reserve(total) != hipSuccess)
+        return fail(L3D_ERR_HIP, "l3d_triangulate_points: allocation failed");
+    char* h = hb.p; char* d = db.p;
+    if (b_P) std::memcpy(h + o_P, P12, b_P);
+    std::memcpy(h + o_off, obs_offsets, b_off);
+    if (n_obs) { std::memcpy(h + o_cam, obs_camera, b_cam); std::memcpy(h + o_xy, obs_xy, b_xy); }
+    const TriArgs a{(const double*)(d + o_P), n_cameras, n_points, (const uint64_t*)(d + o_off), (const uint32_t*)(d + o_cam),
+                    (const double*)(d + o_xy), (double*)(d + o_X), (uint8_t*)(d + o_val)};
+    hipError_t e = hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, 0);
+    if (e == hipSuccess) e = launch_triangulate(a, 0);
+    if (e == hipSuccess) e = hipMemcpyAsync(h + o_X, d + o_X, total - o_X, hipMemcpyDeviceToHost, 0);
+    if (e == hipSuccess) e = hipStreamSynchronize(0);
+    if (e != hipSuccess) return fail(L3D_ERR_HIP, std::string("l3d_triangulate_points: ") + hipGetErrorString(e));
+    std::memcpy(X3, h + o_X, 24 * (size_t)n_points);
+    std::memcpy(valid, h + o_val, (size_t)n_points);
+    return L3D_OK;
 }
 
 int l3d_rotation_from_rpy(double roll, double pitch, double yaw, double R9[9]) {
