@@ -482,6 +482,20 @@ int l3d_cayley_to_segment(const double x[4], const double P1_old[3], const doubl
  * observation, before the loss; ok [n]: 0 where the evaluation fails (residual 0); *cost = 1/2 sum Huber2(|r_i|^2) */
 int l3d_line_opt_eval(int device, uint32_t n, const double x[4], const double* obs, const double* cams, double* cost,
                       double* residuals, double* jacobians, int32_t* ok);
+/* test hook (device): the bundling kernel's solver on its own -- the function the pipeline's stage calls, without a
+ * context.  Line i starts at x0[4i .. 4i+3] = (omega, s) and owns the residuals [res_off[i], res_off[i+1]) (CSR, res_off[0]
+ * == 0, non-decreasing; a line without residuals is legal); residual r is obs[6r .. 6r+5] = (p1x, p1y, p2x, p2y, nx, ny)
+ * seen by camera obs_cam[r] < n_cams, cams [n_cams x 16] as for l3d_line_opt_eval.  The lines are solved in one launch
+ * of k_lineopt in the stage's work order: a stable sort by residual count, longest first; the lines with more than
+ * narrow_max residuals take a wave each, the others a 16-lane group (the stage passes 16; 0 sends every line through the
+ * wave tier).  Per line, by its index in the input: x_out[4i ..] the final parameters, cost01[2i], cost01[2i + 1] the
+ * robust cost at the start and at the end, iters[i] the iterations (accepted and rejected steps), status[i] the stopping
+ * rule: 1 gradient, 2 function, 3 parameter, 4 max_iter, 5 other (a start point that cannot be evaluated, which keeps
+ * x0 with iters 0, or a collapsed trust region).  L3D_ERR_ARG, with nothing launched and no output written: a null
+ * pointer, res_off[0] != 0 or a decreasing res_off, an obs_cam[r] >= n_cams, narrow_max > 16.  n_lines == 0: L3D_OK. */
+int l3d_line_opt_solve(int device, uint32_t n_lines, const double* x0, const uint32_t* res_off, const double* obs,
+                       const uint32_t* obs_cam, uint32_t n_cams, const double* cams, uint32_t max_iter, uint32_t narrow_max,
+                       double* x_out, double* cost01, uint32_t* iters, uint32_t* status);
 
 /* main_pix4d.cpp's triangulation of tie points (linearHomTriangulation, main_pix4d.cpp:34-69, in the loop of :354-372)
  * on the device, one lane per point in fp64 (k_triangulate.hip).  P12: n_cameras row-major 3x4 projection matrices;

@@ -139,7 +139,7 @@ EXPORTS = [
     "l3d_trim_cache", "l3d_set_timing_level", "l3d_tail_shard_count", "l3d_tail_shard_layout", "l3d_tail_shard_commit",
     "l3d_sfm_open_colmap", "l3d_sfm_open_bundler", "l3d_sfm_num_images", "l3d_sfm_get_image", "l3d_sfm_get_worldpoints",
     "l3d_sfm_close", "l3d_debug_counter", "l3d_affinity_shard_begin", "l3d_affinity_shard_finish", "l3d_affinity_shard_abort", "l3d_shard_options",
-    "l3d_line_opt_stats", "l3d_line_to_cayley", "l3d_cayley_to_segment", "l3d_line_opt_eval", "l3d_get_fresh_hyp",
+    "l3d_line_opt_stats", "l3d_line_to_cayley", "l3d_cayley_to_segment", "l3d_line_opt_eval", "l3d_line_opt_solve", "l3d_get_fresh_hyp",
     "l3d_detect_segments", "l3d_detect_view_segments", "l3d_get_detected_segments", "l3d_get_detect_stats",
     "l3d_add_view_image", "l3d_add_view_image_worldpoints", "l3d_undistort_images",
     "l3d_undistort_images_model", "l3d_sfm_get_camera_model", "l3d_sfm_get_camera_params",
@@ -242,6 +242,7 @@ def load():
     L.l3d_line_to_cayley.argtypes = [vp, vp, vp]
     L.l3d_cayley_to_segment.argtypes = [vp, vp, vp, vp, vp]
     L.l3d_line_opt_eval.argtypes = [i32, u32, vp, vp, vp, vp, vp, vp, vp]
+    L.l3d_line_opt_solve.argtypes = [i32, u32, vp, vp, vp, vp, u32, vp, u32, u32, vp, vp, vp, vp]
     L.l3d_selftest_arith.argtypes = [i32, u64, u64, vp]
     L.l3d_selftest_scan.argtypes = [i32, u32, vp, u32, u32, vp, i32, i32, vp, vp, C.POINTER(u64), C.POINTER(u64)]
     L.l3d_detect_segments.argtypes = [vp, u32, vp, i32, u32, vp]

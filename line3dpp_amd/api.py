@@ -699,6 +699,32 @@ def triangulate_points(P, obs_offsets, obs_camera, obs_xy, device=0):
     return X, valid.astype(bool)
 
 
+def line_opt_solve(x0, res_off, obs, obs_cam, cams, max_iter=250, narrow_max=16, device=0):
+    """l3d_line_opt_solve: the line bundling kernel's Levenberg-Marquardt solves on their own (k_lineopt.hip, through the
+    function the pipeline's stage calls).  x0 [n, 4]; line i owns the residuals res_off[i] .. res_off[i + 1] of obs
+    [n_res, 6] = (p1x, p1y, p2x, p2y, nx, ny) and obs_cam [n_res]; cams [n_cams, 16] = (R row-major, C, fx, fy, px, py).
+    Lines with more than narrow_max (<= 16) residuals take a wave each, the others 16 lanes.
+    -> (x [n, 4], cost0 [n], cost1 [n], iters [n], status [n]): 1 gradient, 2 function, 3 parameter, 4 max_iter, 5 other"""
+    L = _lib.load()
+    x0 = np.ascontiguousarray(x0, np.float64).reshape(-1, 4)
+    off = np.ascontiguousarray(res_off, np.uint32).reshape(-1)
+    obs = np.ascontiguousarray(obs, np.float64).reshape(-1, 6)
+    cam = np.ascontiguousarray(obs_cam, np.uint32).reshape(-1)
+    cams = np.ascontiguousarray(cams, np.float64).reshape(-1, 16)
+    n = len(x0)
+    if len(off) != n + 1 or len(obs) != len(cam) or (n and int(off[-1]) > len(cam)):
+        raise ValueError("x0, res_off, obs and obs_cam do not describe the same lines")
+    x = np.zeros((n, 4), np.float64)
+    cost = np.zeros((n, 2), np.float64)
+    iters = np.zeros(n, np.uint32)
+    status = np.zeros(n, np.uint32)
+    rc = L.l3d_line_opt_solve(int(device), n, ptr(x0), ptr(off), ptr(obs), ptr(cam), len(cams), ptr(cams), int(max_iter),
+                              int(narrow_max), ptr(x), ptr(cost), ptr(iters), ptr(status))
+    if rc != 0:
+        raise RuntimeError(f"l3d_line_opt_solve failed [{rc}]: {_lib.last_error()}")
+    return x, cost[:, 0].copy(), cost[:, 1].copy(), iters, status
+
+
 def find_collinear_segments(lines, dist_t, device=0):
     """Seam-level call replacing View::findCollinGPU / find_collinear_segments_GPU (view.cc:173-209) with the
     semantics of View::findCollinCPU: CSR (offsets[M+1], idx) of the collinear segments of every segment."""

@@ -89,8 +89,50 @@ namespace {
 size_t up64(size_t b) { return (b + 63) & ~(size_t)63; }
 }
 
-// LineOptimizer::optimize on `clusters` (clusters3D_, translated frame; views = views_): parameters, one packed upload,
-// one launch, one download, write-back in the original order (dropped clusters leave the list)
+// The per-line solves of `order` (indices into x0 / res_off, in the caller's order): the work order -- a stable sort by
+// residual count, longest first, so lines of equal count keep the caller's order; the first n_wide, with more than
+// narrow_max (<= 16) residuals, take a wave each, the others a 16-lane group -- then one packed upload, one launch of
+// k_lineopt and one download through the caller's buffers.  `order` comes back sorted, *out points at the results by
+// line index (inside hb; only the lines of `order` are written).  ev: an event pair recorded around the launch, or null.
+int lo_solve_lines(PinnedBuf<char>& hb, DevBuf<char>& db, hipStream_t stream, hipEvent_t* ev, const std::vector<LoCam>& cams,
+                   const std::vector<LoObs>& obs, const std::vector<double>& x0, const std::vector<uint32_t>& res_off,
+                   std::vector<uint32_t>& order, uint32_t narrow_max, uint32_t max_iter, uint32_t* n_wide_out, const LoOut** out) {
+    const size_t nl = x0.size() / 4;
+    // work order: one-wave lines (more than narrow_max residuals) first, both classes longest first
+    auto cnt = [&](uint32_t i) { return res_off[i + 1] - res_off[i]; };
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return cnt(a) > cnt(b); });
+    uint32_t n_wide = 0;
+    while (n_wide < order.size() && cnt(order[n_wide]) > narrow_max) ++n_wide;
+    *n_wide_out = n_wide;
+    // one packed upload: cameras | observations | start parameters | CSR | order; then the results
+    const size_t o_cam = 0, o_obs = up64(o_cam + cams.size() * sizeof(LoCam)), o_x = up64(o_obs + obs.size() * sizeof(LoObs));
+    const size_t o_off = up64(o_x + x0.size() * 8), o_ord = up64(o_off + res_off.size() * 4);
+    const size_t in_bytes = o_ord + std::max<size_t>(order.size(), 1) * 4, o_out = up64(in_bytes);
+    const size_t total = o_out + nl * sizeof(LoOut);
+    if (hb.reserve(total) != hipSuccess || db.reserve(total) != hipSuccess)
+        return fail(L3D_ERR_HIP, "line bundling: allocation failed");
+    char* h = hb.p;
+    if (!cams.empty()) std::memcpy(h + o_cam, cams.data(), cams.size() * sizeof(LoCam));
+    if (!obs.empty()) std::memcpy(h + o_obs, obs.data(), obs.size() * sizeof(LoObs));
+    std::memcpy(h + o_x, x0.data(), x0.size() * 8);
+    std::memcpy(h + o_off, res_off.data(), res_off.size() * 4);
+    if (!order.empty()) std::memcpy(h + o_ord, order.data(), order.size() * 4);
+    char* d = db.p;
+    LoArgs a{(const LoCam*)(d + o_cam), (const LoObs*)(d + o_obs), (const double*)(d + o_x), (const uint32_t*)(d + o_off),
+             (const uint32_t*)(d + o_ord), n_wide, (uint32_t)order.size() - n_wide, max_iter, (LoOut*)(d + o_out)};
+    hipError_t e = hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess && ev) e = hipEventRecord(ev[0], stream);
+    if (e == hipSuccess) e = launch_lineopt(a, stream);
+    if (e == hipSuccess && ev) e = hipEventRecord(ev[1], stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(h + o_out, d + o_out, nl * sizeof(LoOut), hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) return fail(L3D_ERR_HIP, std::string("line bundling: ") + hipGetErrorString(e));
+    *out = (const LoOut*)(h + o_out);
+    return L3D_OK;
+}
+
+// LineOptimizer::optimize on `clusters` (clusters3D_, translated frame; views = views_): parameters, the solves
+// (lo_solve_lines), write-back in the original order (dropped clusters leave the list)
 int line_opt(::l3d_ctx* c, const std::map<uint32_t, const HostView*>& views, std::vector<ReconCluster>& clusters,
              uint32_t max_iter) {
     l3d_line_opt_summary& st = c->lo_stats;
@@ -130,43 +172,17 @@ int line_opt(::l3d_ctx* c, const std::map<uint32_t, const HostView*>& views, std
     }
     st.lines_bundled = (uint32_t)order.size();
     st.residuals = (uint32_t)obs.size();
-    // work order: one-wave lines (more than kLoNarrow residuals) first, both classes longest first
-    auto cnt = [&](uint32_t i) { return res_off[i + 1] - res_off[i]; };
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return cnt(a) > cnt(b); });
-    uint32_t n_wide = 0;
-    while (n_wide < order.size() && cnt(order[n_wide]) > kLoNarrow) ++n_wide;
-    st.lines_wide = n_wide;
-    for (uint32_t i : order) st.max_residuals = std::max(st.max_residuals, cnt(i));
-    // one packed upload: cameras | observations | start parameters | CSR | order; then the results
-    const size_t o_cam = 0, o_obs = up64(o_cam + cams.size() * sizeof(LoCam)), o_x = up64(o_obs + obs.size() * sizeof(LoObs));
-    const size_t o_off = up64(o_x + x0.size() * 8), o_ord = up64(o_off + res_off.size() * 4);
-    const size_t in_bytes = o_ord + std::max<size_t>(order.size(), 1) * 4, o_out = up64(in_bytes);
-    const size_t total = o_out + nl * sizeof(LoOut);
-    if (c->h_lopt.reserve(total) != hipSuccess || c->d_lopt.reserve(total) != hipSuccess)
-        return fail(L3D_ERR_HIP, "line bundling: allocation failed");
-    char* h = c->h_lopt.p;
-    std::memcpy(h + o_cam, cams.data(), cams.size() * sizeof(LoCam));
-    if (!obs.empty()) std::memcpy(h + o_obs, obs.data(), obs.size() * sizeof(LoObs));
-    std::memcpy(h + o_x, x0.data(), x0.size() * 8);
-    std::memcpy(h + o_off, res_off.data(), res_off.size() * 4);
-    if (!order.empty()) std::memcpy(h + o_ord, order.data(), order.size() * 4);
-    char* d = c->d_lopt.p;
-    LoArgs a{(const LoCam*)(d + o_cam), (const LoObs*)(d + o_obs), (const double*)(d + o_x), (const uint32_t*)(d + o_off),
-             (const uint32_t*)(d + o_ord), n_wide, (uint32_t)order.size() - n_wide, max_iter, (LoOut*)(d + o_out)};
+    for (uint32_t i : order) st.max_residuals = std::max(st.max_residuals, res_off[i + 1] - res_off[i]);
     const bool timed = c->timing_level >= 2;
     if (timed && !c->lo_ev[0]) {
         if (hipEventCreate(&c->lo_ev[0]) != hipSuccess || hipEventCreate(&c->lo_ev[1]) != hipSuccess)
             return fail(L3D_ERR_HIP, "line bundling: hipEventCreate failed");
     }
-    hipError_t e = hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && timed) e = hipEventRecord(c->lo_ev[0], c->stream);
-    if (e == hipSuccess) e = launch_lineopt(a, c->stream);
-    if (e == hipSuccess && timed) e = hipEventRecord(c->lo_ev[1], c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(h + o_out, d + o_out, nl * sizeof(LoOut), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return fail(L3D_ERR_HIP, std::string("line bundling: ") + hipGetErrorString(e));
+    const LoOut* out = nullptr;
+    if (int rc = lo_solve_lines(c->h_lopt, c->d_lopt, c->stream, timed ? c->lo_ev : nullptr, cams, obs, x0, res_off, order,
+                                kLoNarrow, max_iter, &st.lines_wide, &out))
+        return rc;
     if (timed) st.kernel_ms = ev_ms(c->lo_ev[0], c->lo_ev[1]);
-    const LoOut* out = (const LoOut*)(h + o_out);
     for (uint32_t i : order) {
         const LoOut& o = out[i];
         switch (o.status) {
@@ -196,6 +212,48 @@ int line_opt(::l3d_ctx* c, const std::map<uint32_t, const HostView*>& views, std
 }  // namespace l3d
 
 extern "C" {
+
+int l3d_line_opt_solve(int device, uint32_t n_lines, const double* x0, const uint32_t* res_off, const double* obs,
+                       const uint32_t* obs_cam, uint32_t n_cams, const double* cams, uint32_t max_iter, uint32_t narrow_max,
+                       double* x_out, double* cost01, uint32_t* iters, uint32_t* status) {
+    if (!n_lines) return L3D_OK;
+    if (!x0 || !res_off || !x_out || !cost01 || !iters || !status) return fail(L3D_ERR_ARG, "null argument");
+    if (narrow_max > kLoNarrow) return fail(L3D_ERR_ARG, "narrow_max above 16");
+    if (res_off[0] != 0) return fail(L3D_ERR_ARG, "res_off[0] is not 0");
+    for (uint32_t i = 0; i < n_lines; ++i)
+        if (res_off[i + 1] < res_off[i]) return fail(L3D_ERR_ARG, "res_off decreases");
+    const uint32_t n_res = res_off[n_lines];
+    if (n_res && (!obs || !obs_cam || !cams)) return fail(L3D_ERR_ARG, "null argument");
+    for (uint32_t r = 0; r < n_res; ++r)
+        if (obs_cam[r] >= n_cams) return fail(L3D_ERR_ARG, "observation of a camera >= n_cams");
+    if (int rc = set_device(device)) return rc;
+    std::vector<LoCam> hc(cams ? n_cams : 0);
+    for (size_t i = 0; i < hc.size(); ++i) {
+        const double* c = cams + 16 * i;
+        for (int k = 0; k < 9; ++k) hc[i].R[k] = c[k];
+        for (int k = 0; k < 3; ++k) hc[i].C[k] = c[9 + k];
+        hc[i].fx = c[12]; hc[i].fy = c[13]; hc[i].px = c[14]; hc[i].py = c[15];
+    }
+    std::vector<LoObs> ho(n_res);
+    for (uint32_t r = 0; r < n_res; ++r) {
+        const double* o = obs + 6 * (size_t)r;
+        ho[r] = LoObs{o[0], o[1], o[2], o[3], o[4], o[5], obs_cam[r], 0};
+    }
+    const std::vector<double> hx(x0, x0 + 4 * (size_t)n_lines);
+    const std::vector<uint32_t> hoff(res_off, res_off + (size_t)n_lines + 1);
+    std::vector<uint32_t> order(n_lines);
+    std::iota(order.begin(), order.end(), 0u);
+    PinnedBuf<char> hb; DevBuf<char> db;
+    uint32_t n_wide = 0;
+    const LoOut* out = nullptr;
+    if (int rc = lo_solve_lines(hb, db, 0, nullptr, hc, ho, hx, hoff, order, narrow_max, max_iter, &n_wide, &out)) return rc;
+    for (uint32_t i = 0; i < n_lines; ++i) {
+        for (int j = 0; j < 4; ++j) x_out[4 * (size_t)i + j] = out[i].x[j];
+        cost01[2 * (size_t)i] = out[i].cost0; cost01[2 * (size_t)i + 1] = out[i].cost1;
+        iters[i] = out[i].iters; status[i] = out[i].status;
+    }
+    return L3D_OK;
+}
 
 int l3d_line_opt_stats(l3d_ctx* c, l3d_line_opt_summary* out) {
     if (!c || !out) return fail(L3D_ERR_ARG, "null argument");

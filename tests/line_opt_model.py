@@ -174,3 +174,263 @@ def infinite_line(P1, P2):
     if d[np.argmax(np.abs(d))] < 0:
         d = -d
     return d, P1 - (P1 @ d) * d
+
+
+# ---- the solver -------------------------------------------------------------------------------------------------------
+# Written from the rule list of k_lineopt.hip's header comment and DESIGN §10, in the precision `dtype` (np.float64, or
+# np.longdouble as the model's own yardstick of how much rounding moves a run):
+#
+#   evaluation   residuals r_i (2 each) and their 2x4 Jacobians J_i by forward-mode derivatives; at |dotp| >= 1 the angle
+#                weight is 1 and its derivative 0.  It fails when |omega| < 1e-12 or a projected line has length < 1e-12.
+#   robust loss  Triggs: with s_i = |r_i|^2, r_i and J_i are scaled by sqrt(rho'(s_i)) (Huber: rho'' <= 0, no curvature
+#                term); cost = 1/2 sum rho(s_i); H = sum J_i^T J_i, g = sum J_i^T r_i of the scaled quantities, summed one
+#                residual after the other.
+#   scaling      Jacobi: column j by 1 / (1 + sqrt(H_jj)) of the start point, kept for the whole run.
+#   step         (A + D) y = -b with A, b the scaled H, g and D = clamp(diag A, 1e-6, 1e32) / radius, radius = 1e4 at the
+#                start, by Cholesky; model decrease = -(y.b + y.A y / 2); step = scaling * y.
+#   acceptance   gain ratio q = (cost - new cost) / model decrease > 1e-3.  Accepted: radius /= max(1/3, 1 - (2q - 1)^3),
+#                at most 1e16, decrease factor back to 2.  Rejected (also: model decrease not positive, A + D not positive
+#                definite, the new point cannot be evaluated): radius /= factor, factor *= 2.
+#   stopping     in this order within an iteration: [gradient] max |g_j| <= 1e-10, looked at once per point -- at the start
+#                and at every accepted point; [max_iter] before a step is computed, iterations (accepted and rejected
+#                alike) >= max_iter; [parameter] |step| <= 1e-8 (|x| + 1e-8), before the step is evaluated; [function]
+#                |cost - new cost| <= 1e-6 cost for every step that could be evaluated, taken or not (a taken one is taken
+#                first, and the function rule goes before the gradient rule at the new point); [other] after a rejected
+#                step, radius < 1e-32.  A start that cannot be evaluated: other, x = x0, no iteration.
+
+GRADIENT, FUNCTION, PARAMETER, MAX_ITER, OTHER = 1, 2, 3, 4, 5
+TINY = float(np.finfo(np.float64).tiny)
+
+
+class _Dual:
+    """forward-mode number over n residuals at once: a [n], d [n, 4] = derivative in the 4 line parameters"""
+    __slots__ = ("a", "d")
+    __array_ufunc__ = None          # array * _Dual is _Dual.__rmul__, not an array of objects
+
+    def __init__(self, a, d):
+        self.a, self.d = a, d
+
+    @staticmethod
+    def _lift(o, like):
+        return o if isinstance(o, _Dual) else _Dual(np.broadcast_to(np.asarray(o, like.a.dtype), like.a.shape), np.zeros_like(like.d))
+
+    def __add__(self, o):
+        o = _Dual._lift(o, self); return _Dual(self.a + o.a, self.d + o.d)
+    __radd__ = __add__
+
+    def __sub__(self, o):
+        o = _Dual._lift(o, self); return _Dual(self.a - o.a, self.d - o.d)
+
+    def __rsub__(self, o):
+        return _Dual._lift(o, self) - self
+
+    def __neg__(self):
+        return _Dual(-self.a, -self.d)
+
+    def __mul__(self, o):
+        o = _Dual._lift(o, self); return _Dual(self.a * o.a, self.a[:, None] * o.d + self.d * o.a[:, None])
+    __rmul__ = __mul__
+
+    def __truediv__(self, o):
+        o = _Dual._lift(o, self)
+        q = self.a / o.a
+        return _Dual(q, (self.d - q[:, None] * o.d) / o.a[:, None])
+
+    def sqrt(self):
+        r = np.sqrt(self.a); return _Dual(r, self.d / (2 * r)[:, None])
+
+
+def _evaluate(x, cams, obs, dtype):
+    """residuals of one line in all its observations -> (ok, r [n, 2], J [n, 2, 4]) in dtype"""
+    cams = np.asarray(cams, np.float64).reshape(-1, 16).astype(dtype); obs = np.asarray(obs, np.float64).reshape(-1, 6).astype(dtype)
+    n = len(obs)
+    x = np.asarray(x, dtype)
+    if abs(x[0]) < EPS:
+        return False, np.zeros((n, 2), dtype), np.zeros((n, 2, 4), dtype)
+    one = np.ones(n, dtype)
+    par = [_Dual(x[j] * one, np.tile(np.eye(4, dtype=dtype)[j], (n, 1))) for j in range(4)]
+    omega, s = par[0], par[1:]
+    nm = s[0] * s[0] + s[1] * s[1] + s[2] * s[2]
+    # Q = ((1 - |s|^2) I + 2 [s]x + 2 s s^T) / (1 + |s|^2): l its first column, m = omega times its second
+    l = [((1 - nm) + 2 * s[0] * s[0]) / (1 + nm), (2 * s[2] + 2 * s[1] * s[0]) / (1 + nm), (-2 * s[1] + 2 * s[2] * s[0]) / (1 + nm)]
+    m = [omega * (-2 * s[2] + 2 * s[0] * s[1]) / (1 + nm), omega * ((1 - nm) + 2 * s[1] * s[1]) / (1 + nm),
+         omega * (2 * s[0] + 2 * s[2] * s[1]) / (1 + nm)]
+    C = [cams[:, 9], cams[:, 10], cams[:, 11]]
+    mc = [m[0] - (C[1] * l[2] - C[2] * l[1]), m[1] - (C[2] * l[0] - C[0] * l[2]), m[2] - (C[0] * l[1] - C[1] * l[0])]
+    q = [cams[:, 3 * i] * mc[0] + cams[:, 3 * i + 1] * mc[1] + cams[:, 3 * i + 2] * mc[2] for i in range(3)]
+    fx, fy, px, py = cams[:, 12], cams[:, 13], cams[:, 14], cams[:, 15]
+    pl0 = fy * q[0]; pl1 = fx * q[1]; pl2 = -(fy * px) * q[0] - (fx * py) * q[1] + (fx * fy) * q[2]
+    d = (pl0 * pl0 + pl1 * pl1).sqrt()
+    if n and np.any(d.a < EPS):
+        return False, np.zeros((n, 2), dtype), np.zeros((n, 2, 4), dtype)
+    dotp = pl0 / d * obs[:, 4] + pl1 / d * obs[:, 5]
+    inside = np.abs(dotp.a) < 1                      # False for NaN too: weight 1, derivative 0
+    c = np.where(inside, dotp.a, 0 * one)
+    angle = np.arccos(c)
+    dangle = -1 / np.sqrt(1 - c * c)
+    fold = angle > dtype(np.pi) / 2
+    angle = np.where(fold, dtype(np.pi) - angle, angle)
+    dangle = np.where(fold, -dangle, dangle)
+    w = np.where(inside, np.exp(2 * angle), one)
+    aw = _Dual(w, np.where(inside, 2 * w * dangle, 0 * one)[:, None] * dotp.d)
+    r1 = (pl0 * obs[:, 0] + pl1 * obs[:, 1] + pl2) / d * aw
+    r2 = (pl0 * obs[:, 2] + pl1 * obs[:, 3] + pl2) / d * aw
+    return True, np.stack([r1.a, r2.a], 1), np.stack([r1.d, r2.d], 1)
+
+
+def jacobian(x, cam, obs):
+    """the 2x4 Jacobian of residual(x, cam, obs) in x = (omega, s), before the loss (zeros where residual() fails)"""
+    return _evaluate(x, [cam], [obs], np.float64)[2][0]
+
+
+def _seq(a):
+    """sum over axis 0, one term after the other in the array's own precision"""
+    return np.cumsum(a, axis=0)[-1] if len(a) else np.zeros(a.shape[1:], a.dtype)
+
+
+def _normal_equations(x, cams, obs, dtype):
+    """-> (ok, cost, H [4, 4], g [4]) of the Triggs-scaled problem at x"""
+    ok, r, J = _evaluate(x, cams, obs, dtype)
+    if not ok:
+        return False, dtype(np.inf), None, None
+    s = r[:, 0] * r[:, 0] + r[:, 1] * r[:, 1]
+    out = s > 4
+    root = np.sqrt(np.where(out, s, 4 + 0 * s))
+    rho = np.where(out, 4 * root - 4, s)
+    w = np.sqrt(np.where(out, 2 / root, 1 + 0 * s))            # sqrt(rho')
+    f = w[:, None] * r; Jw = w[:, None, None] * J
+    H = _seq(Jw[:, 0, :, None] * Jw[:, 0, None, :] + Jw[:, 1, :, None] * Jw[:, 1, None, :])
+    g = _seq(Jw[:, 0, :] * f[:, 0, None] + Jw[:, 1, :] * f[:, 1, None])
+    cost = _seq(rho / 2)
+    if not np.isfinite(cost):
+        return False, cost, None, None
+    return True, cost, H, g
+
+
+class _Margin:
+    """smallest relative distance of a compared quantity from its threshold over the decisions of a run"""
+
+    def __init__(self):
+        self.least = np.inf
+
+    def __call__(self, q, t):
+        self.least = min(self.least, float(abs(q - t)) / max(float(abs(t)), TINY))
+
+
+def _cholesky_solve(A, rhs, dtype, margin):
+    """y of A y = rhs for a symmetric positive definite A, else None"""
+    n = len(rhs)
+    L = np.zeros((n, n), dtype)
+    for i in range(n):
+        for j in range(i + 1):
+            v = A[i, j]
+            for k in range(j):
+                v = v - L[i, k] * L[j, k]
+            if i == j:
+                margin(v, 0.0)
+                if not v > 0:
+                    return None
+                L[i, i] = np.sqrt(v)
+            else:
+                L[i, j] = v / L[j, j]
+    z = np.zeros(n, dtype); y = np.zeros(n, dtype)
+    for i in range(n):
+        v = rhs[i]
+        for k in range(i):
+            v = v - L[i, k] * z[k]
+        z[i] = v / L[i, i]
+    for i in reversed(range(n)):
+        v = z[i]
+        for k in range(i + 1, n):
+            v = v - L[k, i] * y[k]
+        y[i] = v / L[i, i]
+    return y
+
+
+def lm_solve(x0, cams, obs, max_iter, dtype=np.float64, trace=None):
+    """Levenberg-Marquardt on one line by the rules above -> (x, cost0, cost1, iters, status, min_margin).  cams [n, 16] is
+    the camera of every observation, obs [n, 6].  min_margin: the least |q - t| / max(|t|, tiny) over the threshold
+    decisions the run took (gain ratio against 1e-3, |cost change| against 1e-6 cost, step norm against its bound,
+    gradient max-norm against 1e-10, model decrease against 0, Cholesky pivots against 0).  trace: a list that receives
+    'accepted' / 'rejected' per iteration ('stopped' for the step of the parameter rule)."""
+    margin = _Margin()
+    c = lambda v: dtype(v)
+    x = np.asarray(x0, np.float64).astype(dtype)
+    ok, cost, H, g = _normal_equations(x, cams, obs, dtype)
+    if not ok:
+        return np.asarray(x0, np.float64).copy(), float(cost), float(cost), 0, OTHER, np.inf
+    cost0 = cost
+    scale = 1 / (1 + np.sqrt(np.diag(H)))
+    radius, factor = c(1e4), c(2.0)
+    iters = 0
+
+    def finish(status):
+        return x.astype(np.float64), float(cost0), float(cost), iters, status, margin.least
+
+    gmax = np.max(np.abs(g))
+    margin(gmax, 1e-10)
+    if gmax <= c(1e-10):
+        return finish(GRADIENT)
+    while True:
+        if iters >= max_iter:
+            return finish(MAX_ITER)
+        iters += 1
+        A = scale[:, None] * H * scale[None, :]
+        b = scale * g
+        D = A + np.diag(np.minimum(np.maximum(np.diag(A), c(1e-6)), c(1e32)) / radius)
+        y = _cholesky_solve(D, -b, dtype, margin)
+        taken = False
+        if y is not None:
+            yb = c(0); yAy = c(0)
+            for p in range(4):
+                yb = yb + y[p] * b[p]
+                t = c(0)
+                for q_ in range(4):
+                    t = t + A[p, q_] * y[q_]
+                yAy = yAy + y[p] * t
+            decrease = -(yb + yAy / 2)
+            margin(decrease, 0.0)
+            if decrease > 0 and np.isfinite(decrease):
+                step = scale * y
+                ns = c(0); nx = c(0)
+                for j in range(4):
+                    ns = ns + step[j] * step[j]; nx = nx + x[j] * x[j]
+                bound = c(1e-8) * (np.sqrt(nx) + c(1e-8))
+                margin(np.sqrt(ns), bound)
+                if np.sqrt(ns) <= bound:
+                    if trace is not None:
+                        trace.append("stopped")
+                    return finish(PARAMETER)
+                xn = x + step
+                okn, costn, Hn, gn = _normal_equations(xn, cams, obs, dtype)
+                if okn:
+                    dc = cost - costn
+                    margin(abs(dc), c(1e-6) * cost)
+                    small = abs(dc) <= c(1e-6) * cost
+                    ratio = dc / decrease
+                    margin(ratio, 1e-3)
+                    if ratio > c(1e-3):
+                        x, cost, H, g = xn, costn, Hn, gn
+                        t = 2 * ratio - 1
+                        radius = min(c(1e16), radius / max(c(1.0) / c(3.0), 1 - t * t * t))
+                        factor = c(2.0)
+                        taken = True
+                        if trace is not None:
+                            trace.append("accepted")
+                        if small:
+                            return finish(FUNCTION)
+                        gmax = np.max(np.abs(g))
+                        margin(gmax, 1e-10)
+                        if gmax <= c(1e-10):
+                            return finish(GRADIENT)
+                    elif small:
+                        if trace is not None:
+                            trace.append("rejected")
+                        return finish(FUNCTION)
+        if not taken:
+            if trace is not None:
+                trace.append("rejected")
+            radius = radius / factor
+            factor = factor * 2
+            if radius < c(1e-32):
+                return finish(OTHER)

@@ -15,7 +15,7 @@ from line3dpp_amd.api import Line3D
 from line3dpp_amd.scene import make_scene
 from tests import line_opt_model as LM
 from tests import project_lines_cases as Cs
-from tests import scan_cases, seam_cases
+from tests import line_opt_cases, scan_cases, seam_cases
 from tests import triangulate_model as TM
 from tests.lsd_scenes import polygons
 
@@ -155,6 +155,12 @@ def _line_opt_eval():
                                          ptr(np.ascontiguousarray(cams, np.float64)), ptr(cost), ptr(r), ptr(J), ptr(ok)) == 0
 
 
+def _line_opt_solve():
+    b = line_opt_cases.grid_batch(1, 1)
+    x, cost0, cost1, iters, status = api.line_opt_solve(b.x0, b.res_off, b.obs, b.obs_cam, b.cams)
+    assert x.shape == (2, 4) and np.all(cost1 <= cost0)
+
+
 def _undistort():
     img = polygons(800, 600, 5)
     K = np.array([[700.0, 0, 400], [0, 700, 300], [0, 0, 1]])
@@ -163,7 +169,7 @@ def _undistort():
 
 
 @pytest.mark.parametrize("call", [_diffuse, _collinear, _score, _match_lines, _triangulate, _projection_stages, _selftests,
-                                  _line_opt_eval, _undistort], ids=lambda f: f.__name__.lstrip("_"))
+                                  _line_opt_eval, _line_opt_solve, _undistort], ids=lambda f: f.__name__.lstrip("_"))
 def test_stateless_entries_hold_nothing_afterwards(call):
     """one successful small call of each (the wrappers raise on a status other than 0)"""
     base = baseline()
