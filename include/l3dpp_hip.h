@@ -584,6 +584,33 @@ int l3d_set_timing_level(l3d_ctx*, int level);
  * the library's buffers hold right now (blocks lying in its cache are not counted): equal before and after a stateless
  * call, and before l3d_create and after l3d_destroy.  Unknown name: ~0. */
 unsigned long long l3d_debug_counter(const char* name);
+/* Test hook (device): what every stage of a detection batch left behind.  The call makes the device work of
+ * l3d_detect_segments -- the same arena, the same one launch per stage for the whole batch -- and copies out, per image,
+ * the stage maps before the arena is released.  It changes nothing in the context: the segments and statistics of the
+ * last detection stay.  The caller owns the buffers; with query_only != 0 nothing runs on the device and only the sizes
+ * below are filled, from which the caller allocates.  Every pointer may be NULL (that map is not copied).  The input
+ * checks are those of l3d_detect_segments. */
+typedef struct l3d_lsd_stages {
+    /* out: the geometry */
+    uint32_t gw, gh;                  /* image handed to LSD (after the max-width downscale) */
+    uint32_t sw, sh;                  /* after the 0.8 resample */
+    uint32_t down;                    /* 1: the 8U downscale ran */
+    uint32_t raw_cap;                 /* upper bound on raw_segments: what raw4 has to hold */
+    /* in: host buffers */
+    uint8_t* gray;                    /* rows x cols: the grey conversion */
+    uint8_t* small_gray;              /* gh x gw: after the max-width downscale (== gray without it) */
+    double* blur;                     /* gh x gw: the 7-tap Gaussian */
+    float* deg;                       /* sh x sw: fastAtan2 degrees, -1024 where the gradient is undefined */
+    double* mod;                      /* sh x sw: gradient norm */
+    float* raw4;                      /* raw_cap x (x1, y1, x2, y2): LSD's output in detection order, LSD-input pixels */
+    /* out: the kernel's result record */
+    uint32_t raw_segments, overflow;
+    uint32_t seeds, nfa_evals;
+    unsigned long long max_grad_bits; /* bits of the largest defined gradient norm (0: none defined) */
+    l3d_detect_stats stats;           /* as l3d_get_detect_stats reports the image, `segments` left 0 */
+} l3d_lsd_stages;
+int l3d_debug_lsd_stages(l3d_ctx*, uint32_t n_images, const l3d_image* images, int max_image_width, int query_only,
+                         l3d_lsd_stages* out);
 
 /* ---- (2) seam layer ------------------------------------------------------------------ */
 

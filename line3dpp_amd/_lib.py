@@ -122,6 +122,15 @@ class DetectStats(C.Structure):
                 ("max_grad", C.c_double)]
 
 
+class LsdStages(C.Structure):
+    """l3d_lsd_stages (include/l3dpp_hip.h): sizes out, host buffers in, the kernel's result record out"""
+    _fields_ = [("gw", C.c_uint32), ("gh", C.c_uint32), ("sw", C.c_uint32), ("sh", C.c_uint32), ("down", C.c_uint32),
+                ("raw_cap", C.c_uint32), ("gray", C.c_void_p), ("small_gray", C.c_void_p), ("blur", C.c_void_p),
+                ("deg", C.c_void_p), ("mod", C.c_void_p), ("raw4", C.c_void_p), ("raw_segments", C.c_uint32),
+                ("overflow", C.c_uint32), ("seeds", C.c_uint32), ("nfa_evals", C.c_uint32),
+                ("max_grad_bits", C.c_ulonglong), ("stats", DetectStats)]
+
+
 EXPORTS = [
     "l3d_last_error", "l3d_build_info", "l3d_create", "l3d_destroy", "l3d_add_view", "l3d_match_images",
     "l3d_match_begin", "l3d_num_pairs", "l3d_get_pairs", "l3d_match_pairs", "l3d_slot_buffer", "l3d_match_finish",
@@ -146,6 +155,7 @@ EXPORTS = [
     "l3d_triangulate_points", "l3d_rotation_from_rpy", "l3d_rotation_from_q", "l3d_decompose_projection_matrix",
     "l3d_project_segments", "l3d_render_line_maps", "l3d_draw_line_maps", "l3d_view_camera", "l3d_project_lines",
     "l3d_get_projected_lines", "l3d_render_lines", "l3d_draw_lines", "l3d_set_projection_budget", "l3d_selftest_scan",
+    "l3d_debug_lsd_stages",
 ]
 
 _lib = None
@@ -249,6 +259,7 @@ def load():
     L.l3d_detect_view_segments.argtypes = [vp, u32, vp, vp, C.POINTER(DetectOptions), vp]
     L.l3d_get_detected_segments.argtypes = [vp, vp, u64, C.POINTER(u64)]
     L.l3d_get_detect_stats.argtypes = [vp, vp, u32, C.POINTER(u32)]
+    L.l3d_debug_lsd_stages.argtypes = [vp, u32, vp, i32, i32, vp]
     L.l3d_add_view_image.argtypes = [vp, u32, C.POINTER(Image), C.POINTER(DetectOptions), vp, vp, vp, f32, vp, u32,
                                      C.POINTER(u32)]
     L.l3d_add_view_image_worldpoints.argtypes = [vp, u32, C.POINTER(Image), C.POINTER(DetectOptions), vp, vp, vp, f32,

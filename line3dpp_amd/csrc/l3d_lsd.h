@@ -47,7 +47,7 @@ struct LsdResult {
 };
 
 struct LsdConst {
-    double gauss[kLsdTaps];        // getGaussianKernel(7, 0.75) in double
+    double gauss[kLsdTaps];        // getGaussianKernel(7, 0.6 / 0.8) in double
     double rho;                    // gradient threshold QUANT / sin(prec)
     double prec, p;                // pi * ANG_TH / 180, ANG_TH / 180
 };

@@ -70,9 +70,11 @@ int check_geometry(const Geometry& g) {
 
 size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
-// LSD on the device for every image; raw[i] = its segments in detection order (LSD-input pixels), stats filled
+// LSD on the device for every image; raw[i] = its segments in detection order (LSD-input pixels), stats filled.
+// tap (test hook, l3d_debug_lsd_stages): one record per image whose non-null host buffers receive the stage maps, copied
+// out of the arena after the stream is synchronised and before the arena is released; nullptr: nothing extra is copied.
 int run_lsd(l3d_ctx* c, const std::vector<const l3d_image*>& ims, const std::vector<Geometry>& geo,
-            std::vector<std::vector<float4>>& raw, std::vector<l3d_detect_stats>& stats) {
+            std::vector<std::vector<float4>>& raw, std::vector<l3d_detect_stats>& stats, l3d_lsd_stages* tap = nullptr) {
     const uint32_t n = (uint32_t)ims.size();
     raw.assign(n, {});
     if (!n) return L3D_OK;
@@ -159,6 +161,19 @@ int run_lsd(l3d_ctx* c, const std::vector<const l3d_image*>& ims, const std::vec
         s.raw_segments = res[i].n; s.seeds = res[i].seeds; s.nfa_evals = res[i].nfa_evals;
         s.max_grad = -1.0;
         if (res[i].max_grad_bits) std::memcpy(&s.max_grad, &res[i].max_grad_bits, sizeof(double));
+        if (tap) {
+            l3d_lsd_stages& t = tap[i];
+            const size_t src = (size_t)ims[i]->cols * ims[i]->rows, sm = (size_t)geo[i].gw * geo[i].gh;
+            const size_t sc = (size_t)geo[i].sw * geo[i].sh;
+            const struct { void* dst; const void* from; size_t bytes; } maps[5] = {
+                {t.gray, d[i].gray, src}, {t.small_gray, d[i].small, sm}, {t.blur, d[i].blur, sm * sizeof(double)},
+                {t.deg, d[i].deg, sc * sizeof(float)}, {t.mod, d[i].mod, sc * sizeof(double)}};
+            for (const auto& m : maps)
+                if (m.dst) L3D_HIP_CHECK(hipMemcpyAsync(m.dst, m.from, m.bytes, hipMemcpyDeviceToHost, c->stream));
+            t.raw_segments = res[i].n; t.overflow = res[i].overflow;
+            t.seeds = res[i].seeds; t.nfa_evals = res[i].nfa_evals; t.max_grad_bits = res[i].max_grad_bits;
+            t.stats = s;
+        }
     }
     L3D_HIP_CHECK(hipStreamSynchronize(c->stream));
     g_lsd_images_detected += n;
@@ -253,6 +268,35 @@ int detect(l3d_ctx* c, uint32_t n, const uint32_t* cams, const l3d_image* images
         c->det_segs.insert(c->det_segs.end(), segs[i].begin(), segs[i].end());
     }
     c->det_stats = stats;
+    return L3D_OK;
+}
+
+void tap_geometry(const Geometry& g, l3d_lsd_stages& t) {
+    t.gw = g.gw; t.gh = g.gh; t.sw = g.sw; t.sh = g.sh;
+    t.down = g.down;
+    t.raw_cap = (uint32_t)((size_t)g.sw * g.sh / 2 + 1);      // LsdImage::out_cap
+}
+
+// l3d_debug_lsd_stages: detect()'s checks and its run_lsd call, with a tap and without the host's filter, order and cap
+int lsd_stages(l3d_ctx* c, uint32_t n, const l3d_image* images, int max_image_width, bool query_only, l3d_lsd_stages* out) {
+    if (!c || (n && (!images || !out))) return fail(L3D_ERR_ARG, "null argument");
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    for (uint32_t i = 0; i < n; ++i) if (int rc = check_image(images[i])) return rc;
+    std::vector<Geometry> geo(n);
+    std::vector<const l3d_image*> ims(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        geo[i] = geometry(images[i], max_image_width);
+        if (int rc = check_geometry(geo[i])) return rc;
+        ims[i] = &images[i];
+    }
+    for (uint32_t i = 0; i < n; ++i) tap_geometry(geo[i], out[i]);
+    if (query_only) return L3D_OK;
+    (void)hipSetDevice(c->device);
+    std::vector<l3d_detect_stats> stats(n, l3d_detect_stats{});
+    std::vector<std::vector<float4>> raw;
+    if (int rc = run_lsd(c, ims, geo, raw, stats, out)) return rc;
+    for (uint32_t i = 0; i < n; ++i)
+        if (out[i].raw4 && !raw[i].empty()) std::memcpy(out[i].raw4, raw[i].data(), raw[i].size() * sizeof(float4));
     return L3D_OK;
 }
 
@@ -440,6 +484,11 @@ int l3d_detect_view_segments(l3d_ctx* c, uint32_t n_images, const uint32_t* camI
                              const l3d_detect_options* opts, uint32_t* counts) {
     if (!opts || (n_images && !camIDs)) return fail(L3D_ERR_ARG, "null argument");
     return detect(c, n_images, camIDs, images, opts->max_image_width, opts->max_line_segments, opts, counts);
+}
+
+int l3d_debug_lsd_stages(l3d_ctx* c, uint32_t n_images, const l3d_image* images, int max_image_width, int query_only,
+                         l3d_lsd_stages* out) {
+    return lsd_stages(c, n_images, images, max_image_width, query_only != 0, out);
 }
 
 int l3d_get_detected_segments(l3d_ctx* c, float* segs4, uint64_t cap, uint64_t* n) {

@@ -81,6 +81,43 @@ def last_stats(L, h):
     return [{k: getattr(st[i], k) for k, _ in _lib.DetectStats._fields_ if k != "reserved"} for i in range(n.value)]
 
 
+def lsd_stages(images, max_image_width=-1, device=0):
+    """l3d_debug_lsd_stages (test hook): what every device stage of one detection batch left behind -> per image a dict
+    of gray, small (u8), blur (f64), deg (f32, -1024 = undefined), mod (f64), raw ([n,4] f32 in detection order,
+    LSD-input pixels) and the kernel's counts: raw_segments, overflow, seeds, nfa_evals, max_grad_bits, down, stats"""
+    L = _lib.load()
+    images = list(images)
+    n = len(images)
+    h = L.l3d_create(int(device), None)
+    if not h:
+        raise RuntimeError("l3d_create failed: " + _lib.last_error())
+    h = C.c_void_p(h)
+    try:
+        arr, keep = image_array(images)
+        st = (_lib.LsdStages * max(n, 1))()
+        for query in (1, 0):
+            rc = L.l3d_debug_lsd_stages(h, n, arr, int(max_image_width), query, st)
+            if rc != 0:
+                raise RuntimeError(f"l3d_debug_lsd_stages failed [{rc}]: {_lib.last_error()}")
+            if query:
+                maps = [{"gray": np.zeros((a.shape[0], a.shape[1]), np.uint8),
+                         "small": np.zeros((s.gh, s.gw), np.uint8), "blur": np.zeros((s.gh, s.gw), np.float64),
+                         "deg": np.zeros((s.sh, s.sw), np.float32), "mod": np.zeros((s.sh, s.sw), np.float64),
+                         "raw": np.zeros((s.raw_cap, 4), np.float32)} for s, a in zip(st, keep)]
+                for s, m in zip(st, maps):
+                    s.gray, s.small_gray, s.blur = m["gray"].ctypes.data, m["small"].ctypes.data, m["blur"].ctypes.data
+                    s.deg, s.mod, s.raw4 = m["deg"].ctypes.data, m["mod"].ctypes.data, m["raw"].ctypes.data
+        out = []
+        for s, m in zip(st, maps):
+            m["raw"] = m["raw"][:s.raw_segments].copy()
+            m.update({k: getattr(s, k) for k in ("raw_segments", "overflow", "seeds", "nfa_evals", "max_grad_bits", "down")})
+            m["stats"] = {k: getattr(s.stats, k) for k, _ in _lib.DetectStats._fields_ if k != "reserved"}
+            out.append(m)
+        return out
+    finally:
+        L.l3d_destroy(h)
+
+
 def distortion(K, radial, tangential):
     """l3d_distortion of undistortImage's arguments: K 3x3, radial (k1, k2, k3), tangential (p1, p2)"""
     d = _lib.Distortion()

@@ -3,7 +3,7 @@ tests/test_gpu_lsd.py), written from the contract in DESIGN §11 rather than fro
 
   gray_rgb          CV_RGB2GRAY on 8U: (R*4899 + G*9617 + B*1868 + 8192) >> 14, first channel = R
   resize_u8         INTER_LINEAR on 8U, the fixed-point form (11-bit coefficients, rounding shift by 22)
-  gauss_kernel      getGaussianKernel(7, 0.75) in double
+  gauss_kernel      getGaussianKernel(7, sigma_scale / scale) in double: 0.6 / 0.8 = 0.7499999999999999, not 0.75
   blur              separable 7-tap fp64 filter, BORDER_REFLECT_101: rows with the taps summed left to right, then
                     columns in the symmetric form (centre tap, then k[j] * (S[+j] + S[-j]))
   resize_f64        INTER_LINEAR by 0.8 on doubles (float coefficients), rows then columns
@@ -13,6 +13,8 @@ tests/test_gpu_lsd.py), written from the contract in DESIGN §11 rather than fro
                     refine / reduce_region_radius, rect_improve, rect_nfa; +0.5, /0.8, float
   detect            items 1-4 of the contract: grey, max-width downscale, LSD, upscale, length filter, priority-queue
                     order, cap
+  stages            every stage of one image on its own: grey, small, blur, float degrees, modgrad, the raw list, and the
+                    counts of the walk (seeds, nfa_evals, max_grad, which branches were taken)
 
 Pure Python region growing: small images only (a 480x360 frame takes seconds).
 """
@@ -117,7 +119,9 @@ def downscale(g, max_image_width):
 
 
 # ---- blur and the 0.8 resample ------------------------------------------------------------------------------------
-def gauss_kernel(n=7, sigma=0.75):
+def gauss_kernel(n=7, sigma=SIGMA_SCALE / SCALE):
+    """lsd_opencv.cpp:550 divides in double: sigma is one ulp under 0.75, and three of the four distinct taps differ from
+    those of 0.75 in the last place"""
     scale2x = -0.5 / (sigma * sigma)
     xs = [i - (n - 1) * 0.5 for i in range(n)]
     t = [math.exp(scale2x * x * x) for x in xs]
@@ -241,6 +245,11 @@ class LSD:
         self.used = bytearray(self.w * self.h)
         self.LOG_NT = 5 * (math.log10(float(self.w)) + math.log10(float(self.h))) / 2 + math.log10(11.0)
         self.nfa_evals = 0
+        self.seeds = 0                     # regions grown from a seed in run (not the re-grow inside refine)
+        # branches taken, for the tests that need to know a scene reaches them: refine's re-grow, reduce_region_radius,
+        # a refine that fails, and rect_improve's exits (after 1 evaluation, then after each later stage)
+        self.regrown = self.reduced = self.refine_failed = 0
+        self.improve_exits = [0] * 6
 
     def aligned(self, adr, theta, prec):
         a = self.angf[adr]
@@ -358,8 +367,10 @@ class LSD:
                 n += 1
         mean = s / float(n)
         tau = 2.0 * math.sqrt((ss - 2.0 * mean * s) / float(n) + mean * mean)
+        self.regrown += 1
         reg, reg_angle = self.region_grow(reg[0][0], reg[0][1], tau)
         if len(reg) < 2:
+            self.refine_failed += 1
             return False, reg, rec
         rec = self.region2rect(reg, reg_angle, prec, p)
         density = float(len(reg)) / (self._dist(rec.x1, rec.y1, rec.x2, rec.y2) * rec.width)
@@ -369,6 +380,7 @@ class LSD:
 
     def reduce_region_radius(self, reg, reg_angle, prec, p, rec, density):
         W = self.w
+        self.reduced += 1
         reg = list(reg)
         xc, yc = float(reg[0][0]), float(reg[0][1])
         r1 = (rec.x1 - xc) * (rec.x1 - xc) + (rec.y1 - yc) * (rec.y1 - yc)
@@ -387,6 +399,7 @@ class LSD:
                     i -= 1
                 i += 1
             if n < 2:
+                self.refine_failed += 1
                 return False, reg[:n], rec
             rec = self.region2rect(reg[:n], reg_angle, prec, p)
             density = float(n) / (self._dist(rec.x1, rec.y1, rec.x2, rec.y2) * rec.width)
@@ -473,6 +486,7 @@ class LSD:
         delta, d2 = 0.5, 0.25
         log_nfa = self.rect_nfa(rec)
         if log_nfa > LOG_EPS:
+            self.improve_exits[0] += 1
             return log_nfa, rec
         r = rec.copy()
         for _ in range(5):
@@ -482,6 +496,7 @@ class LSD:
             if v > log_nfa:
                 log_nfa, rec = v, r.copy()
         if log_nfa > LOG_EPS:
+            self.improve_exits[1] += 1
             return log_nfa, rec
         r = rec.copy()
         for _ in range(5):
@@ -491,6 +506,7 @@ class LSD:
                 if v > log_nfa:
                     rec, log_nfa = r.copy(), v
         if log_nfa > LOG_EPS:
+            self.improve_exits[2] += 1
             return log_nfa, rec
         for sign in (1.0, -1.0):
             r = rec.copy()
@@ -511,6 +527,7 @@ class LSD:
                     if v > log_nfa:
                         rec, log_nfa = r.copy(), v
             if log_nfa > LOG_EPS:
+                self.improve_exits[3 if sign > 0 else 4] += 1
                 return log_nfa, rec
         r = rec.copy()
         for _ in range(5):
@@ -520,6 +537,7 @@ class LSD:
                 v = self.rect_nfa(r)
                 if v > log_nfa:
                     rec, log_nfa = r.copy(), v
+        self.improve_exits[5] += 1
         return log_nfa, rec
 
     def run(self):
@@ -531,6 +549,7 @@ class LSD:
         for adr in range(W * self.h):          # raster order: flsd walks list[] by index
             if self.used[adr] != 0 or self.angf[adr] == NOTDEF:
                 continue
+            self.seeds += 1
             reg, reg_angle = self.region_grow(adr % W, adr // W, prec)
             if len(reg) < min_reg:
                 continue
@@ -617,3 +636,17 @@ def detect(image, max_image_width=-1, max_segments=3000):
     rows, cols = g.shape
     small, upx, upy = downscale(g, max_image_width)
     return finish(lsd(small), rows, cols, upx, upy, max_segments)
+
+
+def stages(image, max_image_width=-1):
+    """every stage of one image, as the GPU's stage hook reports them: gray, small (the image handed to LSD), blur,
+    deg (float32 degrees, NOTDEF where undefined), mod, raw (LSD's output in detection order), seeds, nfa_evals,
+    max_grad (-1: no gradient defined), upx / upy, and `walk`, the LSD object with its branch counters"""
+    image = np.asarray(image, np.uint8)
+    g = gray_rgb(image) if image.ndim == 3 else image
+    small, upx, upy = downscale(g, max_image_width)
+    b = blur(small)
+    walk = LSD(resize_f64(b))
+    raw = walk.run()
+    return {"gray": g, "small": small, "blur": b, "deg": walk.deg, "mod": walk.mod, "raw": raw, "seeds": walk.seeds,
+            "nfa_evals": walk.nfa_evals, "max_grad": walk.max_grad, "upx": upx, "upy": upy, "walk": walk}
