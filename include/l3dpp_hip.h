@@ -582,7 +582,16 @@ int l3d_set_timing_level(l3d_ctx*, int level);
  * of its support kernel (by list length; empty lists are not counted), "seam_score_unstaged_lists": lists it scored on the
  * unstaged path of the scoring kernel; "live_device_blocks", "live_pinned_blocks": blocks of device / pinned host memory
  * the library's buffers hold right now (blocks lying in its cache are not counted): equal before and after a stateless
- * call, and before l3d_create and after l3d_destroy.  Unknown name: ~0. */
+ * call, and before l3d_create and after l3d_destroy.
+ * Which forms of phase B's list pass ran (counted for the pass of a call that converged, from its flag words;
+ * cumulative, tests take differences): "lists_tier2_lists", "lists_tier4_lists", "lists_huge_lists": lists the one-wave
+ * tier handed to the two-wave tier, the four-wave tier and k_lists_huge; "lists_wide_passes", "lists_narrow_passes":
+ * converged passes that staged 256 / 128 hypotheses per wave; "edges_global_segments": segments whose more than 512
+ * candidates k_edges walked in global memory.  Passes that were REPEATED (l3d_timings.pool_retries counts them all):
+ * "lists_tier_repeats": because a tier that had been left out of the launch sequence was handed a list;
+ * "lists_huge_scratch_regrows": because the scratch of k_lists_huge was too small; "lists_cand_pool_regrows",
+ * "lists_edge_pool_regrows": because a record pool overflowed -- the candidate (or segment-header) pools of the list
+ * kernels, or only the edge / header pools of k_edges.  Unknown name: ~0. */
 unsigned long long l3d_debug_counter(const char* name);
 /* Test hook (device): what every stage of a detection batch left behind.  The call makes the device work of
  * l3d_detect_segments -- the same arena, the same one launch per stage for the whole batch -- and copies out, per image,

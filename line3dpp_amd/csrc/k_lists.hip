@@ -954,7 +954,9 @@ __device__ __forceinline__ void edges_of_segment(const PairDesc* __restrict__ pa
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    }   // (beyond the LDS capacity the passes below read the records k_cand_exact left: nothing of this wave's own)
+    } else if (lane == 0) {   // (beyond the LDS capacity the passes below read the records k_cand_exact left: nothing of this wave's own)
+        atomicAdd(&lp.flags[kFlagEdgesGlobal], 1u);   // test hook: segments that took this path (l3d_debug_counter)
+    }
     auto ij_of = [&](uint32_t y) -> uint32_t { return in_lds ? s_ij_w[y] : cand[y].ij; };
     auto sim_of = [&](uint32_t y) -> float { return in_lds ? s_sim_w[y] : cand[y].sim; };
     // inside its run: rank of an accepted pair by j, accepted pairs before it (0: it writes the header), run total
@@ -1400,7 +1402,7 @@ hipError_t launch_lists(uint32_t v0, uint32_t nv, uint32_t max_M, const ViewDev*
                         SimConst sc, ListPools lp, uint32_t* seg_of_g, HugeScratchArgs hsa, hipStream_t st) {
     if (!nv || !max_M) return hipSuccess;
     // the one-wave tier stages 128 hypotheses (8 waves per SIMD) unless the scene's lists are long on average
-    const bool wide = hsa.mean_list > 96;
+    const bool wide = hsa.mean_list > kWideMeanList;
 #define L3D_LISTS(B)                                                                                                       \
     do {                                                                                                                   \
         const size_t lds1 = ListCfg<1, B>::BYTES, lds2 = ListCfg<2, B>::BYTES, lds4 = ListCfg<4, B>::BYTES;                \

@@ -175,6 +175,8 @@ unsigned long long l3d_debug_counter(const char* name) {
                                                 "seam_support_sort_only_lists", "seam_support_all_pairs_lists"};
     for (int i = 0; i < 4; ++i)
         if (name && std::string(name) == kSeamSupport[i]) return g_seam_support_lists[i].load(std::memory_order_relaxed);
+    for (uint32_t i = 0; i < kLcCount; ++i)
+        if (name && std::string(name) == kListCounterNames[i]) return g_list_counters[i].load(std::memory_order_relaxed);
     if (name && std::string(name) == "seam_score_unstaged_lists") return g_seam_score_unstaged_lists.load(std::memory_order_relaxed);
     return ~0ull;
 }

@@ -263,6 +263,7 @@ struct l3d_ctx {
     uint32_t lp_attempts = 0;
     bool huge_skip = false, huge_ran = true;        // k_lists_huge left out while the passes hand it no lists
     bool list4_skip = false, list4_ran = true;      // the same for the four-wave tier k_lists<4>
+    bool lists_wide = false;                        // the last list pass staged 256 hypotheses per wave (launch_lists)
     // The pool capacities (and huge_skip) are kept across calls, separately for unsharded calls [0] and for calls whose
     // list pass is sharded over ranks [1]: the slabs the ranks all-gather must have one size on every rank, and the
     // sharded set only ever changes by decisions every rank takes alike (check_pass sees all ranks' counters), whatever

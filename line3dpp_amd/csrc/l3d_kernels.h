@@ -12,6 +12,11 @@ extern std::atomic<uint64_t> g_knn_replay_calls;      // l3d_api.hip
 extern std::atomic<uint64_t> g_keep_all_repeats;      // l3d_api.hip
 extern std::atomic<uint64_t> g_live_blocks[2];        // l3d_api.hip
 extern std::atomic<uint64_t> g_csr_global_launches;   // k_lists.hip, test hook read through l3d_debug_counter
+// l3d_phase_b.hip, test hooks: which forms of the list pass ran (names: kListCounterNames, same order)
+enum ListCounter : uint32_t { kLcTier2Lists = 0, kLcTier4Lists, kLcHugeLists, kLcWidePasses, kLcNarrowPasses, kLcTierRepeats,
+                              kLcHugeScratchRegrows, kLcEdgesGlobalSegments, kLcCandPoolRegrows, kLcEdgePoolRegrows, kLcCount };
+extern std::atomic<uint64_t> g_list_counters[kLcCount];
+extern const char* const kListCounterNames[kLcCount];
 // l3d_seam.hip, test hooks: lists l3d_score_matches sent down each path of k_support / k_score_all (k_views.hip)
 extern std::atomic<uint64_t> g_seam_support_lists[4];  // indexed by SupportTier - 1
 extern std::atomic<uint64_t> g_seam_score_unstaged_lists;
@@ -167,6 +172,8 @@ hipError_t launch_prep_views(const ViewDev* views, uint32_t n_views, uint32_t ma
 
 // ---- k_lists.hip: the sparse phase B (l3d_lists.h) ----
 struct InvRec; struct ListPools; struct PairCsr;
+constexpr uint32_t kWideMeanList = 96;      // a pass whose mean list length lies above stages 256 hypotheses per wave, else 128
+constexpr uint32_t kFlagEdgesGlobal = 8;    // word of the pass' flag block: segments whose candidates k_edges walked in global memory
 struct HugeScratchArgs { float* f32; uint32_t* u32; uint64_t* u64; uint32_t cap; uint32_t mean_list; uint32_t run_huge; uint32_t run_tier4; };   // [2 cap] [3 cap] [cap]; mean list length (estimate); which of the rarely needed tiers are launched
 hipError_t launch_scan64(const unsigned long long* in, uint32_t n, unsigned long long* out, unsigned long long* tmp,
                          unsigned long long* total, hipStream_t st);

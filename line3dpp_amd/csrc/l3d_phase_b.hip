@@ -4,6 +4,14 @@
 // (l3d_plan_shards).  Split from l3d_api.hip (context, views, l3d_match_begin, phase A).
 #include "l3d_ctx.h"
 
+namespace l3d {
+// test hooks (l3d_debug_counter): which forms of the list pass ran, process-wide and cumulative
+std::atomic<uint64_t> g_list_counters[kLcCount];
+const char* const kListCounterNames[kLcCount] = {"lists_tier2_lists", "lists_tier4_lists", "lists_huge_lists", "lists_wide_passes",
+                                                 "lists_narrow_passes", "lists_tier_repeats", "lists_huge_scratch_regrows",
+                                                 "edges_global_segments", "lists_cand_pool_regrows", "lists_edge_pool_regrows"};
+}  // namespace l3d
+
 extern "C" {
 
 // phase B: line3D.cc:745-773 for every view in ascending camID order (k_lists.hip)
@@ -308,7 +316,14 @@ static int lists_prepare(l3d_ctx* c, int caps_mode) {
         c->lp_ccap = (uint32_t)std::max<double>(gen * ns / 2 / kListPools, scale < 1.0 ? 32 : 1024);
     }
     c->lp_scap = std::max<uint32_t>(c->lp_scap, G / kListPools + 64);   // 30-50 % of the segments have candidates; grows on demand
-    if (!c->huge_cap) c->huge_cap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(c->n_slots / 16, 1u << 20), 1u << 30);
+    if (!c->huge_cap) {
+        // (L3D_POOL_SCALE < 1 also shrinks the scratch of k_lists_huge, whose floor no small scene outgrows: its regrow in
+        // check_pass can then be exercised at any scene size)
+        const char* e = std::getenv("L3D_POOL_SCALE");
+        const double scale = e ? std::atof(e) : 1.0;
+        if (scale > 0.0 && scale < 1.0) c->huge_cap = (uint32_t)std::min<double>(std::max<double>(scale * (double)c->n_slots / 16, 2048.0), (double)(1u << 30));
+        else c->huge_cap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(c->n_slots / 16, 1u << 20), 1u << 30);
+    }
     return L3D_OK;
 }
 
@@ -368,6 +383,7 @@ static int lists_run(l3d_ctx* c, uint32_t v0, uint32_t nv, uint32_t pool0, uint3
     const HugeScratchArgs hsa{c->d_huge_f32.p, c->d_huge_u32.p, (uint64_t*)c->d_huge_u64.p, c->huge_cap, mean_list,
                               c->huge_skip ? 0u : 1u, c->list4_skip ? 0u : 1u};
     c->huge_ran = !c->huge_skip; c->list4_ran = !c->list4_skip;
+    c->lists_wide = mean_list > kWideMeanList;
     uint32_t max_M = 0;
     for (uint32_t vi = v0; vi < v0 + nv; ++vi) max_M = std::max(max_M, c->order[vi]->M);
     L3D_HIP_CHECK(launch_lists(v0, nv, max_M, c->d_views.p, c->d_pairs.p, lviews, opairs, ipairs, c->d_gseg_view.p,
@@ -491,7 +507,7 @@ static int check_pass(l3d_ctx* c) {
     const bool huge_missed = (fl[5] && !c->huge_ran) || (fl[4] && !c->list4_ran);   // (the same for the four-wave tier: flags[4])
     c->huge_skip = fl[5] == 0 && c->shard_world <= 1;
     c->list4_skip = fl[4] == 0 && c->shard_world <= 1;
-    if (huge_missed) { ++c->tm.pool_retries; return kRetry; }
+    if (huge_missed) { ++c->tm.pool_retries; g_list_counters[kLcTierRepeats].fetch_add(1, std::memory_order_relaxed); return kRetry; }
     if (fl[3]) return fail(L3D_ERR_HIP, "internal error: hypothesis counters and slot flags disagree");
     if (fl[0] || fl[2]) {
         ++c->tm.pool_retries;
@@ -504,10 +520,12 @@ static int check_pass(l3d_ctx* c) {
                 ms = std::max(ms, std::max(h[q * 16 + 2], h[q * 16 + 4])); mc = std::max(mc, h[q * 16 + 3]);
             }
             const bool cands_over = mc > c->lp_ccap || ms > c->lp_scap;
+            g_list_counters[cands_over ? kLcCandPoolRegrows : kLcEdgePoolRegrows].fetch_add(1, std::memory_order_relaxed);
             c->lp_ccap = std::max(c->lp_ccap, mc + mc / 2 + 64); c->lp_scap = std::max(c->lp_scap, ms + ms / 2 + 64);
             c->lp_ecap = std::max(cands_over ? 2 * c->lp_ecap : c->lp_ecap, me + me / 2 + 64);
             c->lp_hcap = std::max(cands_over ? 2 * c->lp_hcap : c->lp_hcap, mh + mh / 2 + 64);
         }
+        if (fl[2]) g_list_counters[kLcHugeScratchRegrows].fetch_add(1, std::memory_order_relaxed);
         if (fl[2]) c->huge_cap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(2ull * c->huge_cap, fl[6] + 1024ull), 1u << 31);
         return kRetry;
     }
@@ -531,6 +549,14 @@ static int finish_commit(l3d_ctx* c) {
         c->tm.list_candidates = (uint32_t)std::min<uint64_t>(cands, 0xFFFFFFFFu);
         c->tm.list_headers = (uint32_t)std::min<uint64_t>(hdrs, 0xFFFFFFFFu);
         c->tm.slots_lo = (uint32_t)c->n_slots; c->tm.slots_hi = (uint32_t)(c->n_slots >> 32);
+    }
+    {   // which forms of the list pass the converged pass took (l3d_debug_counter)
+        const uint32_t* hf = h + kListPools * 16;                         // flags
+        g_list_counters[kLcTier2Lists].fetch_add(hf[7], std::memory_order_relaxed);
+        g_list_counters[kLcTier4Lists].fetch_add(hf[4], std::memory_order_relaxed);
+        g_list_counters[kLcHugeLists].fetch_add(hf[5], std::memory_order_relaxed);
+        g_list_counters[c->lists_wide ? kLcWidePasses : kLcNarrowPasses].fetch_add(1, std::memory_order_relaxed);
+        g_list_counters[kLcEdgesGlobalSegments].fetch_add(hf[kFlagEdgesGlobal], std::memory_order_relaxed);
     }
     for (uint32_t s2 = 0; s2 < c->chain_enqueued; ++s2) c->tm.chain_sweeps += changed[s2] ? 1u : 0u;   // of the last round
     c->chain_need = c->tm.chain_extra_rounds ? kChainSweeps : c->tm.chain_sweeps;

@@ -267,3 +267,43 @@ def gap_scene(world, n_segs, seed=0):
             views.append(v)
     views.sort(key=lambda v: v.cam)
     return Scene(views, f"gap{world}")
+
+
+def sharded_list_pass(sc, world, **match_kw):
+    """Phase B's list pass sharded by views (l3d_lists_shard, line3dpp_amd/dist.py) without a process group: `world`
+    contexts on one GPU; every context holds all slots (as after the slot exchange), runs the list pass for ITS views into
+    ITS pools, the pool slabs are copied where the all-gather would put them, and every context finishes on the complete
+    records (repeating the step while the ranks report enlarged pools).  Returns the contexts after l3d_match_finish."""
+    import torch
+    from line3dpp_amd import dist
+    from line3dpp_amd.api import Line3D
+    dev = torch.device("cuda", 0)
+    ctxs = []
+    for _ in range(world):
+        g = Line3D()
+        g.add_scene(sc)
+        assert g.matchBegin(**match_kw) and g.matchPairs(0, len(g.pairs()[0]))
+        ctxs.append(g)
+    for attempt in range(8):
+        slabs = []
+        for r, g in enumerate(ctxs):
+            sl = g.listsShard(r, world)
+            assert sl is not None and len(sl) == 4
+            slabs.append(sl)
+        for k in range(4):
+            sizes = {sl[k][1] for sl in slabs}
+            assert len(sizes) == 1, "equal slab sizes on every rank"
+            sb = sizes.pop()
+            fulls = [dist.device_tensor(sl[k][2], sb * world, dev) for sl in slabs]
+            for r in range(world):
+                assert slabs[r][k][0] == slabs[r][k][2] + r * sb
+                for q in range(world):
+                    if q != r:
+                        fulls[q][r * sb:(r + 1) * sb].copy_(fulls[r][r * sb:(r + 1) * sb])
+        torch.cuda.synchronize()
+        rcs = [g.L.l3d_match_finish(g.h) for g in ctxs]
+        assert len(set(rcs)) == 1, "every rank takes the same decision (all of them see all pool counters)"
+        if rcs[0] == 0:
+            return ctxs
+        assert rcs[0] == -10, rcs               # L3D_ERR_RETRY: pools enlarged on every rank alike, repeat the step
+    raise AssertionError("the pools never became large enough")

@@ -763,15 +763,23 @@ def test_collinearity_links_and_lines():
 
 
 @pytest.mark.parametrize("n_views,n_segs,nn,kNN,epi,seed,rf,min_avg", [
-    (18, 300, 16, 30, 0.1, 71, 0.5, 50),       # ~200 lists beyond one wave's staging (192), longest ~360
-    (12, 1100, 11, 80, 0.05, 73, 0.9, 200),    # thousands of long lists, some beyond 768 (sort-only path)
+    (18, 300, 16, 30, 0.1, 71, 0.5, 50),       # 379 lists beyond one wave's staging (256), longest 418
+    (12, 1100, 11, 80, 0.05, 73, 0.9, 200),    # thousands of long lists, some beyond the two-wave tier (512)
 ])
 def test_long_hypothesis_lists_parity(n_views, n_segs, nn, kNN, epi, seed, rf, min_avg):
-    """Many neighbours / large kNN make per-segment hypothesis lists longer than one wave's LDS staging (192):
-    the workgroup-per-list support kernel (staged up to 768, sort-only beyond) against the oracle, full pipeline."""
+    """Many neighbours / large kNN make per-segment hypothesis lists longer than one wave's LDS staging.  Both scenes
+    estimate a mean list length above 96 on their first call, so a wave stages 256 hypotheses (ListCfg<WPL, 256>: one wave
+    up to 256, two waves up to 512, four up to 1024, k_lists_huge beyond): the multi-wave tiers against the oracle, full
+    pipeline.  The first scene hands lists to the two-wave tier, the second also to the four-wave tier or beyond."""
+    from tests import lists_cases as LC
     sc = make_scene(n_views, n_segs, n_neighbors=nn, seed=seed, real_fraction=rf)
     g = _gpu(sc)
+    before = LC.read_counters()
     assert g.matchImages(kNN=kNN, epipolar_overlap=epi) and g.computeAffinity()
+    dc = LC.counters_since(before)
+    assert dc["lists_wide_passes"] == 1 and dc["lists_tier2_lists"] >= 1, dc
+    if n_segs > 1000:
+        assert dc["lists_tier4_lists"] + dc["lists_huge_lists"] >= 1, dc
     tm = g.timings()
     assert tm["list_entries"] / (n_views * n_segs) > min_avg
     o = _oracle(sc, threads=16)
@@ -890,41 +898,12 @@ def test_sharded_list_pass_emulated_on_one_gpu(world):
     context holds all slots (as after the slot exchange), runs the list pass for ITS views into ITS pools, the pool
     slabs are copied where the all-gather would put them, and every context finishes on the complete records.
     Surviving matches, best hypotheses, view medians and A_ must equal a single context's, byte for byte."""
-    import torch
-    from line3dpp_amd import dist
     sc = H.split_scene(make_scene(11, 420, n_neighbors=6, seed=29))
     for i, v in enumerate(sc.views):                 # ragged views: view ranges of unequal length
         v.segs = v.segs[:len(v.segs) - 9 * i].copy()
     ref = _gpu(sc)
     assert ref.matchImages() and ref.computeAffinity()
-    dev = torch.device("cuda", 0)
-    ctxs = [_gpu(sc) for _ in range(world)]
-    for g in ctxs:
-        assert g.matchBegin() and g.matchPairs(0, len(g.pairs()[0]))
-    for attempt in range(8):
-        slabs = []
-        for r, g in enumerate(ctxs):
-            sl = g.listsShard(r, world)
-            assert sl is not None and len(sl) == 4
-            slabs.append(sl)
-        for k in range(4):
-            sizes = {sl[k][1] for sl in slabs}
-            assert len(sizes) == 1, "equal slab sizes on every rank"
-            sb = sizes.pop()
-            fulls = [dist.device_tensor(sl[k][2], sb * world, dev) for sl in slabs]
-            for r in range(world):
-                assert slabs[r][k][0] == slabs[r][k][2] + r * sb
-                for q in range(world):
-                    if q != r:
-                        fulls[q][r * sb:(r + 1) * sb].copy_(fulls[r][r * sb:(r + 1) * sb])
-        torch.cuda.synchronize()
-        rcs = [g.L.l3d_match_finish(g.h) for g in ctxs]
-        assert len(set(rcs)) == 1, "every rank takes the same decision (all of them see all pool counters)"
-        if rcs[0] == 0:
-            break
-        assert rcs[0] == -10, rcs               # L3D_ERR_RETRY: pools enlarged on every rank alike, repeat the step
-    else:
-        raise AssertionError("the pools never became large enough")
+    ctxs = H.sharded_list_pass(sc, world)
     for g in ctxs:
         assert g.computeAffinity()
         for v in sc.views:
