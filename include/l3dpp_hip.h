@@ -591,8 +591,31 @@ int l3d_set_timing_level(l3d_ctx*, int level);
  * "lists_tier_repeats": because a tier that had been left out of the launch sequence was handed a list;
  * "lists_huge_scratch_regrows": because the scratch of k_lists_huge was too small; "lists_cand_pool_regrows",
  * "lists_edge_pool_regrows": because a record pool overflowed -- the candidate (or segment-header) pools of the list
- * kernels, or only the edge / header pools of k_edges.  Unknown name: ~0. */
+ * kernels, or only the edge / header pools of k_edges.
+ * Which form a launch of the bounded-kNN pair kernel took (one count per launch of the staged kernel -- not the
+ * brute-force hook, not the keep-all passes, not a call that replays every row): "match_tile_launches": the tile form,
+ * 16 rows per item; "match_row2_launches": row form, two waves per item; "match_row2_cached_launches": the same with the
+ * source-row cache in LDS (the launches k_order_items orders); "match_row1_launches": row form, one wave per item;
+ * "match_ix32_launches": launches, of any of the four, whose LDS tables hold 32-bit indices (a target view of 65 536
+ * segments or more); "match_order_launches": launches of k_order_items.  Unknown name: ~0. */
 unsigned long long l3d_debug_counter(const char* name);
+/* Test hook (host only, no device, no context): the form a launch of the bounded-kNN pair kernel takes and what
+ * l3d_match_begin decides for the call it belongs to, computed by the functions the library itself calls.  total_items:
+ * work items of the whole call (all pairs); launch_items: work items of one l3d_match_pairs range, 1 .. total_items; kNN
+ * >= 1; max_target_segments: the largest target view (from 65 536 on the tables hold 32-bit indices); tile_rows: 16 = the
+ * call is in the tile form, 0 = in the row form (l3d_match_tile_rows tells which, from the estimate below). */
+typedef struct l3d_match_plan_info {
+    uint32_t tier;             /* 0 tile form, 1 row form with two waves per item, 2 the same with the row cache, 3 one wave per item */
+    uint32_t waves, row_cache, ix16;
+    uint64_t lds_bytes;        /* dynamic LDS the launch asks for */
+    uint32_t replay;           /* 1: l3d_match_begin sends every row of the call through the exact replay (no such launch is made) */
+    uint32_t launch_accepted;  /* 0: l3d_match_pairs refuses this launch with L3D_ERR_LIMIT unless the call replays */
+} l3d_match_plan_info;
+int l3d_match_plan(uint64_t total_items, uint32_t launch_items, uint32_t kNN, uint32_t max_target_segments, uint32_t tile_rows,
+                   l3d_match_plan_info* out);
+/* ... and the form l3d_match_begin chooses for a bounded-kNN call: 16 (tile form) or 0 (row form), from est_row_items = half
+ * the sum over the views of (visual neighbours x ceil(segments / 64)), rounded up.  L3D_MATCH_TILE=0|16 overrides. */
+uint32_t l3d_match_tile_rows(uint64_t est_row_items);
 /* Test hook (device): what every stage of a detection batch left behind.  The call makes the device work of
  * l3d_detect_segments -- the same arena, the same one launch per stage for the whole batch -- and copies out, per image,
  * the stage maps before the arena is released.  It changes nothing in the context: the segments and statistics of the

@@ -66,6 +66,12 @@ class Timings(C.Structure):
                 ("slots_lo", C.c_uint32), ("slots_hi", C.c_uint32)]
 
 
+class MatchPlanInfo(C.Structure):
+    """l3d_match_plan_info (include/l3dpp_hip.h)"""
+    _fields_ = [("tier", C.c_uint32), ("waves", C.c_uint32), ("row_cache", C.c_uint32), ("ix16", C.c_uint32),
+                ("lds_bytes", C.c_uint64), ("replay", C.c_uint32), ("launch_accepted", C.c_uint32)]
+
+
 class LineOptStats(C.Structure):
     """l3d_line_opt_summary (include/l3dpp_hip.h)"""
     _fields_ = [("lines_bundled", C.c_uint32), ("lines_constant", C.c_uint32), ("lines_dropped", C.c_uint32),
@@ -155,7 +161,7 @@ EXPORTS = [
     "l3d_triangulate_points", "l3d_rotation_from_rpy", "l3d_rotation_from_q", "l3d_decompose_projection_matrix",
     "l3d_project_segments", "l3d_render_line_maps", "l3d_draw_line_maps", "l3d_view_camera", "l3d_project_lines",
     "l3d_get_projected_lines", "l3d_render_lines", "l3d_draw_lines", "l3d_set_projection_budget", "l3d_selftest_scan",
-    "l3d_debug_lsd_stages",
+    "l3d_debug_lsd_stages", "l3d_match_plan", "l3d_match_tile_rows",
 ]
 
 _lib = None
@@ -222,6 +228,8 @@ def load():
     L.l3d_set_timing_level.argtypes = [vp, C.c_int]
     L.l3d_debug_counter.argtypes = [C.c_char_p]
     L.l3d_debug_counter.restype = C.c_ulonglong
+    L.l3d_match_plan.argtypes = [u64, u32, u32, u32, u32, C.POINTER(MatchPlanInfo)]
+    L.l3d_match_tile_rows.argtypes = [u64]; L.l3d_match_tile_rows.restype = u32
     L.l3d_tail_shard_count.argtypes = [vp, vp]
     L.l3d_tail_shard_layout.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp]
     L.l3d_tail_shard_commit.argtypes = [vp]

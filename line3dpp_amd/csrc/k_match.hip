@@ -1010,6 +1010,31 @@ uint32_t match_waves_per_group(int mode, bool brute, uint32_t nwork) {
     return nwork <= kMatchOrderMaxItems ? 2u : 1u;
 }
 
+MatchPlan match_launch_plan(int mode, bool brute, uint32_t nwork, uint32_t K, uint32_t max_Mt, uint32_t tile_rows) {
+    MatchPlan p;
+    // 16-bit indices in the kernel's LDS tables (top bit of a row's minpos: tie flag); only the hot variant has the compact layout
+    p.ix16 = mode == 0 && !brute && max_Mt < 65536u && K < 32768u;
+    p.waves = tile_rows ? 1u : match_waves_per_group(mode, brute, nwork);
+    p.row_cache = match_row_cache(mode, brute, nwork, tile_rows);
+    p.tier = tile_rows ? kMatchTierTile : p.waves == 1 ? kMatchTierRow1 : p.row_cache ? kMatchTierRow2Cached : kMatchTierRow2;
+    p.lds = match_lds_bytes(mode, K, p.ix16, p.waves, brute, tile_rows, p.row_cache);
+    return p;
+}
+
+// The tier of a launch follows from ITS item count, and l3d_match_pairs may launch any range of the pair list: the decision
+// holds for the strictest tier an item count of at most total_items reaches (the tiers change at kMatchOrderMinItems and
+// kMatchOrderMaxItems: the call's own count and both sides of every edge below it are tried).
+bool match_knn_replay(bool brute, uint32_t K, uint32_t max_Mt, uint64_t total_items, uint32_t tile_rows) {
+    const uint32_t total = (uint32_t)std::min<uint64_t>(total_items, 0xFFFFFFFFu);
+    size_t worst = 0;
+    for (uint32_t n : {total, kMatchOrderMinItems, kMatchOrderMinItems + 1, kMatchOrderMaxItems, kMatchOrderMaxItems + 1})
+        if (n && n <= total) worst = std::max(worst, match_launch_plan(0, brute, n, K, max_Mt, tile_rows).lds);
+    return worst > kMatchLdsLimit;
+}
+
+std::atomic<uint64_t> g_match_tier_launches[kMatchTierCount + 1];
+std::atomic<uint64_t> g_match_order_launches{0};
+
 hipError_t launch_match_pairs(int mode, bool brute, const ViewDev* views, const PairDesc* pairs,
                               const WorkItem* work, uint32_t nwork, uint32_t maxK, Slot* slots,
                               uint32_t* row_counts, float thr, CullPools pools, OrientFuse of, bool ix16,
@@ -1041,6 +1066,11 @@ hipError_t launch_match_pairs(int mode, bool brute, const ViewDev* views, const 
     else if (mode == 1) { if (brute) L3D_LAUNCH(1, true, false, 1, 0); else L3D_LAUNCH(1, false, false, 1, 0); }
     else { if (brute) L3D_LAUNCH(2, true, false, 1, 0); else L3D_LAUNCH(2, false, false, 1, 0); }
 #undef L3D_LAUNCH
+    if (mode == 0 && !brute) {   // test hooks: which form of the staged bounded-kNN kernel this launch took
+        const MatchTier tier = tile_rows ? kMatchTierTile : wpg == 1 ? kMatchTierRow1 : pools.row_cache ? kMatchTierRow2Cached : kMatchTierRow2;
+        g_match_tier_launches[tier].fetch_add(1, std::memory_order_relaxed);
+        if (!ix16) g_match_tier_launches[kMatchTierCount].fetch_add(1, std::memory_order_relaxed);
+    }
     return hipGetLastError();
 }
 
@@ -1368,6 +1398,7 @@ hipError_t launch_order_items(const PairDesc* pairs, uint32_t first, uint32_t co
     hipError_t e = hipFuncSetAttribute((const void*)k_order_items, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_order_items, dim3(count), dim3(kCullBlock), lds, stream, pairs, first, pools, nwork);
+    g_match_order_launches.fetch_add(1, std::memory_order_relaxed);
     return hipGetLastError();
 }
 

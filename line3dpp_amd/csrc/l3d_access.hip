@@ -178,8 +178,29 @@ unsigned long long l3d_debug_counter(const char* name) {
     for (uint32_t i = 0; i < kLcCount; ++i)
         if (name && std::string(name) == kListCounterNames[i]) return g_list_counters[i].load(std::memory_order_relaxed);
     if (name && std::string(name) == "seam_score_unstaged_lists") return g_seam_score_unstaged_lists.load(std::memory_order_relaxed);
+    static const char* const kMatchTiers[kMatchTierCount + 1] = {"match_tile_launches", "match_row2_launches", "match_row2_cached_launches",
+                                                                 "match_row1_launches", "match_ix32_launches"};
+    for (uint32_t i = 0; i <= kMatchTierCount; ++i)
+        if (name && std::string(name) == kMatchTiers[i]) return g_match_tier_launches[i].load(std::memory_order_relaxed);
+    if (name && std::string(name) == "match_order_launches") return g_match_order_launches.load(std::memory_order_relaxed);
     return ~0ull;
 }
+
+// test hook (host only): the form a bounded-kNN launch takes and what l3d_match_begin decides for its call, from the
+// very functions run_match_kernel and match_begin_body call (k_match.hip)
+int l3d_match_plan(uint64_t total_items, uint32_t launch_items, uint32_t kNN, uint32_t max_target_segments, uint32_t tile_rows,
+                   l3d_match_plan_info* out) {
+    if (!out || (tile_rows != 0 && tile_rows != 16) || !launch_items || launch_items > total_items || !kNN)
+        return fail(L3D_ERR_ARG, "l3d_match_plan: tile_rows 0 or 16, 1 <= launch_items <= total_items, kNN >= 1");
+    const MatchPlan p = match_launch_plan(0, false, launch_items, kNN, max_target_segments, tile_rows);
+    out->tier = (uint32_t)p.tier; out->waves = p.waves; out->row_cache = p.row_cache ? 1u : 0u; out->ix16 = p.ix16 ? 1u : 0u;
+    out->lds_bytes = p.lds;
+    out->replay = match_knn_replay(false, kNN, max_target_segments, total_items, tile_rows) ? 1u : 0u;
+    out->launch_accepted = p.fits() ? 1u : 0u;   // (run_match_kernel refuses the launch otherwise: L3D_ERR_LIMIT)
+    return L3D_OK;
+}
+
+uint32_t l3d_match_tile_rows(uint64_t est_row_items) { return match_tile_rows(0, false, est_row_items); }
 
 int l3d_set_timing_level(l3d_ctx* c, int level) {
     if (!c || level < 0 || level > 2) return fail(L3D_ERR_ARG, "l3d_set_timing_level: level 0, 1 or 2");

@@ -706,11 +706,9 @@ static int match_begin_body(l3d_ctx* c) {
         // bounded kNN keeps the per-row top-K tables of 64 rows in LDS (k_match.hip): the real limit of this build
         size_t n_work = 0; uint32_t maxMt = 0;
         for (auto& pd : c->pairs) { n_work += match_items(c, pd.Ms); maxMt = std::max(maxMt, pd.Mt); }
-        const uint32_t wpg = match_waves_per_group(0, c->brute, (uint32_t)std::min<size_t>(n_work, 0xFFFFFFFFu));
-        auto fits = [&](uint32_t K) { return match_lds_bytes(0, K, maxMt < 65536u && K < 32768u && !c->brute, wpg, c->brute, c->tile_rows,
-                                                           match_row_cache(0, c->brute, (uint32_t)std::min<size_t>(n_work, 0xFFFFFFFFu), c->tile_rows)) <= 160 * 1024; };
-        // beyond that, every row takes the exact replay path (k_match_tied_rows): slower per row, any kNN <= 4096
-        c->knn_replay = !fits((uint32_t)c->kNN);
+        // beyond that, every row takes the exact replay path (k_match_tied_rows): slower per row, any kNN <= 4096.  Decided for
+        // every launch l3d_match_pairs can make of this pair list (match_knn_replay, k_match.hip), not for the whole list alone.
+        c->knn_replay = match_knn_replay(c->brute, (uint32_t)c->kNN, maxMt, n_work, c->tile_rows);
         if (c->knn_replay) l3d::g_knn_replay_calls.fetch_add(1, std::memory_order_relaxed);
     } else c->knn_replay = false;
     c->cull_tot[0] = cs_off; c->cull_tot[1] = ct_off; c->cull_tot[2] = ck_off; c->cull_tot[3] = cc_off;
@@ -809,8 +807,9 @@ static int run_match_kernel(l3d_ctx* c, int mode, uint32_t first, uint32_t count
         maxMt = std::max(maxMt, pd.Mt);
     }
     const bool replay_all = mode == 0 && c->knn_replay;   // kNN beyond the LDS tables: every row through k_match_tied_rows
-    if (!replay_all && match_lds_bytes(mode, maxK, false, match_waves_per_group(mode, c->brute, (uint32_t)n_work), c->brute, tile,
-                                       match_row_cache(mode, c->brute, (uint32_t)n_work, tile)) > 160 * 1024)
+    // (the launch's own form and index width: what launch_match_pairs will ask for)
+    const MatchPlan plan = match_launch_plan(mode, c->brute, (uint32_t)n_work, maxK, maxMt, tile);
+    if (!replay_all && !plan.fits())
         return fail(L3D_ERR_LIMIT, "kNN too large for the LDS top-K table");
     L3D_HIP_CHECK(c->d_work.reserve(n_work));
     // the work list of these pairs is on the device already when the pair list has not changed since it was sent
@@ -853,7 +852,7 @@ static int run_match_kernel(l3d_ctx* c, int mode, uint32_t first, uint32_t count
         L3D_HIP_CHECK(launch_order_items(c->d_pairs.p, first, count, maxMt, pools, (uint32_t)n_work, c->stream));
     }
     if (c->ev_on(4)) L3D_HIP_CHECK(hipEventRecord(c->ev[4], c->stream));
-    const bool ix16 = maxMt < 65536u && maxK < 32768u;   // 16-bit indices in the kernel's LDS tables (top bit of a row's minpos: tie flag)
+    const bool ix16 = plan.ix16;   // 16-bit indices in the kernel's LDS tables (top bit of a row's minpos: tie flag)
     // bounded kNN: the orientation filter of phase B is fused into the epilogue
     OrientFuse of{mode == 0 ? c->d_inv_tgt.p : nullptr, c->tgt16, OrientThr{c->orient_lo, c->orient_hi}, nullptr, nullptr, 0u, nullptr, nullptr,
                   mode == 0 ? c->d_hyp_p.p : nullptr, mode == 0 ? c->d_hyp_q.p : nullptr};

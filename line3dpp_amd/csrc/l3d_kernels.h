@@ -134,6 +134,20 @@ bool match_row_cache(int mode, bool brute, uint32_t nwork, uint32_t tile_rows); 
 constexpr uint32_t kMatchOrderMaxItems = 16384;   // launches up to this many work items: two waves per item
 constexpr uint32_t kMatchOrderMinItems = 3584;    // ... and, from this many on (more waves than wave slots), longest-first order
 uint32_t match_waves_per_group(int mode, bool brute, uint32_t nwork);   // waves that share one 64-row work item of k_match_pairs
+// The form a launch of k_match_pairs takes, from the functions above: what run_match_kernel checks before it
+// launches, what the replay decision of l3d_match_begin is taken from, and what l3d_match_plan shows to the tests.
+constexpr size_t kMatchLdsLimit = 160 * 1024;     // LDS of a CU: the top-K tables of a work item must fit
+enum MatchTier : uint32_t { kMatchTierTile = 0, kMatchTierRow2, kMatchTierRow2Cached, kMatchTierRow1, kMatchTierCount };
+struct MatchPlan { MatchTier tier; uint32_t waves; bool row_cache; bool ix16; size_t lds; bool fits() const { return lds <= kMatchLdsLimit; } };
+// nwork: items of the launch; K, max_Mt: largest kNN and largest target view of its pairs
+MatchPlan match_launch_plan(int mode, bool brute, uint32_t nwork, uint32_t K, uint32_t max_Mt, uint32_t tile_rows);
+// l3d_match_begin: true when some launch l3d_match_pairs can make of a call of total_items work items -- any range of its pair
+// list, i.e. any item count up to total_items -- would not fit the LDS: every row of the call then takes the exact replay
+bool match_knn_replay(bool brute, uint32_t K, uint32_t max_Mt, uint64_t total_items, uint32_t tile_rows);
+// test hooks (l3d_debug_counter): launches of the staged bounded-kNN kernel per tier ([kMatchTierCount]: those with 32-bit
+// table indices), launches of k_order_items
+extern std::atomic<uint64_t> g_match_tier_launches[kMatchTierCount + 1];
+extern std::atomic<uint64_t> g_match_order_launches;
 hipError_t launch_cull_prepare(const ViewDev* views, const PairDesc* pairs, uint32_t first, uint32_t count,
                                uint32_t max_M, CullPools pools, uint32_t tile_rows, hipStream_t stream);
 hipError_t launch_order_items(const PairDesc* pairs, uint32_t first, uint32_t count, uint32_t max_Mt, CullPools pools,
