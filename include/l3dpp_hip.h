@@ -644,6 +644,44 @@ typedef struct l3d_lsd_stages {
 int l3d_debug_lsd_stages(l3d_ctx*, uint32_t n_images, const l3d_image* images, int max_image_width, int query_only,
                          l3d_lsd_stages* out);
 
+/* Test hook (device, read only): the records the converged list pass of the last l3d_match_images / l3d_match_finish left
+ * behind -- headers, edges, segment headers of every pool (l3d_lists.h) -- and what each kernel of phase B's tail made of
+ * them.  It launches nothing and writes nothing on the device; a call that never uses it makes the same
+ * device calls as before.  Valid in state MATCHED (L3D_ERR_STATE otherwise) and until the next call that runs on the
+ * context.  With query_only != 0 only the sizes are filled, without touching the device; the caller then allocates.  Every
+ * pointer may be NULL (that array is not copied).  Records come in pool order, inside a pool in record order; a header's
+ * edge_begin and the edges' edge_index are positions pool * ecap + k in the edge pools of the pass, whose strides ecap /
+ * hcap / scap are those the pass ran with (the context refits its strides after every call). */
+typedef struct l3d_tail_records {
+    /* out: sizes */
+    uint32_t G, V;                    /* 2D segments of all views, views */
+    uint32_t pools, ecap, hcap, scap; /* record pools and their strides in the converged pass */
+    uint32_t n_headers, n_edges, n_segs, n_surv, n_hyps, reserved;
+    uint64_t n_slots;
+    /* in: host buffers */
+    uint32_t* seg_base;               /* V + 1: first global segment of each view */
+    uint32_t* hdr_words;              /* n_headers x 16: HypHdr as it lies */
+    uint32_t* hdr_pool;               /* n_headers: its pool */
+    uint32_t* hdr_index;              /* n_headers: its index in the pool */
+    uint8_t* hdr_positive;            /* n_headers: positive[ref] */
+    uint32_t* edge_words;             /* n_edges x 4: EdgeRec as it lies */
+    uint32_t* edge_index;             /* n_edges: pool * ecap + index */
+    uint8_t* edge_positive;           /* n_edges: positive[ref_j] */
+    uint32_t* seg_words;              /* n_segs x 4: SegHdr */
+    uint32_t* max_score_bits;         /* V x 16: the replicas of each view's largest score */
+    uint32_t* kept_cnt;               /* G */
+    unsigned long long* best_pack;    /* G: score bits << 32 | ~canon of the best kept header */
+    unsigned long long* off64s;       /* G + 1: scan of (surviving matches | best hypotheses << 32) */
+    uint32_t* surv_off;               /* G + 1 */
+    uint32_t* hyp_off;                /* G + 1 */
+    int32_t* hyp_of_seg;              /* G */
+    uint32_t* surv_sg;                /* n_surv */
+    uint32_t* surv_tg;                /* n_surv */
+    float* depths;                    /* 2 x n_hyps */
+    float* medians;                   /* V */
+} l3d_tail_records;
+int l3d_debug_tail_records(l3d_ctx*, int query_only, l3d_tail_records* out);
+
 /* ---- (2) seam layer ------------------------------------------------------------------ */
 
 /* Replaces match_lines_GPU (cudawrapper.h:54-63; caller Line3D::matchingGPU line3D.cc:1040-1074)

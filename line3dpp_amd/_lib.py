@@ -137,6 +137,24 @@ class LsdStages(C.Structure):
                 ("max_grad_bits", C.c_ulonglong), ("stats", DetectStats)]
 
 
+class TailRecords(C.Structure):
+    """l3d_tail_records (include/l3dpp_hip.h): sizes out, host buffers in"""
+    SIZES = ("G", "V", "pools", "ecap", "hcap", "scap", "n_headers", "n_edges", "n_segs", "n_surv", "n_hyps", "reserved")
+    BUFFERS = ("seg_base", "hdr_words", "hdr_pool", "hdr_index", "hdr_positive", "edge_words", "edge_index", "edge_positive",
+               "seg_words", "max_score_bits", "kept_cnt", "best_pack", "off64s", "surv_off", "hyp_off", "hyp_of_seg",
+               "surv_sg", "surv_tg", "depths", "medians")
+    _fields_ = [(n, C.c_uint32) for n in SIZES] + [("n_slots", C.c_uint64)] + [(n, C.c_void_p) for n in BUFFERS]
+
+
+# l3d_lists.h: HypHdr (64 bytes), EdgeRec (16), SegHdr (16) as the hook hands them out
+HYP_HDR_DTYPE = np.dtype([("g", "<u4"), ("ref", "<u4"), ("pair_flags", "<u4"), ("canon", "<u4"), ("dp1", "<f4"), ("dp2", "<f4"),
+                          ("edge_begin", "<u4"), ("edge_cnt", "<u4"), ("score3D", "<f4"), ("state", "<u4"), ("tgt_seg", "<u4"),
+                          ("overlap", "<f4"), ("oq1", "<f4"), ("oq2", "<f4"), ("pad", "<u4", 2)])
+EDGE_REC_DTYPE = np.dtype([("ref_j", "<u4"), ("sim", "<f4"), ("j_cam", "<u4"), ("tv_j", "<u4")])
+SEG_HDR_DTYPE = np.dtype([("g", "<u4"), ("hyp_begin", "<u4"), ("hyp_cnt", "<u4"), ("pad", "<u4")])
+assert HYP_HDR_DTYPE.itemsize == 64 and EDGE_REC_DTYPE.itemsize == 16 and SEG_HDR_DTYPE.itemsize == 16
+
+
 EXPORTS = [
     "l3d_last_error", "l3d_build_info", "l3d_create", "l3d_destroy", "l3d_add_view", "l3d_match_images",
     "l3d_match_begin", "l3d_num_pairs", "l3d_get_pairs", "l3d_match_pairs", "l3d_slot_buffer", "l3d_match_finish",
@@ -161,7 +179,7 @@ EXPORTS = [
     "l3d_triangulate_points", "l3d_rotation_from_rpy", "l3d_rotation_from_q", "l3d_decompose_projection_matrix",
     "l3d_project_segments", "l3d_render_line_maps", "l3d_draw_line_maps", "l3d_view_camera", "l3d_project_lines",
     "l3d_get_projected_lines", "l3d_render_lines", "l3d_draw_lines", "l3d_set_projection_budget", "l3d_selftest_scan",
-    "l3d_debug_lsd_stages", "l3d_match_plan", "l3d_match_tile_rows",
+    "l3d_debug_lsd_stages", "l3d_match_plan", "l3d_match_tile_rows", "l3d_debug_tail_records",
 ]
 
 _lib = None
@@ -268,6 +286,7 @@ def load():
     L.l3d_get_detected_segments.argtypes = [vp, vp, u64, C.POINTER(u64)]
     L.l3d_get_detect_stats.argtypes = [vp, vp, u32, C.POINTER(u32)]
     L.l3d_debug_lsd_stages.argtypes = [vp, u32, vp, i32, i32, vp]
+    L.l3d_debug_tail_records.argtypes = [vp, i32, C.POINTER(TailRecords)]
     L.l3d_add_view_image.argtypes = [vp, u32, C.POINTER(Image), C.POINTER(DetectOptions), vp, vp, vp, f32, vp, u32,
                                      C.POINTER(u32)]
     L.l3d_add_view_image_worldpoints.argtypes = [vp, u32, C.POINTER(Image), C.POINTER(DetectOptions), vp, vp, vp, f32,

@@ -541,6 +541,36 @@ class Line3D:
         self._check(self.L.l3d_get_sparse_matrix(self.h, int(sort_by_row), ptr(ent), ptr(start)), "sparse_matrix")
         return ent[:ne.value], start[:nr.value]
 
+    def tail_records(self):
+        """l3d_debug_tail_records (test hook): the records the converged list pass of the last matchImages left behind and
+        what every kernel of phase B's tail made of them -> dict: the sizes (G, V, pools, ecap, hcap, scap, n_surv,
+        n_hyps, n_slots), headers (HYP_HDR_DTYPE) with hdr_pool / hdr_index / hdr_positive, edges (EDGE_REC_DTYPE) with
+        edge_index (pool * ecap + k, what HypHdr.edge_begin counts in) / edge_positive, segs (SEG_HDR_DTYPE), seg_base,
+        max_score_bits [V, 16], kept_cnt, best_pack, off64s, surv_off, hyp_off, hyp_of_seg, surv_sg, surv_tg,
+        depths [n_hyps, 2], medians.  None (and last_status) when the context holds no matches."""
+        from ._lib import EDGE_REC_DTYPE, HYP_HDR_DTYPE, SEG_HDR_DTYPE, TailRecords
+        t = TailRecords()
+        if not self._check(self.L.l3d_debug_tail_records(self.h, 1, C.byref(t)), "tail_records"):
+            return None
+        out = {k: int(getattr(t, k)) for k in TailRecords.SIZES if k != "reserved"}
+        out["n_slots"] = int(t.n_slots)
+        G, V, nh, ne = t.G, t.V, t.n_headers, t.n_edges
+        bufs = dict(seg_base=np.zeros(V + 1, np.uint32), hdr_words=np.zeros(nh, HYP_HDR_DTYPE), hdr_pool=np.zeros(nh, np.uint32),
+                    hdr_index=np.zeros(nh, np.uint32), hdr_positive=np.zeros(nh, np.uint8), edge_words=np.zeros(ne, EDGE_REC_DTYPE),
+                    edge_index=np.zeros(ne, np.uint32), edge_positive=np.zeros(ne, np.uint8),
+                    seg_words=np.zeros(t.n_segs, SEG_HDR_DTYPE), max_score_bits=np.zeros((V, 16), np.uint32),
+                    kept_cnt=np.zeros(G, np.uint32), best_pack=np.zeros(G, np.uint64), off64s=np.zeros(G + 1, np.uint64),
+                    surv_off=np.zeros(G + 1, np.uint32), hyp_off=np.zeros(G + 1, np.uint32), hyp_of_seg=np.zeros(G, np.int32),
+                    surv_sg=np.zeros(t.n_surv, np.uint32), surv_tg=np.zeros(t.n_surv, np.uint32),
+                    depths=np.zeros((t.n_hyps, 2), np.float32), medians=np.zeros(V, np.float32))
+        for k, a in bufs.items():
+            setattr(t, k, a.ctypes.data if a.size else None)
+        if not self._check(self.L.l3d_debug_tail_records(self.h, 0, C.byref(t)), "tail_records"):
+            return None
+        out.update(bufs)
+        out["headers"] = out.pop("hdr_words"); out["edges"] = out.pop("edge_words"); out["segs"] = out.pop("seg_words")
+        return out
+
     def setTimingLevel(self, level):
         """l3d_set_timing_level: 1 = the match kernel only (default), 2 = every phase timed with HIP events (profiling), 0 = none"""
         return self._check(self.L.l3d_set_timing_level(self.h, int(level)), "setTimingLevel")

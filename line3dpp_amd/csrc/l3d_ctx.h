@@ -261,6 +261,8 @@ struct l3d_ctx {
     DevBuf<CandHdr> d_lchdrs;
     uint32_t lp_ecap = 0, lp_hcap = 0, lp_scap = 0, lp_ccap = 0, huge_cap = 0;
     uint32_t lp_attempts = 0;
+    uint32_t pass_ecap = 0, pass_hcap = 0, pass_scap = 0;   // the strides the converged pass ran with (finish_commit refits lp_*):
+                                                            // where its records lie, for l3d_debug_tail_records
     bool huge_skip = false, huge_ran = true;        // k_lists_huge left out while the passes hand it no lists
     bool list4_skip = false, list4_ran = true;      // the same for the four-wave tier k_lists<4>
     bool lists_wide = false;                        // the last list pass staged 256 hypotheses per wave (launch_lists)

@@ -574,6 +574,7 @@ static int finish_commit(l3d_ctx* c) {
         // all-gathers are pools x stride, so a stride several times the fullest pool's count is traffic for nothing.
         // Every rank sees every counter, so every rank takes the same decision.  (A later call that needs more grows
         // them again through the retry path.)
+        c->pass_ecap = c->lp_ecap; c->pass_hcap = c->lp_hcap; c->pass_scap = c->lp_scap;   // (l3d_debug_tail_records)
         auto fit = [](uint32_t cap, uint32_t need, uint32_t lowest) {
             const uint32_t want = std::max(need + need / 4 + 64, lowest);
             return cap > want + want / 2 ? want : cap;
@@ -787,6 +788,78 @@ int l3d_tail_shard_commit(l3d_ctx* c) {
         return fr;
     }();
     return close_failed_call(c, rc);
+}
+
+// Test hook (include/l3dpp_hip.h): the records the converged pass of the last matchImages left on the device and what
+// every kernel of its tail made of them, copied out as they lie -- no kernel, nothing written.  The pool counters are
+// those of the call's read-back (h_fin), the strides those the pass ran with (finish_commit refits lp_* afterwards).
+int l3d_debug_tail_records(l3d_ctx* c, int query_only, l3d_tail_records* out) {
+    if (!c || !out) return fail(L3D_ERR_ARG, "null argument");
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    if (c->state != l3d_ctx::MATCHED) return fail(L3D_ERR_STATE, "l3d_debug_tail_records: no matches yet");
+    const uint32_t V = (uint32_t)c->order.size(), G = c->G;
+    const uint32_t ecap = c->pass_ecap, hcap = c->pass_hcap, scap = c->pass_scap;
+    const uint32_t* h = c->h_fin.p;
+    uint64_t n_hdr = 0, n_edge = 0, n_seg = 0;
+    for (uint32_t q = 0; q < kListPools; ++q) {
+        n_edge += std::min(h[q * 16], ecap); n_hdr += std::min(h[q * 16 + 1], hcap); n_seg += std::min(h[q * 16 + 2], scap);
+    }
+    out->G = G; out->V = V; out->pools = kListPools; out->ecap = ecap; out->hcap = hcap; out->scap = scap;
+    out->n_headers = (uint32_t)n_hdr; out->n_edges = (uint32_t)n_edge; out->n_segs = (uint32_t)n_seg;
+    out->n_surv = c->n_surv; out->n_hyps = c->n_hyps;
+    out->n_slots = c->n_slots;
+    if (query_only) return L3D_OK;
+    (void)hipSetDevice(c->device);
+    L3D_HIP_CHECK(hipStreamSynchronize(c->stream));
+    const ZeroLayout z = zero_layout(V, G);
+    auto fetch = [](void* dst, const void* src, size_t bytes) -> hipError_t {
+        return dst && bytes ? hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) : hipSuccess;
+    };
+    if (out->seg_base) std::memcpy(out->seg_base, c->seg_base.data(), ((size_t)V + 1) * 4);
+    std::vector<uint8_t> positive;
+    if (out->hdr_positive || out->edge_positive) {
+        positive.resize(std::max<uint64_t>(c->n_slots, 1));
+        L3D_HIP_CHECK(fetch(positive.data(), positive_of(c), c->n_slots));
+    }
+    std::vector<HypHdr> hdrs;
+    std::vector<EdgeRec> edges;
+    size_t at_h = 0, at_e = 0, at_s = 0;
+    for (uint32_t q = 0; q < kListPools; ++q) {
+        const uint32_t nh = std::min(h[q * 16 + 1], hcap), ne = std::min(h[q * 16], ecap), ns = std::min(h[q * 16 + 2], scap);
+        if (nh && (out->hdr_words || out->hdr_positive)) {
+            hdrs.resize(nh);
+            L3D_HIP_CHECK(fetch(hdrs.data(), c->d_lhyps.p + (size_t)q * hcap, (size_t)nh * sizeof(HypHdr)));
+            if (out->hdr_words) std::memcpy(out->hdr_words + at_h * 16, hdrs.data(), (size_t)nh * sizeof(HypHdr));
+        }
+        if (ne && (out->edge_words || out->edge_positive)) {
+            edges.resize(ne);
+            L3D_HIP_CHECK(fetch(edges.data(), c->d_ledges.p + (size_t)q * ecap, (size_t)ne * sizeof(EdgeRec)));
+            if (out->edge_words) std::memcpy(out->edge_words + at_e * 4, edges.data(), (size_t)ne * sizeof(EdgeRec));
+        }
+        for (uint32_t k = 0; k < nh; ++k) {
+            if (out->hdr_pool) out->hdr_pool[at_h + k] = q;
+            if (out->hdr_index) out->hdr_index[at_h + k] = k;
+            if (out->hdr_positive) out->hdr_positive[at_h + k] = hdrs[k].ref < c->n_slots ? positive[hdrs[k].ref] : (uint8_t)0xFF;
+        }
+        for (uint32_t k = 0; k < ne; ++k) {
+            if (out->edge_index) out->edge_index[at_e + k] = q * ecap + k;
+            if (out->edge_positive) out->edge_positive[at_e + k] = edges[k].ref_j < c->n_slots ? positive[edges[k].ref_j] : (uint8_t)0xFF;
+        }
+        if (out->seg_words) L3D_HIP_CHECK(fetch(out->seg_words + at_s * 4, c->d_lsegs.p + (size_t)q * scap, (size_t)ns * sizeof(SegHdr)));
+        at_h += nh; at_e += ne; at_s += ns;
+    }
+    L3D_HIP_CHECK(fetch(out->max_score_bits, c->d_lzero.p + z.max_score, (size_t)V * 16 * 4));
+    L3D_HIP_CHECK(fetch(out->kept_cnt, c->d_lzero.p + z.kept, (size_t)G * 4));
+    L3D_HIP_CHECK(fetch(out->best_pack, c->d_lzero.p + z.best, (size_t)G * 8));
+    L3D_HIP_CHECK(fetch(out->off64s, c->d_off64s.p, ((size_t)G + 1) * 8));
+    L3D_HIP_CHECK(fetch(out->surv_off, c->d_surv_off.p, ((size_t)G + 1) * 4));
+    L3D_HIP_CHECK(fetch(out->hyp_off, c->d_hyp_off.p, ((size_t)G + 1) * 4));
+    L3D_HIP_CHECK(fetch(out->hyp_of_seg, c->d_hyp_of_seg.p, (size_t)G * 4));
+    L3D_HIP_CHECK(fetch(out->surv_sg, c->d_surv_sg.p, (size_t)c->n_surv * 4));
+    L3D_HIP_CHECK(fetch(out->surv_tg, c->d_surv_tg.p, (size_t)c->n_surv * 4));
+    L3D_HIP_CHECK(fetch(out->depths, c->d_depths.p, (size_t)c->n_hyps * 8));
+    L3D_HIP_CHECK(fetch(out->medians, medians_of(c), (size_t)V * 4));
+    return L3D_OK;
 }
 
 }  // extern "C"
