@@ -810,6 +810,49 @@ int l3d_draw_lines(l3d_ctx*, uint32_t n_cams, const l3d_camera* cams, const l3d_
  * 256 MiB); a small one makes many groups.  The results do not depend on it. */
 int l3d_set_projection_budget(l3d_ctx*, uint64_t bytes);
 
+/* ---- the 2D segments that support each 3D line (GPU: k_associate.hip) ------------------------------------
+ * No reference counterpart.  The way back from an image to the model: every 2D segment of a camera is tested against
+ * every record of that camera (l3d_projected_segment, as stage 1 above hands them out) and assigned the record it
+ * observes.  A pair (segment, record) is accepted iff the record is at least a pixel long, the segment is not a point,
+ * both end points of the segment lie within max_distance pixels of the record's line, the angle between the two is at
+ * most the one whose squared cosine is min_cos2, and at least min_overlap of the segment lies within the record's
+ * extent.  Of the accepted records the segment is assigned the one with the smallest distance (the larger of its two
+ * end points' distances), of equal distances the one with the smaller index.  fp64, the contract of DESIGN §17. */
+typedef struct l3d_associate_params {
+    double max_distance;   /* pixels, finite, >= 0 */
+    double min_cos2;       /* in [0, 1]: cos^2 of the largest angle between segment and record */
+    double min_overlap;    /* in [0, 1]: share of the 2D segment inside the record's extent */
+} l3d_associate_params;
+/* the result for one 2D segment (24 bytes) */
+typedef struct l3d_association {
+    int32_t record;        /* index among its camera's records, -1: none accepted */
+    uint32_t line;         /* the record's line (0xFFFFFFFF: none) */
+    uint32_t segment;      /* the record's segment & L3D_PROJ_SEGMENT_MASK (0xFFFFFFFF: none) */
+    float distance;        /* pixels: the larger distance of the segment's end points from the record's line (0: none) */
+    float overlap;         /* share of the 2D segment inside the record's extent (0: none) */
+    uint32_t n_accepted;   /* accepted records; more than 1 marks an ambiguous segment */
+} l3d_association;
+/* Argument checks of both entries, the outputs untouched: L3D_ERR_ARG for a null pointer where one is needed, a
+ * non-finite record or segment (the message names camera and index), max_distance negative or not finite, min_cos2 or
+ * min_overlap outside [0, 1] or NaN; L3D_ERR_LIMIT for 2^31 or more records in a camera or 2^32 or more segments in
+ * total.  Cameras are taken in groups under the budget of l3d_set_projection_budget; the results do not depend on it.
+ * Stateless, host pointers: n_records_per_cam[c] records of camera c in `records`, camera after camera;
+ * n_segments_per_cam[c] segments (x1, y1, x2, y2) of camera c in segs4, camera after camera; out: one l3d_association
+ * per segment in the same order.  Zero cameras, records or segments: L3D_OK, every output "none". */
+int l3d_associate_segments(int device, uint32_t n_cams, const uint32_t* n_records_per_cam,
+                           const l3d_projected_segment* records, const uint32_t* n_segments_per_cam, const float* segs4,
+                           const l3d_associate_params* params, l3d_association* out);
+/* The same for added views (camIDs, each once) and the lines the last l3d_reconstruct_3d_lines left in the context: the
+ * lines are projected into the views' own cameras (l3d_view_camera, as l3d_project_lines does: l3d_get_projected_lines
+ * returns these records afterwards) and every view's own segments -- the coordinates of l3d_get_segment_coords2d, segID
+ * = index -- are associated.  offsets[n_views + 1]: where every view's results begin in out; out may be NULL: the offsets
+ * only, and nothing runs.  support_segments / support_views (n_lines of l3d_num_3d_lines each, may be NULL): per 3D line
+ * the number of assigned (view, segment) pairs and the number of distinct views among them.  L3D_ERR_STATE without
+ * reconstructed lines or while a split call is open; an unknown camID or one named twice: L3D_ERR_ARG. */
+int l3d_associate_view_segments(l3d_ctx*, uint32_t n_views, const uint32_t* camIDs, const l3d_associate_params* params,
+                                double near_plane, uint64_t* offsets, l3d_association* out, uint32_t* support_segments,
+                                uint32_t* support_views);
+
 #ifdef __cplusplus
 }
 #endif

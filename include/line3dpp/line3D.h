@@ -10,6 +10,7 @@
 //     computeAffinityMatrix()            // the affinity part of reconstruct3Dlines()
 //     projectLines(camID | K, R, t, width, height, out)    (no reference counterpart: the 3D lines as a camera sees them)
 //     drawLines(camID | K, R, t, inImg, outImg, thickness, alpha)      (... drawn over an image)
+//     associateSegments([camID,] out, max_distance, max_angle, min_overlap)   (... and the 2D segments that observe them)
 //
 // Same names, argument order, defaults (commons.h:40-70) and error behaviour as the reference: errors
 // are printed with the "[L3D++] ERROR:" prefix and the call returns (void), no exceptions
@@ -23,6 +24,7 @@
 #ifndef L3DPP_HIP_FACADE_LINE3D_H_
 #define L3DPP_HIP_FACADE_LINE3D_H_
 
+#include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <initializer_list>
@@ -451,6 +453,29 @@ public:
         project_camera(cam, out, near_plane);
     }
 
+    // The 2D segments that support each 3D line (no reference counterpart; DESIGN §17, k_associate.hip): every segment of
+    // the added view camID is assigned the 3D line of the last reconstruct3Dlines it observes -- out[segID].record is the
+    // index among the view's projected records (projectLines(camID, ...)), -1 where the segment observes none; .line the
+    // 3D line.  max_distance in pixels, max_angle in degrees [0, 90], min_overlap = the share of the 2D segment that has
+    // to lie within the projected 3D segment.  Errors are printed and leave `out` empty.
+    void associateSegments(const unsigned int camID, std::vector<l3d_association>& out, const double max_distance = 2.5,
+                           const double max_angle = 10.0, const double min_overlap = 0.5, const double near_plane = 1e-6) {
+        std::map<unsigned int, std::vector<l3d_association>> all;
+        associate_views(std::vector<uint32_t>(1, camID), all, max_distance, max_angle, min_overlap, near_plane);
+        out.clear();
+        if (!all.empty()) out.swap(all.begin()->second);
+    }
+    // ... of every added view: out[camID][segID]
+    void associateSegments(std::map<unsigned int, std::vector<l3d_association>>& out, const double max_distance = 2.5,
+                           const double max_angle = 10.0, const double min_overlap = 0.5, const double near_plane = 1e-6) {
+        std::vector<uint32_t> ids;
+        {
+            std::lock_guard<std::mutex> lk(lines_mu_);
+            for (const auto& kv : num_lines_) ids.push_back(kv.first);
+        }
+        associate_views(ids, out, max_distance, max_angle, min_overlap, near_plane);
+    }
+
     // The 3D lines drawn over inImg (cv::Mat, Image8U or ImageBuf8U, 8-bit with 1 or 3 channels, of the camera's size):
     // outImg.create(rows, cols, 16) -- RGB -- as undistortImage makes its output; thickness in pixels (odd), alpha 0..255,
     // one colour per line from a fixed palette.  Errors are printed and leave outImg empty.
@@ -494,6 +519,27 @@ private:
         }
         out.resize(count);
         l3d_get_projected_lines(ctx_, out.data(), out.size(), &n);
+    }
+    void associate_views(const std::vector<uint32_t>& ids, std::map<unsigned int, std::vector<l3d_association>>& out,
+                         double max_distance, double max_angle, double min_overlap, double near_plane) {
+        out.clear();
+        if (!(max_angle >= 0.0 && max_angle <= 90.0)) {
+            std::cout << prefix_err_ << "associateSegments: max_angle must lie in [0, 90] degrees" << std::endl;
+            return;
+        }
+        const double cosine = std::cos(max_angle * (3.14159265358979323846 / 180.0));
+        const l3d_associate_params par{max_distance, cosine * cosine, min_overlap};
+        std::vector<uint64_t> off(ids.size() + 1, 0);
+        if (l3d_associate_view_segments(ctx_, (uint32_t)ids.size(), ids.data(), &par, near_plane, off.data(), nullptr, nullptr, nullptr) != L3D_OK) {
+            std::cout << prefix_err_ << "associateSegments: " << l3d_last_error() << std::endl;
+            return;
+        }
+        std::vector<l3d_association> flat(off.back() ? off.back() : 1);
+        if (l3d_associate_view_segments(ctx_, (uint32_t)ids.size(), ids.data(), &par, near_plane, off.data(), flat.data(), nullptr, nullptr) != L3D_OK) {
+            std::cout << prefix_err_ << "associateSegments: " << l3d_last_error() << std::endl;
+            return;
+        }
+        for (size_t k = 0; k < ids.size(); ++k) out[ids[k]].assign(flat.begin() + off[k], flat.begin() + off[k + 1]);
     }
     template <class InImage, class OutImage>
     void draw_camera(const l3d_camera& cam, const InImage& inImg, OutImage& outImg, unsigned int thickness, unsigned int alpha) {

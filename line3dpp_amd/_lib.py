@@ -31,6 +31,10 @@ PROJECTED_SEGMENT_DTYPE = np.dtype([("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"),
 PROJ_CLIPPED_NEAR, PROJ_CLIPPED_RECT, PROJ_SEGMENT_MASK = 0x80000000, 0x40000000, 0x3FFFFFFF
 assert MATCH_DTYPE.itemsize == 40 and SLOT_DTYPE.itemsize == 32 and SEGMENT3D_DTYPE.itemsize == 80
 assert PROJECTED_SEGMENT_DTYPE.itemsize == 32
+# l3d_association: the record a 2D segment was assigned; record = -1, line = segment = EMPTY: none
+ASSOCIATION_DTYPE = np.dtype([("record", "<i4"), ("line", "<u4"), ("segment", "<u4"), ("distance", "<f4"),
+                              ("overlap", "<f4"), ("n_accepted", "<u4")])
+assert ASSOCIATION_DTYPE.itemsize == 24
 EMPTY = 0xFFFFFFFF
 L3D_ERR_NO_SEGMENTS = -5
 L3D_ERR_IO = -11
@@ -121,6 +125,11 @@ class ProjectedSegment(C.Structure):
                 ("inv_depth2", C.c_float), ("line", C.c_uint32), ("segment", C.c_uint32)]
 
 
+class AssociateParams(C.Structure):
+    """l3d_associate_params (include/l3dpp_hip.h)"""
+    _fields_ = [("max_distance", C.c_double), ("min_cos2", C.c_double), ("min_overlap", C.c_double)]
+
+
 class DetectStats(C.Structure):
     """l3d_detect_stats (include/l3dpp_hip.h)"""
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("raw_segments", C.c_uint32), ("segments", C.c_uint32),
@@ -180,6 +189,7 @@ EXPORTS = [
     "l3d_project_segments", "l3d_render_line_maps", "l3d_draw_line_maps", "l3d_view_camera", "l3d_project_lines",
     "l3d_get_projected_lines", "l3d_render_lines", "l3d_draw_lines", "l3d_set_projection_budget", "l3d_selftest_scan",
     "l3d_debug_lsd_stages", "l3d_match_plan", "l3d_match_tile_rows", "l3d_debug_tail_records",
+    "l3d_associate_segments", "l3d_associate_view_segments",
 ]
 
 _lib = None
@@ -310,6 +320,8 @@ def load():
     L.l3d_render_lines.argtypes = [vp, u32, vp, f64, u32, vp, vp]
     L.l3d_draw_lines.argtypes = [vp, u32, vp, vp, f64, u32, u32, vp, vp]
     L.l3d_set_projection_budget.argtypes = [vp, u64]
+    L.l3d_associate_segments.argtypes = [i32, u32, vp, vp, vp, vp, C.POINTER(AssociateParams), vp]
+    L.l3d_associate_view_segments.argtypes = [vp, u32, vp, C.POINTER(AssociateParams), f64, vp, vp, vp, vp]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("l3d_last_error", "l3d_build_info", "l3d_create", "l3d_destroy"):

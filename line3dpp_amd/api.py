@@ -15,7 +15,7 @@ import threading
 import numpy as np
 
 from . import _lib, lsd
-from ._lib import (CLEDGE_DTYPE, EMPTY, FLOAT4_DTYPE, MATCH_DTYPE, PROJECTED_SEGMENT_DTYPE, SEGMENT2D_DTYPE,
+from ._lib import (ASSOCIATION_DTYPE, CLEDGE_DTYPE, EMPTY, FLOAT4_DTYPE, MATCH_DTYPE, PROJECTED_SEGMENT_DTYPE, SEGMENT2D_DTYPE,
                    SEGMENT3D_DTYPE, SLOT_DTYPE, MatchParams, Timings, ptr)
 
 # commons.h:40-70
@@ -434,8 +434,35 @@ class Line3D:
             return None
         return outs
 
+    # ---- the 2D segments that support each 3D line (no reference counterpart) ------------------------------
+    def associateSegments(self, camIDs=None, max_distance=L3D_DEF_SCORING_POS_REGULARIZER,
+                          max_angle=L3D_DEF_SCORING_ANG_REGULARIZER, min_overlap=0.5, near=1e-6):
+        """every segment of the views camIDs (None: all, ascending) assigned the 3D line of the last reconstruct3Dlines
+        it observes -> (dict camID -> ASSOCIATION_DTYPE array with one entry per segment of the view, support_segments,
+        support_views: per 3D line the assigned (view, segment) pairs and the distinct views among them); None after an
+        error.  max_distance in pixels, max_angle in degrees [0, 90], min_overlap = share of the 2D segment."""
+        ids = np.ascontiguousarray(sorted(self._M) if camIDs is None else list(camIDs), np.uint32).reshape(-1)
+        try:
+            par = associate_params(max_distance, max_angle, min_overlap)
+        except ValueError as e:
+            print(f"{self.PREFIX}ERROR: associateSegments: {e}")
+            self.last_status = -1
+            return None
+        off = np.zeros(len(ids) + 1, np.uint64)
+        args = (self.h, len(ids), ptr(ids), C.byref(par), float(near), ptr(off))
+        nl = C.c_uint32(); ns = C.c_uint32(); nr = C.c_uint32()
+        if not (self._check(self.L.l3d_associate_view_segments(*args, None, None, None), "associateSegments") and
+                self._check(self.L.l3d_num_3d_lines(self.h, C.byref(nl), C.byref(ns), C.byref(nr)), "associateSegments")):
+            return None
+        out = np.zeros(max(int(off[-1]), 1), ASSOCIATION_DTYPE)
+        sup_s = np.zeros(max(nl.value, 1), np.uint32); sup_v = np.zeros(max(nl.value, 1), np.uint32)
+        if not self._check(self.L.l3d_associate_view_segments(*args, ptr(out), ptr(sup_s), ptr(sup_v)), "associateSegments"):
+            return None
+        res = {int(c): out[int(off[k]):int(off[k + 1])].copy() for k, c in enumerate(ids)}
+        return res, sup_s[:nl.value], sup_v[:nl.value]
+
     def set_projection_budget(self, n_bytes):
-        """test hook: device-memory budget of a group of cameras in the three calls above (0: the default)"""
+        """test hook: device-memory budget of a group of cameras in the four calls above (0: the default)"""
         self.L.l3d_set_projection_budget(self.h, int(n_bytes))
 
     def set_brute_force(self, on):
@@ -637,6 +664,36 @@ def project_segments(cams, P1, P2, line_of_segment, near=1e-6, device=0):
     if rc != 0:
         raise RuntimeError(f"l3d_project_segments failed [{rc}]: {_lib.last_error()}")
     return split_records(rec, counts[:len(cams)])
+
+
+def associate_params(max_distance, max_angle, min_overlap):
+    """l3d_associate_params from the wrappers' arguments: min_cos2 = cos(radians(max_angle))^2, max_angle in [0, 90]"""
+    if not 0.0 <= float(max_angle) <= 90.0:
+        raise ValueError("max_angle must lie in [0, 90] degrees")
+    cos = float(np.cos(np.radians(np.float64(max_angle))))
+    return _lib.AssociateParams(float(max_distance), cos * cos, float(min_overlap))
+
+
+def associate_segments(records_per_cam, segs_per_cam, max_distance=L3D_DEF_SCORING_POS_REGULARIZER,
+                       max_angle=L3D_DEF_SCORING_ANG_REGULARIZER, min_overlap=0.5, device=0):
+    """l3d_associate_segments: records_per_cam = one PROJECTED_SEGMENT_DTYPE array per camera (as
+    project_segments returns them), segs_per_cam = one float32 [M, 4] array of 2D segments (x1, y1, x2, y2) per camera
+    -> one ASSOCIATION_DTYPE array per camera, one entry per 2D segment: the record it observes, or none"""
+    L = _lib.load()
+    if len(records_per_cam) != len(segs_per_cam):
+        raise ValueError("one array of records and one of segments per camera")
+    recs = [np.ascontiguousarray(r, PROJECTED_SEGMENT_DTYPE).reshape(-1) for r in records_per_cam]
+    segs = [np.ascontiguousarray(s, np.float32).reshape(-1, 4) for s in segs_per_cam]
+    n = len(recs)
+    n_rec = np.array([len(r) for r in recs] + [0], np.uint32); n_seg = np.array([len(s) for s in segs] + [0], np.uint32)
+    rec = np.concatenate(recs + [np.zeros(1, PROJECTED_SEGMENT_DTYPE)])
+    seg = np.concatenate(segs + [np.zeros((1, 4), np.float32)])
+    out = np.zeros(len(seg), ASSOCIATION_DTYPE)
+    par = associate_params(max_distance, max_angle, min_overlap)
+    rc = L.l3d_associate_segments(int(device), n, ptr(n_rec), ptr(rec), ptr(n_seg), ptr(seg), C.byref(par), ptr(out))
+    if rc != 0:
+        raise RuntimeError(f"l3d_associate_segments failed [{rc}]: {_lib.last_error()}")
+    return split_records(out, n_seg[:n])
 
 
 def render_line_maps(cams, records, thickness=1, device=0):

@@ -169,6 +169,8 @@ unsigned long long l3d_debug_counter(const char* name) {
     if (name && std::string(name) == "keep_all_repeats") return g_keep_all_repeats.load(std::memory_order_relaxed);
     if (name && std::string(name) == "lsd_images_detected") return g_lsd_images_detected.load(std::memory_order_relaxed);
     if (name && std::string(name) == "lsd_cache_loads") return g_lsd_cache_loads.load(std::memory_order_relaxed);
+    if (name && std::string(name) == "associate_launches") return g_assoc_launches.load(std::memory_order_relaxed);
+    if (name && std::string(name) == "associate_kernel_ns") return g_assoc_kernel_ns.load(std::memory_order_relaxed);
     if (name && std::string(name) == "live_device_blocks") return g_live_blocks[0].load(std::memory_order_relaxed);
     if (name && std::string(name) == "live_pinned_blocks") return g_live_blocks[1].load(std::memory_order_relaxed);
     static const char* const kSeamSupport[4] = {"seam_support_wave_lists", "seam_support_group_staged_lists",

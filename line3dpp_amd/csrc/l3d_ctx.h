@@ -133,6 +133,9 @@ struct ProjWork {
     DevBuf<unsigned long long> keys, scan_ws;   // key planes of the group; k_scan.hip's work space (all-zero between scans)
     size_t budget = 0;                       // device-memory budget of a group of cameras; 0: l3d_project.hip's kProjBudget
 };
+size_t projection_budget(const ProjWork& w);   // l3d_project.hip: the budget in force
+// l3d_project.hip: stage 1 on the context's lines into c->proj_records, camera after camera (the caller holds the mutex)
+int project_context_lines(::l3d_ctx* c, uint32_t n_cams, const l3d_camera* cams, double near_plane, std::vector<uint32_t>& counts);
 
 }  // namespace l3d
 

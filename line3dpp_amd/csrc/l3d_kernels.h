@@ -278,4 +278,22 @@ hipError_t launch_raster_lines(const MapArgs& a, uint32_t blocks, hipStream_t st
 hipError_t launch_map_decode(const MapArgs& a, hipStream_t st);                      // keys -> line_id, inv_depth
 hipError_t launch_overlay(const MapArgs& a, hipStream_t st);                         // line_id + img -> rgb
 
+// ---- k_associate.hip: 2D segments assigned to the projected 3D lines they observe (host side: l3d_associate.hip) ----
+constexpr uint32_t kAssocTile = 256;     // 2D segments of one camera per workgroup, one lane each
+constexpr uint32_t kAssocChunk = 512;    // records per pass through LDS (16 KiB)
+constexpr uint32_t kAssocSegmentMask = 0x3FFFFFFFu;   // = L3D_PROJ_SEGMENT_MASK
+// a camera of a group: its tiles in the launch, its segments and records in the group's arrays
+struct AssocCam { uint32_t tile0, seg0, n_seg, rec0, n_rec; };
+// = l3d_association, but for d2: the squared distance, of which the host takes the root after the download
+struct AssocOut { int32_t record; uint32_t line, segment; float d2, overlap; uint32_t n_accepted; };
+struct AssocArgs {
+    const AssocCam* cams; uint32_t n_cams;   // [n_cams] tile0 ascending: the exclusive prefix of tiles per camera
+    const float4* segs;                      // [segments of the group] (x1, y1, x2, y2)
+    const ProjRecord* rec;                   // [records of the group]
+    AssocOut* out;                           // [segments of the group]
+    double max_d2, min_cos2, min_overlap;    // max_distance * max_distance, the squared cosine, the overlap share
+};
+hipError_t launch_associate(const AssocArgs& a, uint32_t n_tiles, hipStream_t st);
+extern std::atomic<uint64_t> g_assoc_launches, g_assoc_kernel_ns;   // l3d_associate.hip, test hooks read through l3d_debug_counter
+
 }  // namespace l3d

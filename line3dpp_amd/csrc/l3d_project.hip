@@ -281,6 +281,14 @@ int project_context(l3d_ctx* c, uint32_t n_cams, const l3d_camera* cams, double 
 
 }  // namespace
 
+// what l3d_associate.hip shares with the stages above: the budget of a group of cameras, and stage 1 on the context's lines
+namespace l3d {
+size_t projection_budget(const ProjWork& w) { return budget_of(w); }
+int project_context_lines(l3d_ctx* c, uint32_t n_cams, const l3d_camera* cams, double near_plane, std::vector<uint32_t>& counts) {
+    return project_context(c, n_cams, cams, near_plane, counts);
+}
+}  // namespace l3d
+
 extern "C" {
 
 int l3d_project_segments(int device, uint32_t n_cams, const l3d_camera* cams, uint32_t n_segments, const l3d_segment3d* segments,
