@@ -853,6 +853,61 @@ int l3d_associate_view_segments(l3d_ctx*, uint32_t n_views, const uint32_t* camI
                                 double near_plane, uint64_t* offsets, l3d_association* out, uint32_t* support_segments,
                                 uint32_t* support_views);
 
+/* ---- two 3D line models compared segment by segment, in both directions (GPU: k_compare.hip) ------------
+ * No reference counterpart.  A model is a flat array of 3D segments (P1, P2: 6 doubles each, world frame) with a line
+ * index per segment.  A pair (query q, reference r) is accepted iff neither is a point, the angle between them is at
+ * most the one whose squared cosine is min_cos2, both end points of q lie within max_distance of r's line, and at least
+ * min_overlap of q lies within r's extent; with exclude_same_line, iff also line(q) != line(r).  Of the accepted
+ * references a query gets the one with the smallest distance (the larger of its two end points' distances), of equal
+ * distances the one with the smaller index.  fp64, the contract of DESIGN §18.  The caller aligns the models: no
+ * similarity transform is estimated. */
+typedef struct l3d_compare_params {
+    double max_distance;         /* model units, finite, >= 0: a 3D model has no natural unit, so there is no default */
+    double min_cos2;             /* in [0, 1]: cos^2 of the largest angle between query and reference */
+    double min_overlap;          /* in [0, 1]: share of the query inside the reference's extent */
+    uint32_t exclude_same_line;  /* 0 or 1; 1: pairs of the same line index are not accepted (a model against itself:
+                                    its near-duplicate lines) */
+    uint32_t slice_chunks;       /* 0: the library chooses; else chunks of 256 references per slice.  A tuning knob and
+                                    test hook: no output depends on it */
+} l3d_compare_params;
+/* the result for one query segment (24 bytes) */
+typedef struct l3d_line_match {
+    int32_t segment;       /* index of the reference segment, -1: none accepted */
+    uint32_t line;         /* the reference's line (0xFFFFFFFF: none) */
+    uint32_t n_accepted;   /* accepted references; more than 1 marks an ambiguous segment */
+    float overlap;         /* share of the query inside the reference's extent (0: none) */
+    double distance;       /* the larger distance of the query's end points from the reference's line (0: none) */
+} l3d_line_match;
+/* one direction summed up (56 bytes); the lengths are added sequentially in ascending index order */
+typedef struct l3d_compare_summary {
+    uint64_t n_segments;       /* queries */
+    uint64_t n_matched;        /* ... with a reference */
+    uint64_t n_ambiguous;      /* ... with n_accepted > 1 */
+    uint64_t n_lines;          /* distinct line indices among the queries */
+    uint64_t n_lines_matched;  /* ... with at least one matched segment */
+    double length_total;       /* sum of the queries' lengths */
+    double length_matched;     /* ... of the matched ones */
+} l3d_compare_summary;
+/* Stateless, host pointers.  q_segs6 [n_q x 6], q_line [n_q]; r_segs6, r_line alike.  out_q [n_q]: every segment of Q
+ * against R; out_r [n_r]: every segment of R against Q; either may be NULL, and that direction is skipped together with
+ * its summary.  summary_q / summary_r may be NULL.  One upload, one launch (pair) and one download per direction.
+ * Checked before any device work, the outputs untouched: L3D_ERR_LIMIT for 2^30 or more segments on a side; L3D_ERR_ARG
+ * for a null pointer where one is needed, a coordinate that is not finite or beyond 2^100 in magnitude (the message
+ * names the side and the segment), max_distance negative or not finite, min_cos2 or min_overlap outside [0, 1] or NaN,
+ * exclude_same_line > 1.  Zero segments on either side: L3D_OK, every record "none" and both summaries all zero: nothing was
+ * compared. */
+int l3d_compare_segments(int device, uint32_t n_q, const double* q_segs6, const uint32_t* q_line, uint32_t n_r,
+                         const double* r_segs6, const uint32_t* r_line, const l3d_compare_params* params,
+                         l3d_line_match* out_q, l3d_line_match* out_r, l3d_compare_summary* summary_q,
+                         l3d_compare_summary* summary_r);
+/* The same with the context's side = the flat collinear segments of the last l3d_reconstruct_3d_lines, in the order
+ * and coordinates l3d_get_3d_lines returns them (n_segments of l3d_num_3d_lines; the line of a segment is the index of
+ * its 3D line): out_mine [n_segments], out_other [n_other].  On the context's stream.  L3D_ERR_STATE without
+ * reconstructed lines or while a split call is open. */
+int l3d_compare_lines(l3d_ctx*, uint32_t n_other, const double* other_segs6, const uint32_t* other_line,
+                      const l3d_compare_params* params, l3d_line_match* out_mine, l3d_line_match* out_other,
+                      l3d_compare_summary* summary_mine, l3d_compare_summary* summary_other);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,7 @@
 //     projectLines(camID | K, R, t, width, height, out)    (no reference counterpart: the 3D lines as a camera sees them)
 //     drawLines(camID | K, R, t, inImg, outImg, thickness, alpha)      (... drawn over an image)
 //     associateSegments([camID,] out, max_distance, max_angle, min_overlap)   (... and the 2D segments that observe them)
+//     compareLines(other, mine, theirs, max_distance, max_angle, min_overlap)   (... and compared with another model)
 //
 // Same names, argument order, defaults (commons.h:40-70) and error behaviour as the reference: errors
 // are printed with the "[L3D++] ERROR:" prefix and the call returns (void), no exceptions
@@ -474,6 +475,47 @@ public:
             for (const auto& kv : num_lines_) ids.push_back(kv.first);
         }
         associate_views(ids, out, max_distance, max_angle, min_overlap, near_plane);
+    }
+
+    // This model compared with another one (no reference counterpart; DESIGN §18, k_compare.hip): `other` as get3Dlines
+    // hands a model out, in the same frame.  mine[k]: the counterpart in `other` of this model's k-th flat segment (the
+    // collinear3Dsegments_ of get3Dlines, line after line); theirs[k]: the counterpart in this model of other's k-th.
+    // .segment is the index among the flat segments of the opposite side (-1: none), .line the index of its line.
+    // max_distance in model units -- a 3D model has no natural unit, so there is no default --, max_angle in degrees
+    // [0, 90], min_overlap = the share of a segment inside its counterpart's extent.  Errors are printed and leave both
+    // outputs empty.
+    void compareLines(const std::vector<FinalLine3D>& other, std::vector<l3d_line_match>& mine, std::vector<l3d_line_match>& theirs,
+                      const double max_distance, const double max_angle = 10.0, const double min_overlap = 0.5) {
+        mine.clear();
+        theirs.clear();
+        if (!(max_angle >= 0.0 && max_angle <= 90.0)) {
+            std::cout << prefix_err_ << "compareLines: max_angle must lie in [0, 90] degrees" << std::endl;
+            return;
+        }
+        const double cosine = std::cos(max_angle * (3.14159265358979323846 / 180.0));
+        const l3d_compare_params par{max_distance, cosine * cosine, min_overlap, 0u, 0u};
+        std::vector<double> segs;
+        std::vector<uint32_t> line;
+        for (size_t i = 0; i < other.size(); ++i)
+            for (const l3d_segment3d& s : other[i].collinear3Dsegments_) {
+                segs.insert(segs.end(), s.P1, s.P1 + 3);
+                segs.insert(segs.end(), s.P2, s.P2 + 3);
+                line.push_back((uint32_t)i);
+            }
+        uint32_t ns = 0;
+        if (l3d_num_3d_lines(ctx_, nullptr, &ns, nullptr) != L3D_OK) {
+            std::cout << prefix_err_ << "compareLines: " << l3d_last_error() << std::endl;
+            return;
+        }
+        std::vector<l3d_line_match> a(ns ? ns : 1), b(line.empty() ? 1 : line.size());
+        if (l3d_compare_lines(ctx_, (uint32_t)line.size(), segs.data(), line.data(), &par, a.data(), b.data(), nullptr, nullptr) != L3D_OK) {
+            std::cout << prefix_err_ << "compareLines: " << l3d_last_error() << std::endl;
+            return;
+        }
+        a.resize(ns);
+        b.resize(line.size());
+        mine.swap(a);
+        theirs.swap(b);
     }
 
     // The 3D lines drawn over inImg (cv::Mat, Image8U or ImageBuf8U, 8-bit with 1 or 3 channels, of the camera's size):

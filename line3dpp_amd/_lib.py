@@ -35,6 +35,10 @@ assert PROJECTED_SEGMENT_DTYPE.itemsize == 32
 ASSOCIATION_DTYPE = np.dtype([("record", "<i4"), ("line", "<u4"), ("segment", "<u4"), ("distance", "<f4"),
                               ("overlap", "<f4"), ("n_accepted", "<u4")])
 assert ASSOCIATION_DTYPE.itemsize == 24
+# l3d_line_match: the reference segment a 3D query segment was assigned; segment = -1, line = EMPTY: none
+LINE_MATCH_DTYPE = np.dtype([("segment", "<i4"), ("line", "<u4"), ("n_accepted", "<u4"), ("overlap", "<f4"),
+                             ("distance", "<f8")])
+assert LINE_MATCH_DTYPE.itemsize == 24
 EMPTY = 0xFFFFFFFF
 L3D_ERR_NO_SEGMENTS = -5
 L3D_ERR_IO = -11
@@ -130,6 +134,18 @@ class AssociateParams(C.Structure):
     _fields_ = [("max_distance", C.c_double), ("min_cos2", C.c_double), ("min_overlap", C.c_double)]
 
 
+class CompareParams(C.Structure):
+    """l3d_compare_params (include/l3dpp_hip.h)"""
+    _fields_ = [("max_distance", C.c_double), ("min_cos2", C.c_double), ("min_overlap", C.c_double),
+                ("exclude_same_line", C.c_uint32), ("slice_chunks", C.c_uint32)]
+
+
+class CompareSummary(C.Structure):
+    """l3d_compare_summary (include/l3dpp_hip.h)"""
+    _fields_ = [("n_segments", C.c_uint64), ("n_matched", C.c_uint64), ("n_ambiguous", C.c_uint64), ("n_lines", C.c_uint64),
+                ("n_lines_matched", C.c_uint64), ("length_total", C.c_double), ("length_matched", C.c_double)]
+
+
 class DetectStats(C.Structure):
     """l3d_detect_stats (include/l3dpp_hip.h)"""
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("raw_segments", C.c_uint32), ("segments", C.c_uint32),
@@ -190,6 +206,7 @@ EXPORTS = [
     "l3d_get_projected_lines", "l3d_render_lines", "l3d_draw_lines", "l3d_set_projection_budget", "l3d_selftest_scan",
     "l3d_debug_lsd_stages", "l3d_match_plan", "l3d_match_tile_rows", "l3d_debug_tail_records",
     "l3d_associate_segments", "l3d_associate_view_segments",
+    "l3d_compare_segments", "l3d_compare_lines",
 ]
 
 _lib = None
@@ -322,6 +339,10 @@ def load():
     L.l3d_set_projection_budget.argtypes = [vp, u64]
     L.l3d_associate_segments.argtypes = [i32, u32, vp, vp, vp, vp, C.POINTER(AssociateParams), vp]
     L.l3d_associate_view_segments.argtypes = [vp, u32, vp, C.POINTER(AssociateParams), f64, vp, vp, vp, vp]
+    L.l3d_compare_segments.argtypes = [i32, u32, vp, vp, u32, vp, vp, C.POINTER(CompareParams), vp, vp,
+                                       C.POINTER(CompareSummary), C.POINTER(CompareSummary)]
+    L.l3d_compare_lines.argtypes = [vp, u32, vp, vp, C.POINTER(CompareParams), vp, vp, C.POINTER(CompareSummary),
+                                    C.POINTER(CompareSummary)]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("l3d_last_error", "l3d_build_info", "l3d_create", "l3d_destroy"):

@@ -15,7 +15,8 @@ import threading
 import numpy as np
 
 from . import _lib, lsd
-from ._lib import (ASSOCIATION_DTYPE, CLEDGE_DTYPE, EMPTY, FLOAT4_DTYPE, MATCH_DTYPE, PROJECTED_SEGMENT_DTYPE, SEGMENT2D_DTYPE,
+from ._lib import (ASSOCIATION_DTYPE, CLEDGE_DTYPE, EMPTY, FLOAT4_DTYPE, LINE_MATCH_DTYPE, MATCH_DTYPE, PROJECTED_SEGMENT_DTYPE,
+                   SEGMENT2D_DTYPE,
                    SEGMENT3D_DTYPE, SLOT_DTYPE, MatchParams, Timings, ptr)
 
 # commons.h:40-70
@@ -461,6 +462,32 @@ class Line3D:
         res = {int(c): out[int(off[k]):int(off[k + 1])].copy() for k, c in enumerate(ids)}
         return res, sup_s[:nl.value], sup_v[:nl.value]
 
+    # ---- this model compared with another one (no reference counterpart) ---------------------------------
+    def compareLines(self, other, max_distance, max_angle=10.0, min_overlap=0.5, exclude_same_line=False, slice_chunks=0):
+        """the 3D lines of the last reconstruct3Dlines compared with `other` -- a list of lines as get3Dlines or
+        io.read_3d_lines_txt / read_3d_lines_bin return it, or another Line3D -- in both directions -> (matches_mine,
+        matches_other, summary_mine, summary_other): a LINE_MATCH_DTYPE array with one entry per flat segment of each
+        side (flatten_lines' order) and the summaries as dicts; None after an error.  max_distance in model units,
+        max_angle in degrees [0, 90], min_overlap = the share of a segment inside its counterpart's extent."""
+        if isinstance(other, Line3D):
+            other = other.get3Dlines()
+        try:
+            par = compare_params(max_distance, max_angle, min_overlap, exclude_same_line, slice_chunks)
+            segs, line = flatten_lines(other)
+        except (ValueError, KeyError, TypeError) as e:
+            print(f"{self.PREFIX}ERROR: compareLines: {e}")
+            self.last_status = -1
+            return None
+        nl = C.c_uint32(); ns = C.c_uint32(); nr = C.c_uint32()
+        if not self._check(self.L.l3d_num_3d_lines(self.h, C.byref(nl), C.byref(ns), C.byref(nr)), "compareLines"):
+            return None
+        mine = np.zeros(max(ns.value, 1), LINE_MATCH_DTYPE); theirs = np.zeros(max(len(line), 1), LINE_MATCH_DTYPE)
+        s_mine = _lib.CompareSummary(); s_other = _lib.CompareSummary()
+        if not self._check(self.L.l3d_compare_lines(self.h, len(line), ptr(segs), ptr(line), C.byref(par), ptr(mine), ptr(theirs),
+                                                    C.byref(s_mine), C.byref(s_other)), "compareLines"):
+            return None
+        return mine[:ns.value], theirs[:len(line)], summary_dict(s_mine), summary_dict(s_other)
+
     def set_projection_budget(self, n_bytes):
         """test hook: device-memory budget of a group of cameras in the four calls above (0: the default)"""
         self.L.l3d_set_projection_budget(self.h, int(n_bytes))
@@ -694,6 +721,59 @@ def associate_segments(records_per_cam, segs_per_cam, max_distance=L3D_DEF_SCORI
     if rc != 0:
         raise RuntimeError(f"l3d_associate_segments failed [{rc}]: {_lib.last_error()}")
     return split_records(out, n_seg[:n])
+
+
+def compare_params(max_distance, max_angle=10.0, min_overlap=0.5, exclude_same_line=False, slice_chunks=0):
+    """l3d_compare_params from the wrappers' arguments: min_cos2 = cos(radians(max_angle))^2, max_angle in [0, 90]"""
+    if not 0.0 <= float(max_angle) <= 90.0:
+        raise ValueError("max_angle must lie in [0, 90] degrees")
+    cos = float(np.cos(np.radians(np.float64(max_angle))))
+    return _lib.CompareParams(float(max_distance), cos * cos, float(min_overlap), int(bool(exclude_same_line)), int(slice_chunks))
+
+
+def flatten_lines(lines):
+    """a list of 3D lines -> (segs [n, 6] float64 (P1, P2), line [n] uint32: the index of each segment's line in the
+    list).  Both list forms: the dicts of Line3D.get3Dlines (collinear3Dsegments with P1, P2) and those of
+    io.read_3d_lines_txt / read_3d_lines_bin (segments [n, 6] or [n, 9]: P1, P2 first)."""
+    segs, line = [], []
+    for i, L in enumerate(lines):
+        c = L["collinear3Dsegments"] if "collinear3Dsegments" in L else L["segments"]
+        if getattr(c, "dtype", None) is not None and c.dtype.names:
+            s = np.concatenate([np.asarray(c["P1"], np.float64).reshape(-1, 3), np.asarray(c["P2"], np.float64).reshape(-1, 3)], 1)
+        else:
+            s = np.asarray(c, np.float64)
+            s = s.reshape(len(s), -1)[:, :6] if len(s) else np.zeros((0, 6))
+        if s.shape[1] != 6:
+            raise ValueError(f"line {i}: segments need P1 and P2, six coordinates each")
+        segs.append(s)
+        line.append(np.full(len(s), i, np.uint32))
+    if not segs:
+        return np.zeros((0, 6), np.float64), np.zeros(0, np.uint32)
+    return np.ascontiguousarray(np.concatenate(segs), np.float64), np.concatenate(line)
+
+
+def summary_dict(s):
+    return {f: getattr(s, f) for f, _ in _lib.CompareSummary._fields_}
+
+
+def compare_segments(q_segs, q_line, r_segs, r_line, max_distance, max_angle=10.0, min_overlap=0.5, exclude_same_line=False,
+                     slice_chunks=0, device=0):
+    """l3d_compare_segments: two models of 3D segments, segs [n, 6] float64 (P1, P2) with a line index each,
+    compared in both directions -> (matches_q, matches_r, summary_q, summary_r): one LINE_MATCH_DTYPE entry per segment
+    of Q (its counterpart in R) and of R (its counterpart in Q); the summaries are dicts"""
+    L = _lib.load()
+    q = np.ascontiguousarray(q_segs, np.float64).reshape(-1, 6); r = np.ascontiguousarray(r_segs, np.float64).reshape(-1, 6)
+    ql = np.ascontiguousarray(q_line, np.uint32).reshape(-1); rl = np.ascontiguousarray(r_line, np.uint32).reshape(-1)
+    if len(ql) != len(q) or len(rl) != len(r):
+        raise ValueError("one line index per segment")
+    par = compare_params(max_distance, max_angle, min_overlap, exclude_same_line, slice_chunks)
+    mq = np.zeros(max(len(q), 1), LINE_MATCH_DTYPE); mr = np.zeros(max(len(r), 1), LINE_MATCH_DTYPE)
+    sq = _lib.CompareSummary(); sr = _lib.CompareSummary()
+    rc = L.l3d_compare_segments(int(device), len(q), ptr(q), ptr(ql), len(r), ptr(r), ptr(rl), C.byref(par), ptr(mq), ptr(mr),
+                                C.byref(sq), C.byref(sr))
+    if rc != 0:
+        raise RuntimeError(f"l3d_compare_segments failed [{rc}]: {_lib.last_error()}")
+    return mq[:len(q)], mr[:len(r)], summary_dict(sq), summary_dict(sr)
 
 
 def render_line_maps(cams, records, thickness=1, device=0):

@@ -296,4 +296,26 @@ struct AssocArgs {
 hipError_t launch_associate(const AssocArgs& a, uint32_t n_tiles, hipStream_t st);
 extern std::atomic<uint64_t> g_assoc_launches, g_assoc_kernel_ns;   // l3d_associate.hip, test hooks read through l3d_debug_counter
 
+// ---- k_compare.hip: two 3D line models compared segment by segment (host side: l3d_compare.hip) ----
+constexpr uint32_t kCmpTile = 256;       // queries per workgroup, one lane each
+constexpr uint32_t kCmpChunk = 256;      // references per pass through LDS (12 KiB of end points + 1 KiB of line indices)
+// = l3d_line_match, but for d2: the squared distance, of which the host takes the root after the download
+struct CmpOut { int32_t segment; uint32_t line, n_accepted; float overlap; double d2; };
+// what one slice of the references found for one query: [query * n_slices + slice]
+struct CmpPartial { unsigned long long bits; uint32_t index, n_accepted; double frac; double pad; };
+static_assert(sizeof(CmpOut) == 24 && sizeof(CmpPartial) == 32, "comparison layout");
+struct CmpArgs {
+    const double* q; const uint32_t* q_line; uint32_t n_q;   // [n_q] x (P1, P2), their lines
+    const double* r; const uint32_t* r_line; uint32_t n_r;   // the references
+    uint32_t slice_chunks, n_slices;         // chunks of kCmpChunk references per slice; slices (grid.y)
+    uint32_t exclude_same_line;
+    double max_d2, min_cos2, min_overlap;    // max_distance * max_distance, the squared cosine, the overlap share
+    CmpOut* out;                             // [n_q]
+    CmpPartial* part;                        // [n_q * n_slices], used when n_slices > 1
+};
+hipError_t launch_compare(const CmpArgs& a, hipStream_t st);         // tiles x slices; writes out (one slice) or part
+hipError_t launch_compare_merge(const CmpArgs& a, hipStream_t st);   // part -> out
+// l3d_compare.hip, test hooks read through l3d_debug_counter
+extern std::atomic<uint64_t> g_cmp_launches, g_cmp_merge_launches, g_cmp_slices, g_cmp_kernel_ns;
+
 }  // namespace l3d
