@@ -908,6 +908,60 @@ int l3d_compare_lines(l3d_ctx*, uint32_t n_other, const double* other_segs6, con
                       const l3d_compare_params* params, l3d_line_match* out_mine, l3d_line_match* out_other,
                       l3d_compare_summary* summary_mine, l3d_compare_summary* summary_other);
 
+/* ---- near-duplicate 3D lines merged (GPU: k_merge.hip) ----------------------------------------------------
+ * No reference counterpart.  One model as above: a flat array of 3D segments with a line index per segment (any values,
+ * not only dense ones).  An ordered pair of segments (q, r) is accepted iff line(q) != line(r) and the pair test of
+ * l3d_compare_segments accepts it with q as the query and r as the reference; one direction suffices.  Lines joined by
+ * accepted pairs, directly or through a chain of them, form a component; a component of two or more lines becomes one
+ * line: its live segments are projected onto a common carrier (through their length-weighted centroid, along the sum of
+ * their directions) and intervals that touch or overlap are fused.  A line in no accepted pair keeps its segments
+ * unchanged.  Output lines are numbered 0, 1, ... by the smallest input line index they hold.  fp64, the contract of
+ * DESIGN §19. */
+typedef struct l3d_merge_params {
+    double max_distance;         /* as in l3d_compare_params */
+    double min_cos2;
+    double min_overlap;
+    uint32_t slice_chunks;       /* 0: the library chooses; else chunks of 256 references per slice.  No output depends on it */
+    uint32_t reserved;           /* must be 0 */
+} l3d_merge_params;
+/* one output line (16 bytes) */
+typedef struct l3d_merge_line_info {
+    uint32_t n_members;          /* input lines fused into this one; 1: an untouched line */
+    uint32_t label;              /* the smallest input line index among them */
+    double max_offset;           /* the largest distance of a member's end point from the fused carrier; 0 for an untouched
+                                    line.  Components form by chaining: this is how a caller sees a chain that went far */
+} l3d_merge_line_info;
+/* (80 bytes); the lengths are added sequentially in ascending index order */
+typedef struct l3d_merge_summary {
+    uint64_t n_segments_in, n_segments_out;
+    uint64_t n_lines_in, n_lines_out;
+    uint64_t n_pairs;                /* accepted ordered pairs of segments */
+    uint64_t n_merged_components;    /* output lines with n_members >= 2 */
+    uint64_t largest_component;      /* the largest n_members (0: an empty model) */
+    double length_in, length_out;
+    double max_offset;               /* the largest of the lines' */
+} l3d_merge_summary;
+/* Stateless, host pointers.  segs6 [n x 6], line [n].  out_line_map [n]: the output line of every input segment (also of
+ * a point segment that a fused line dropped).  out_segs6 [out_seg_cap x 6], out_seg_line [out_seg_cap]: the output
+ * segments, line after line, and the output line of each; *out_n_segs <= n.  out_line_info [out_line_cap]; *out_n_lines
+ * <= the number of distinct line indices, which is <= n: capacities of n are always enough.  summary may be NULL.
+ * Checked before any device work, the outputs untouched: L3D_ERR_LIMIT for 2^30 or more segments; L3D_ERR_ARG for a null
+ * pointer, a coordinate that is not finite or beyond 2^100 (the message names the segment), a threshold outside its
+ * range, reserved != 0, out_seg_cap < n or out_line_cap < the number of distinct line indices.  More than 2^28 accepted
+ * pairs: L3D_ERR_LIMIT, found after the count pass, the outputs untouched.  n = 0: L3D_OK, a summary of zeros. */
+int l3d_merge_segments(int device, uint32_t n, const double* segs6, const uint32_t* line, const l3d_merge_params* params,
+                       uint32_t* out_line_map, uint32_t out_seg_cap, double* out_segs6, uint32_t* out_seg_line,
+                       uint32_t* out_n_segs, uint32_t out_line_cap, l3d_merge_line_info* out_line_info, uint32_t* out_n_lines,
+                       l3d_merge_summary* summary);
+/* The same on the context's lines (flattened as for l3d_compare_lines), which the result REPLACES: l3d_num_3d_lines,
+ * l3d_get_3d_lines, the writers and the projection, association and comparison stages see the merged model.  An
+ * untouched line keeps every field.  A fused line gets the fused segments (direction, length and validity as for any 3D
+ * segment), the carrier from its first to its last fused end point as the cluster's segment, the residuals of its members
+ * concatenated in ascending line index, and the reference view of the line of its longest member segment.  The records
+ * of the last l3d_project_lines are dropped.  l3d_output_filename carries MERGED_<max_distance>__ in front of vis_ until
+ * the next l3d_reconstruct_3d_lines.  L3D_ERR_STATE without reconstructed lines or while a split call is open. */
+int l3d_merge_lines(l3d_ctx*, const l3d_merge_params* params, l3d_merge_summary* summary);
+
 #ifdef __cplusplus
 }
 #endif

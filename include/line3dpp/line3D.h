@@ -12,6 +12,7 @@
 //     drawLines(camID | K, R, t, inImg, outImg, thickness, alpha)      (... drawn over an image)
 //     associateSegments([camID,] out, max_distance, max_angle, min_overlap)   (... and the 2D segments that observe them)
 //     compareLines(other, mine, theirs, max_distance, max_angle, min_overlap)   (... and compared with another model)
+//     mergeLines(max_distance, max_angle, min_overlap)                           (... and their near-duplicates merged)
 //
 // Same names, argument order, defaults (commons.h:40-70) and error behaviour as the reference: errors
 // are printed with the "[L3D++] ERROR:" prefix and the call returns (void), no exceptions
@@ -516,6 +517,23 @@ public:
         b.resize(line.size());
         mine.swap(a);
         theirs.swap(b);
+    }
+
+    // The near-duplicate lines of this model merged (no reference counterpart; DESIGN §19, k_merge.hip): lines joined by
+    // accepted pairs of segments -- compareLines' pair test, between different lines -- become one line, and the merged
+    // model takes the place of lines3D_: get3Dlines, the writers, projectLines, associateSegments and compareLines see
+    // it; saved files carry MERGED_<max_distance>__ in their name until the next reconstruct3Dlines.  max_distance in
+    // model units, max_angle in degrees [0, 90], min_overlap = the share of a segment inside its counterpart's extent.
+    // summary (may be null): the counts of the merge.  Errors are printed and leave the model as it was.
+    void mergeLines(const double max_distance, const double max_angle = 10.0, const double min_overlap = 0.5,
+                    l3d_merge_summary* summary = nullptr) {
+        if (!(max_angle >= 0.0 && max_angle <= 90.0)) {
+            std::cout << prefix_err_ << "mergeLines: max_angle must lie in [0, 90] degrees" << std::endl;
+            return;
+        }
+        const double cosine = std::cos(max_angle * (3.14159265358979323846 / 180.0));
+        const l3d_merge_params par{max_distance, cosine * cosine, min_overlap, 0u, 0u};
+        if (l3d_merge_lines(ctx_, &par, summary) != L3D_OK) std::cout << prefix_err_ << "mergeLines: " << l3d_last_error() << std::endl;
     }
 
     // The 3D lines drawn over inImg (cv::Mat, Image8U or ImageBuf8U, 8-bit with 1 or 3 channels, of the camera's size):

@@ -39,6 +39,9 @@ assert ASSOCIATION_DTYPE.itemsize == 24
 LINE_MATCH_DTYPE = np.dtype([("segment", "<i4"), ("line", "<u4"), ("n_accepted", "<u4"), ("overlap", "<f4"),
                              ("distance", "<f8")])
 assert LINE_MATCH_DTYPE.itemsize == 24
+# l3d_merge_line_info: one line of a merged model
+MERGE_LINE_INFO_DTYPE = np.dtype([("n_members", "<u4"), ("label", "<u4"), ("max_offset", "<f8")])
+assert MERGE_LINE_INFO_DTYPE.itemsize == 16
 EMPTY = 0xFFFFFFFF
 L3D_ERR_NO_SEGMENTS = -5
 L3D_ERR_IO = -11
@@ -146,6 +149,20 @@ class CompareSummary(C.Structure):
                 ("n_lines_matched", C.c_uint64), ("length_total", C.c_double), ("length_matched", C.c_double)]
 
 
+class MergeParams(C.Structure):
+    """l3d_merge_params (include/l3dpp_hip.h)"""
+    _fields_ = [("max_distance", C.c_double), ("min_cos2", C.c_double), ("min_overlap", C.c_double),
+                ("slice_chunks", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class MergeSummary(C.Structure):
+    """l3d_merge_summary (include/l3dpp_hip.h)"""
+    _fields_ = [("n_segments_in", C.c_uint64), ("n_segments_out", C.c_uint64), ("n_lines_in", C.c_uint64),
+                ("n_lines_out", C.c_uint64), ("n_pairs", C.c_uint64), ("n_merged_components", C.c_uint64),
+                ("largest_component", C.c_uint64), ("length_in", C.c_double), ("length_out", C.c_double),
+                ("max_offset", C.c_double)]
+
+
 class DetectStats(C.Structure):
     """l3d_detect_stats (include/l3dpp_hip.h)"""
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("raw_segments", C.c_uint32), ("segments", C.c_uint32),
@@ -207,6 +224,7 @@ EXPORTS = [
     "l3d_debug_lsd_stages", "l3d_match_plan", "l3d_match_tile_rows", "l3d_debug_tail_records",
     "l3d_associate_segments", "l3d_associate_view_segments",
     "l3d_compare_segments", "l3d_compare_lines",
+    "l3d_merge_segments", "l3d_merge_lines",
 ]
 
 _lib = None
@@ -343,6 +361,9 @@ def load():
                                        C.POINTER(CompareSummary), C.POINTER(CompareSummary)]
     L.l3d_compare_lines.argtypes = [vp, u32, vp, vp, C.POINTER(CompareParams), vp, vp, C.POINTER(CompareSummary),
                                     C.POINTER(CompareSummary)]
+    L.l3d_merge_segments.argtypes = [i32, u32, vp, vp, C.POINTER(MergeParams), vp, u32, vp, vp, C.POINTER(u32), u32, vp,
+                                     C.POINTER(u32), C.POINTER(MergeSummary)]
+    L.l3d_merge_lines.argtypes = [vp, C.POINTER(MergeParams), C.POINTER(MergeSummary)]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("l3d_last_error", "l3d_build_info", "l3d_create", "l3d_destroy"):

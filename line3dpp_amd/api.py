@@ -15,8 +15,8 @@ import threading
 import numpy as np
 
 from . import _lib, lsd
-from ._lib import (ASSOCIATION_DTYPE, CLEDGE_DTYPE, EMPTY, FLOAT4_DTYPE, LINE_MATCH_DTYPE, MATCH_DTYPE, PROJECTED_SEGMENT_DTYPE,
-                   SEGMENT2D_DTYPE,
+from ._lib import (ASSOCIATION_DTYPE, CLEDGE_DTYPE, EMPTY, FLOAT4_DTYPE, LINE_MATCH_DTYPE, MATCH_DTYPE, MERGE_LINE_INFO_DTYPE,
+                   PROJECTED_SEGMENT_DTYPE, SEGMENT2D_DTYPE,
                    SEGMENT3D_DTYPE, SLOT_DTYPE, MatchParams, Timings, ptr)
 
 # commons.h:40-70
@@ -488,6 +488,23 @@ class Line3D:
             return None
         return mine[:ns.value], theirs[:len(line)], summary_dict(s_mine), summary_dict(s_other)
 
+    # ---- near-duplicate lines merged (no reference counterpart) -------------------------------------------
+    def mergeLines(self, max_distance, max_angle=10.0, min_overlap=0.5, slice_chunks=0):
+        """the 3D lines of the last reconstruct3Dlines replaced by the merged model: lines joined by accepted pairs of
+        segments (the pair test of compareLines, between different lines) become one line -> the summary as a dict; None
+        after an error.  get3Dlines, the writers, projectLines, associateSegments and compareLines see the merged model;
+        outputFilename carries MERGED_<max_distance>__ until the next reconstruct3Dlines."""
+        try:
+            par = merge_params(max_distance, max_angle, min_overlap, slice_chunks)
+        except (ValueError, TypeError) as e:
+            print(f"{self.PREFIX}ERROR: mergeLines: {e}")
+            self.last_status = -1
+            return None
+        s = _lib.MergeSummary()
+        if not self._check(self.L.l3d_merge_lines(self.h, C.byref(par), C.byref(s)), "mergeLines"):
+            return None
+        return merge_summary_dict(s)
+
     def set_projection_budget(self, n_bytes):
         """test hook: device-memory budget of a group of cameras in the four calls above (0: the default)"""
         self.L.l3d_set_projection_budget(self.h, int(n_bytes))
@@ -774,6 +791,37 @@ def compare_segments(q_segs, q_line, r_segs, r_line, max_distance, max_angle=10.
     if rc != 0:
         raise RuntimeError(f"l3d_compare_segments failed [{rc}]: {_lib.last_error()}")
     return mq[:len(q)], mr[:len(r)], summary_dict(sq), summary_dict(sr)
+
+
+def merge_params(max_distance, max_angle=10.0, min_overlap=0.5, slice_chunks=0):
+    """l3d_merge_params from the wrappers' arguments, by compare_params' degree rule"""
+    p = compare_params(max_distance, max_angle, min_overlap, False, slice_chunks)
+    return _lib.MergeParams(p.max_distance, p.min_cos2, p.min_overlap, p.slice_chunks, 0)
+
+
+def merge_summary_dict(s):
+    return {f: getattr(s, f) for f, _ in _lib.MergeSummary._fields_}
+
+
+def merge_segments(segs, line, max_distance, max_angle=10.0, min_overlap=0.5, slice_chunks=0, device=0):
+    """l3d_merge_segments: one model of 3D segments, segs [n, 6] float64 (P1, P2) with a line index each ->
+    (segs_out [m, 6], line_out [m] uint32: the output line of each output segment, line_map [n] uint32: the output line
+    of each input segment, line_info: one MERGE_LINE_INFO_DTYPE entry per output line, summary: a dict)"""
+    L = _lib.load()
+    s = np.ascontiguousarray(segs, np.float64).reshape(-1, 6)
+    ln = np.ascontiguousarray(line, np.uint32).reshape(-1)
+    if len(ln) != len(s):
+        raise ValueError("one line index per segment")
+    par = merge_params(max_distance, max_angle, min_overlap, slice_chunks)
+    n = len(s); cap = max(n, 1)
+    line_map = np.zeros(cap, np.uint32); out = np.zeros((cap, 6), np.float64); out_line = np.zeros(cap, np.uint32)
+    info = np.zeros(cap, MERGE_LINE_INFO_DTYPE)
+    n_segs = C.c_uint32(); n_lines = C.c_uint32(); summary = _lib.MergeSummary()
+    rc = L.l3d_merge_segments(int(device), n, ptr(s), ptr(ln), C.byref(par), ptr(line_map), cap, ptr(out), ptr(out_line),
+                              C.byref(n_segs), cap, ptr(info), C.byref(n_lines), C.byref(summary))
+    if rc != 0:
+        raise RuntimeError(f"l3d_merge_segments failed [{rc}]: {_lib.last_error()}")
+    return out[:n_segs.value], out_line[:n_segs.value], line_map[:n], info[:n_lines.value], merge_summary_dict(summary)
 
 
 def render_line_maps(cams, records, thickness=1, device=0):

@@ -28,16 +28,7 @@ __global__ __launch_bounds__(kCmpTile) void k_compare(CmpArgs a) {
     const uint32_t tile = blockIdx.x / a.n_slices, slice = blockIdx.x - tile * a.n_slices;
     const uint32_t q = tile * kCmpTile + threadIdx.x;
     const bool in_range = q < a.n_q;
-    double px = 0.0, py = 0.0, pz = 0.0, sx = 0.0, sy = 0.0, sz = 0.0;
-    uint32_t my_line = 0;
-    if (in_range) {
-        const double* v = a.q + 6 * (size_t)q;
-        px = v[0]; py = v[1]; pz = v[2]; sx = v[3]; sy = v[4]; sz = v[5];
-        my_line = a.q_line[q];
-    }
-    const double ex = sx - px, ey = sy - py, ez = sz - pz;
-    const double E2 = ex * ex + ey * ey + ez * ez;
-    const bool live = in_range && E2 > 0.0;
+    const CmpQuery me = cmp_query(a.q + 6 * (size_t)(in_range ? q : 0), in_range ? a.q_line[q] : 0u, in_range);
     unsigned long long best_bits = ~0ull;
     uint32_t best_r = 0xFFFFFFFFu, n_acc = 0;
     double best_frac = 0.0;
@@ -53,37 +44,12 @@ __global__ __launch_bounds__(kCmpTile) void k_compare(CmpArgs a) {
         if (threadIdx.x < n) s_line[threadIdx.x] = a.r_line[r0 + threadIdx.x];
         __syncthreads();
         for (uint32_t k = 0; k < n; ++k) {
-            // 1. reference vector and length
-            const double bx = s_p[6 * k], by = s_p[6 * k + 1], bz = s_p[6 * k + 2];
-            const double dx = s_p[6 * k + 3] - bx, dy = s_p[6 * k + 4] - by, dz = s_p[6 * k + 5] - bz;
-            const double L2 = dx * dx + dy * dy + dz * dz;
-            if (!(L2 > 0.0)) continue;                                           // (uniform)
-            if (!live) continue;
-            // 3. the same line
-            if (a.exclude_same_line && s_line[k] == my_line) continue;
-            // 4. angle
-            const double dot = dx * ex + dy * ey + dz * ez;
-            if (!(dot * dot >= a.min_cos2 * (L2 * E2))) continue;
-            // 5. distance
-            const double wx = px - bx, wy = py - by, wz = pz - bz;
-            const double ux = sx - bx, uy = sy - by, uz = sz - bz;
-            const double c1x = dy * wz - dz * wy, c1y = dz * wx - dx * wz, c1z = dx * wy - dy * wx;
-            const double c2x = dy * uz - dz * uy, c2y = dz * ux - dx * uz, c2z = dx * uy - dy * ux;
-            const double m1 = c1x * c1x + c1y * c1y + c1z * c1z;
-            const double m2 = c2x * c2x + c2y * c2y + c2z * c2z;
-            const double D2 = (m1 > m2 ? m1 : m2) / L2;
-            if (!(D2 <= a.max_d2)) continue;
-            // 6. overlap
-            const double t1 = (dx * wx + dy * wy + dz * wz) / L2;
-            const double t2 = (dx * ux + dy * uy + dz * uz) / L2;
-            const double tlo = t1 < t2 ? t1 : t2, thi = t1 < t2 ? t2 : t1;
-            const double ov = (thi < 1.0 ? thi : 1.0) - (tlo > 0.0 ? tlo : 0.0);
-            if (!(ov > 0.0)) continue;
-            const double frac = ov / (thi - tlo);
-            if (!(frac >= a.min_overlap)) continue;
-            ++n_acc;
-            const unsigned long long bits = (unsigned long long)__double_as_longlong(D2);
-            if (bits < best_bits) { best_bits = bits; best_r = r0 + k; best_frac = frac; }
+            // steps 1-6: l3d_kernels.h
+            cmp_pair(me, s_p + 6 * k, s_line[k], a.exclude_same_line != 0, a.max_d2, a.min_cos2, a.min_overlap, [&](double D2, double frac) {
+                ++n_acc;
+                const unsigned long long bits = (unsigned long long)__double_as_longlong(D2);
+                if (bits < best_bits) { best_bits = bits; best_r = r0 + k; best_frac = frac; }
+            });
         }
     }
     if (!in_range) return;

@@ -175,6 +175,11 @@ unsigned long long l3d_debug_counter(const char* name) {
     if (name && std::string(name) == "compare_merge_launches") return g_cmp_merge_launches.load(std::memory_order_relaxed);
     if (name && std::string(name) == "compare_slices") return g_cmp_slices.load(std::memory_order_relaxed);
     if (name && std::string(name) == "compare_kernel_ns") return g_cmp_kernel_ns.load(std::memory_order_relaxed);
+    if (name && std::string(name) == "merge_count_launches") return g_mrg_count_launches.load(std::memory_order_relaxed);
+    if (name && std::string(name) == "merge_write_launches") return g_mrg_write_launches.load(std::memory_order_relaxed);
+    if (name && std::string(name) == "merge_slices") return g_mrg_slices.load(std::memory_order_relaxed);
+    if (name && std::string(name) == "merge_pairs") return g_mrg_pairs.load(std::memory_order_relaxed);
+    if (name && std::string(name) == "merge_kernel_ns") return g_mrg_kernel_ns.load(std::memory_order_relaxed);
     if (name && std::string(name) == "live_device_blocks") return g_live_blocks[0].load(std::memory_order_relaxed);
     if (name && std::string(name) == "live_pinned_blocks") return g_live_blocks[1].load(std::memory_order_relaxed);
     static const char* const kSeamSupport[4] = {"seam_support_wave_lists", "seam_support_group_staged_lists",

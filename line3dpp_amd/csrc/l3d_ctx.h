@@ -306,6 +306,8 @@ struct l3d_ctx {
     std::vector<l3d_segment2d> l2g;
     std::vector<ReconLine> lines3D;                 // lines3D_ (original frame)
     bool lines_done = false;
+    bool lines_merged = false;                      // l3d_merge_lines has replaced lines3D since the last reconstruct3Dlines
+    double merged_distance = 0.0;                   // ... with this max_distance (l3d_output_filename)
     // line bundling (use_CERES_ of the last reconstruct3Dlines; l3d_lineopt.hip)
     bool use_ceres = false;
     l3d_line_opt_summary lo_stats{};

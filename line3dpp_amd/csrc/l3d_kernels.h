@@ -313,9 +313,74 @@ struct CmpArgs {
     CmpOut* out;                             // [n_q]
     CmpPartial* part;                        // [n_q * n_slices], used when n_slices > 1
 };
+// Steps 1-6 of DESIGN §18 for one pair, shared by k_compare.hip and k_merge.hip so that the two stages cannot drift apart.
+// CmpQuery holds step 2, computed once per lane; cmp_pair runs the others on one reference r6 = (P1, P2) and calls
+// accept(D2, frac), with the squared distance and the overlap share, iff the pair is accepted.  The tests are
+// ordered cheapest first; a pair is accepted iff all hold, so the order changes nothing.
+struct CmpQuery { double px, py, pz, sx, sy, sz, ex, ey, ez, E2; uint32_t line; bool live; };
+__device__ __forceinline__ CmpQuery cmp_query(const double* v, uint32_t line, bool in_range) {
+    CmpQuery q{0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0u, false};
+    if (in_range) { q.px = v[0]; q.py = v[1]; q.pz = v[2]; q.sx = v[3]; q.sy = v[4]; q.sz = v[5]; q.line = line; }
+    q.ex = q.sx - q.px; q.ey = q.sy - q.py; q.ez = q.sz - q.pz;
+    q.E2 = q.ex * q.ex + q.ey * q.ey + q.ez * q.ez;
+    q.live = in_range && q.E2 > 0.0;
+    return q;
+}
+template <class Accept>
+__device__ __forceinline__ void cmp_pair(const CmpQuery& q, const double* r6, uint32_t r_line, bool exclude_same_line,
+                                         double max_d2, double min_cos2, double min_overlap, Accept&& accept) {
+    // 1. reference vector and length
+    const double bx = r6[0], by = r6[1], bz = r6[2];
+    const double dx = r6[3] - bx, dy = r6[4] - by, dz = r6[5] - bz;
+    const double L2 = dx * dx + dy * dy + dz * dz;
+    if (!(L2 > 0.0)) return;                                       // (uniform over the workgroup)
+    // 2. the query
+    if (!q.live) return;
+    // 3. the same line
+    if (exclude_same_line && r_line == q.line) return;
+    // 4. angle
+    const double dot = dx * q.ex + dy * q.ey + dz * q.ez;
+    if (!(dot * dot >= min_cos2 * (L2 * q.E2))) return;
+    // 5. distance
+    const double wx = q.px - bx, wy = q.py - by, wz = q.pz - bz;
+    const double ux = q.sx - bx, uy = q.sy - by, uz = q.sz - bz;
+    const double c1x = dy * wz - dz * wy, c1y = dz * wx - dx * wz, c1z = dx * wy - dy * wx;
+    const double c2x = dy * uz - dz * uy, c2y = dz * ux - dx * uz, c2z = dx * uy - dy * ux;
+    const double m1 = c1x * c1x + c1y * c1y + c1z * c1z;
+    const double m2 = c2x * c2x + c2y * c2y + c2z * c2z;
+    const double D2 = (m1 > m2 ? m1 : m2) / L2;
+    if (!(D2 <= max_d2)) return;
+    // 6. overlap
+    const double t1 = (dx * wx + dy * wy + dz * wz) / L2;
+    const double t2 = (dx * ux + dy * uy + dz * uz) / L2;
+    const double tlo = t1 < t2 ? t1 : t2, thi = t1 < t2 ? t2 : t1;
+    const double ov = (thi < 1.0 ? thi : 1.0) - (tlo > 0.0 ? tlo : 0.0);
+    if (!(ov > 0.0)) return;
+    const double frac = ov / (thi - tlo);
+    if (!(frac >= min_overlap)) return;
+    accept(D2, frac);
+}
 hipError_t launch_compare(const CmpArgs& a, hipStream_t st);         // tiles x slices; writes out (one slice) or part
 hipError_t launch_compare_merge(const CmpArgs& a, hipStream_t st);   // part -> out
 // l3d_compare.hip, test hooks read through l3d_debug_counter
 extern std::atomic<uint64_t> g_cmp_launches, g_cmp_merge_launches, g_cmp_slices, g_cmp_kernel_ns;
+
+// ---- k_merge.hip: the accepted pairs of one model against itself, as a list (host side: l3d_merge.hip) ----
+// k_compare's tiling (kCmpTile queries x one slice of the references per workgroup, chunks of kCmpChunk through LDS).
+struct MrgPair { uint32_t q, r; };
+struct MrgArgs {
+    const double* segs; const uint32_t* line; uint32_t n;    // [n] x (P1, P2), their lines: queries and references alike
+    uint32_t slice_chunks, n_slices;
+    double max_d2, min_cos2, min_overlap;
+    uint32_t* counts;                        // [n * n_slices + 1]: k_merge_count's counts at [q * n_slices + slice], then
+                                             // their exclusive scan in place (the total behind the last one)
+    MrgPair* pairs; uint32_t n_pairs;        // [n_pairs = the total], written by k_merge_write
+    uint32_t* wrapped;                       // k_merge_check: set to 1 where the 32-bit scan has wrapped
+};
+hipError_t launch_merge_count(const MrgArgs& a, hipStream_t st);
+hipError_t launch_merge_write(const MrgArgs& a, hipStream_t st);
+hipError_t launch_merge_check(const MrgArgs& a, hipStream_t st);
+// l3d_merge.hip, test hooks read through l3d_debug_counter
+extern std::atomic<uint64_t> g_mrg_count_launches, g_mrg_write_launches, g_mrg_slices, g_mrg_pairs, g_mrg_kernel_ns;
 
 }  // namespace l3d
