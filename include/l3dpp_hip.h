@@ -682,6 +682,58 @@ typedef struct l3d_tail_records {
 } l3d_tail_records;
 int l3d_debug_tail_records(l3d_ctx*, int query_only, l3d_tail_records* out);
 
+/* Test hook (device, read only): what every stage of the affinity fill (k_affinity.hip, l3d_affinity_host.hip)
+ * left behind after the last l3d_compute_affinity / l3d_affinity_shard_begin / _finish / l3d_reconstruct_3d_lines.  It
+ * synchronises the stream and copies device to host; it launches nothing and writes nothing on the device.  It answers
+ * L3D_ERR_STATE when no affinity step has run on the current matches, so a stale buffer is never handed out.  With
+ * query_only != 0 only the sizes are filled, without touching the device; the caller then allocates.  Every pointer may
+ * be NULL (that array is not copied).
+ *   mode 0  the parallel path: every array up to l2g
+ *   mode 1  the collinear path (collinearity_t > 0): inputs, simv, cand_*, coll_*, the child and own candidate streams
+ *           (the third stream the host pass walks is the primary one: surv_off / surv_tg / simv), and the host pass's edges
+ *           and l2g
+ *   mode 2  between l3d_affinity_shard_begin and _finish: inputs, simv (this rank's window only) and cand_*
+ * n_cand is N when the fill ran (N > 0 and H > 0) and 0 otherwise: the length of every per-candidate array; when it is 0
+ * only the inputs are copied.  diffused != 0: l3d_reconstruct_3d_lines has replaced the edges on the device by the
+ * diffused matrix, which is NOT the fill's output: `edges` is then left untouched. */
+typedef struct l3d_affinity_records {
+    /* out: sizes and scalars */
+    uint32_t N, H, G, V;              /* surviving matches, best hypotheses, 2D segments of all views, views */
+    uint32_t n_cand, mode, diffused;
+    uint32_t n_edges, n_rows;         /* CLEdge entries (two per edge) and matrix rows; 0 in mode 2 */
+    uint32_t epos_total, touch_total; /* totals of the two scans as they lie on the device (mode 0, filled by the copying call) */
+    uint32_t n_coll, n_child, n_own;  /* entries of coll_idx and of the two streams (mode 1) */
+    float two_sigA_sqr, med_scene_depth_lines;
+    /* in: host buffers */
+    float* view_k;                    /* V: View::k_ as the kernel read it */
+    float* msdl_dev;                  /* 1: med_scene_depth_lines_ as the kernel read it */
+    float* medians;                   /* V: the medians the kernel read */
+    uint8_t* hyps;                    /* H x 128: HypRec as it lies */
+    uint32_t* surv_off;               /* G + 1 */
+    uint32_t* surv_sg;                /* N */
+    uint32_t* surv_tg;                /* N */
+    int32_t* hyp_of_seg;              /* G */
+    float* simv;                      /* n_cand */
+    int32_t* cand_a;                  /* n_cand */
+    int32_t* cand_b;                  /* n_cand */
+    uint32_t* flag;                   /* n_cand */
+    uint32_t* epos;                   /* n_cand */
+    uint32_t* first_touch;            /* H */
+    uint32_t* touch_flag;             /* 2 n_cand + 1 */
+    uint32_t* touch_rank;             /* 2 n_cand */
+    l3d_cledge* edges;                /* n_edges */
+    l3d_segment2d* l2g;               /* n_rows */
+    uint32_t* coll_off;               /* G + 1 */
+    uint32_t* coll_idx;               /* n_coll: segment index inside its view */
+    uint32_t* child_off;              /* N + 1 */
+    uint32_t* child_seg;              /* n_child: global segment */
+    float* child_sim;                 /* n_child */
+    uint32_t* own_off;                /* H + 1 */
+    uint32_t* own_seg;                /* n_own: global segment */
+    float* own_sim;                   /* n_own */
+} l3d_affinity_records;
+int l3d_debug_affinity_records(l3d_ctx*, int query_only, l3d_affinity_records* out);
+
 /* ---- (2) seam layer ------------------------------------------------------------------ */
 
 /* Replaces match_lines_GPU (cudawrapper.h:54-63; caller Line3D::matchingGPU line3D.cc:1040-1074)

@@ -188,6 +188,23 @@ class TailRecords(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in SIZES] + [("n_slots", C.c_uint64)] + [(n, C.c_void_p) for n in BUFFERS]
 
 
+class AffinityRecords(C.Structure):
+    """l3d_affinity_records (include/l3dpp_hip.h): sizes and scalars out, host buffers in"""
+    SIZES = ("N", "H", "G", "V", "n_cand", "mode", "diffused", "n_edges", "n_rows", "epos_total", "touch_total", "n_coll",
+             "n_child", "n_own")
+    BUFFERS = ("view_k", "msdl_dev", "medians", "hyps", "surv_off", "surv_sg", "surv_tg", "hyp_of_seg", "simv", "cand_a",
+               "cand_b", "flag", "epos", "first_touch", "touch_flag", "touch_rank", "edges", "l2g", "coll_off", "coll_idx",
+               "child_off", "child_seg", "child_sim", "own_off", "own_seg", "own_sim")
+    _fields_ = [(n, C.c_uint32) for n in SIZES] + [("two_sigA_sqr", C.c_float), ("med_scene_depth_lines", C.c_float)] + \
+        [(n, C.c_void_p) for n in BUFFERS]
+
+
+# l3d_dev.h: HypRec (128 bytes) as l3d_debug_affinity_records hands it out
+HYP_REC_DTYPE = np.dtype([("P1", "<f8", 3), ("P2", "<f8", 3), ("dir", "<f8", 3), ("length", "<f4"), ("valid", "<u4"),
+                          ("m", MATCH_DTYPE), ("view", "<u4"), ("pad", "<u4")])
+assert HYP_REC_DTYPE.itemsize == 128
+
+
 # l3d_lists.h: HypHdr (64 bytes), EdgeRec (16), SegHdr (16) as the hook hands them out
 HYP_HDR_DTYPE = np.dtype([("g", "<u4"), ("ref", "<u4"), ("pair_flags", "<u4"), ("canon", "<u4"), ("dp1", "<f4"), ("dp2", "<f4"),
                           ("edge_begin", "<u4"), ("edge_cnt", "<u4"), ("score3D", "<f4"), ("state", "<u4"), ("tgt_seg", "<u4"),
@@ -222,6 +239,7 @@ EXPORTS = [
     "l3d_project_segments", "l3d_render_line_maps", "l3d_draw_line_maps", "l3d_view_camera", "l3d_project_lines",
     "l3d_get_projected_lines", "l3d_render_lines", "l3d_draw_lines", "l3d_set_projection_budget", "l3d_selftest_scan",
     "l3d_debug_lsd_stages", "l3d_match_plan", "l3d_match_tile_rows", "l3d_debug_tail_records",
+    "l3d_debug_affinity_records",
     "l3d_associate_segments", "l3d_associate_view_segments",
     "l3d_compare_segments", "l3d_compare_lines",
     "l3d_merge_segments", "l3d_merge_lines",
@@ -332,6 +350,7 @@ def load():
     L.l3d_get_detect_stats.argtypes = [vp, vp, u32, C.POINTER(u32)]
     L.l3d_debug_lsd_stages.argtypes = [vp, u32, vp, i32, i32, vp]
     L.l3d_debug_tail_records.argtypes = [vp, i32, C.POINTER(TailRecords)]
+    L.l3d_debug_affinity_records.argtypes = [vp, i32, C.POINTER(AffinityRecords)]
     L.l3d_add_view_image.argtypes = [vp, u32, C.POINTER(Image), C.POINTER(DetectOptions), vp, vp, vp, f32, vp, u32,
                                      C.POINTER(u32)]
     L.l3d_add_view_image_worldpoints.argtypes = [vp, u32, C.POINTER(Image), C.POINTER(DetectOptions), vp, vp, vp, f32,

@@ -642,6 +642,45 @@ class Line3D:
         out["headers"] = out.pop("hdr_words"); out["edges"] = out.pop("edge_words"); out["segs"] = out.pop("seg_words")
         return out
 
+    def affinity_records(self):
+        """l3d_debug_affinity_records (test hook): what every stage of the affinity fill left behind -> dict: the sizes (N, H,
+        G, V, n_cand, n_edges, n_rows, epos_total, touch_total, n_coll, n_child, n_own), mode (0 parallel path, 1 collinear
+        path, 2 similarities only: between affinityShardBegin and affinityShardFinish), diffused, two_sigA_sqr,
+        med_scene_depth_lines, and the arrays: view_k, msdl_dev, medians, hyps (HYP_REC_DTYPE), surv_off, surv_sg, surv_tg,
+        hyp_of_seg, simv, cand_a, cand_b; mode 0: flag, epos, first_touch, touch_flag, touch_rank, edges, l2g; mode 1:
+        coll_off, coll_idx, child_off / child_seg / child_sim, own_off / own_seg / own_sim, edges, l2g.  `edges` is None when
+        the device holds the diffused matrix instead.  None (and last_status) when no affinity step has run on the
+        current matches."""
+        from ._lib import HYP_REC_DTYPE, AffinityRecords
+        t = AffinityRecords()
+        if not self._check(self.L.l3d_debug_affinity_records(self.h, 1, C.byref(t)), "affinity_records"):
+            return None
+        N, H, G, V, n, mode = t.N, t.H, t.G, t.V, t.n_cand, t.mode
+        u32, i32, f32 = np.uint32, np.int32, np.float32
+        bufs = dict(view_k=np.zeros(V, f32), msdl_dev=np.zeros(1, f32), medians=np.zeros(V, f32),
+                    hyps=np.zeros(H, HYP_REC_DTYPE), surv_off=np.zeros(G + 1, u32), surv_sg=np.zeros(N, u32),
+                    surv_tg=np.zeros(N, u32), hyp_of_seg=np.zeros(G, i32), simv=np.zeros(n, f32), cand_a=np.zeros(n, i32),
+                    cand_b=np.zeros(n, i32))
+        if mode == 0:
+            bufs.update(flag=np.zeros(n, u32), epos=np.zeros(n, u32), first_touch=np.zeros(H if n else 0, u32),
+                        touch_flag=np.zeros(2 * n + 1 if n else 0, u32), touch_rank=np.zeros(2 * n, u32))
+        if mode == 1:
+            bufs.update(coll_off=np.zeros(G + 1, u32), coll_idx=np.zeros(t.n_coll, u32),
+                        child_off=np.zeros(N + 1, u32), child_seg=np.zeros(t.n_child, u32), child_sim=np.zeros(t.n_child, f32),
+                        own_off=np.zeros(H + 1, u32), own_seg=np.zeros(t.n_own, u32), own_sim=np.zeros(t.n_own, f32))
+        if mode in (0, 1):
+            bufs.update(edges=np.zeros(t.n_edges, CLEDGE_DTYPE), l2g=np.zeros(t.n_rows, SEGMENT2D_DTYPE))
+        for k, a in bufs.items():
+            setattr(t, k, a.ctypes.data if a.size else None)
+        if not self._check(self.L.l3d_debug_affinity_records(self.h, 0, C.byref(t)), "affinity_records"):
+            return None
+        out = {k: int(getattr(t, k)) for k in AffinityRecords.SIZES}
+        out["two_sigA_sqr"] = np.float32(t.two_sigA_sqr); out["med_scene_depth_lines"] = np.float32(t.med_scene_depth_lines)
+        out.update(bufs)
+        if t.diffused and "edges" in out:
+            out["edges"] = None
+        return out
+
     def setTimingLevel(self, level):
         """l3d_set_timing_level: 1 = the match kernel only (default), 2 = every phase timed with HIP events (profiling), 0 = none"""
         return self._check(self.L.l3d_set_timing_level(self.h, int(level)), "setTimingLevel")

@@ -17,49 +17,8 @@
 
 namespace l3d {
 
-namespace {
-
-// Segment3D::distance_Point2Line, segment3D.h:69-73: P1 + (dir * v^T) * dir with Eigen's evaluation
-// order (outer product first, then row sums left to right)
-__device__ __forceinline__ float dist_p2l(const HypRec& s, const double* P) {
-    const d3 p1{s.P1[0], s.P1[1], s.P1[2]}, dir{s.dir[0], s.dir[1], s.dir[2]}, p{P[0], P[1], P[2]};
-    const d3 v = p - p1;
-    const d3 h{p1.x + (((dir.x * v.x) * dir.x + (dir.x * v.y) * dir.y) + (dir.x * v.z) * dir.z),
-               p1.y + (((dir.y * v.x) * dir.x + (dir.y * v.y) * dir.y) + (dir.y * v.z) * dir.z),
-               p1.z + (((dir.z * v.x) * dir.x + (dir.z * v.y) * dir.y) + (dir.z * v.z) * dir.z)};
-    return (float)norm(h - p);
-}
-
-__device__ __forceinline__ float expf_ref(float y) { return (float)exp((double)y); }
-
-// Line3D::similarity(s1,m1,seg2,truncate=false), line3D.cc:1467-1553
-__device__ __forceinline__ float sim_affinity(const HypRec& h1, const HypRec& h2, float k1, float md1, float k2,
-                                              float md2, float med_scene_depth_lines, float two_sigA_sqr) {
-    if (h1.length < kEps || h2.length < kEps) return 0.0f;
-    const float dot_p = (float)dot(d3{h1.dir[0], h1.dir[1], h1.dir[2]}, d3{h2.dir[0], h2.dir[1], h2.dir[2]});
-    float angle = (float)(acos((double)fmaxf(fminf(dot_p, 1.0f), -1.0f)) / M_PI * 180.0f);
-    if (angle > 90.0f) angle = 180.0f - angle;
-    const float y_a = -angle * angle / two_sigA_sqr;
-    float cutoff1 = md1, cutoff2 = md2;
-    if (med_scene_depth_lines > kEps) {
-        cutoff1 = fminf(cutoff1, med_scene_depth_lines);
-        cutoff2 = fminf(cutoff2, med_scene_depth_lines);
-    }
-    const float d11 = dist_p2l(h2, h1.P1), d12 = dist_p2l(h2, h1.P2);
-    const float d21 = dist_p2l(h1, h2.P1), d22 = dist_p2l(h1, h2.P2);
-    const float sig11 = (h1.m.dp1 > cutoff1) ? cutoff1 * k1 : h1.m.dp1 * k1;
-    const float sig12 = (h1.m.dp2 > cutoff1) ? cutoff1 * k1 : h1.m.dp2 * k1;
-    const float reg11 = 2.0f * sig11 * sig11, reg12 = 2.0f * sig12 * sig12;
-    const float sig21 = (h2.m.dp1 > cutoff2) ? cutoff2 * k2 : h2.m.dp1 * k2;
-    const float sig22 = (h2.m.dp2 > cutoff2) ? cutoff2 * k2 : h2.m.dp2 * k2;
-    const float reg21 = 2.0f * sig21 * sig21, reg22 = 2.0f * sig22 * sig22;
-    // fmin over five expf values == expf of the fmin of their arguments (monotone, NaNs skipped alike)
-    const float y_p1 = fminf(-d11 * d11 / reg11, -d12 * d12 / reg12);
-    const float y_p2 = fminf(-d21 * d21 / reg21, -d22 * d22 / reg22);
-    return expf_ref(fminf(y_a, fminf(y_p1, y_p2)));
-}
-
-}  // namespace
+// dist_p2l, expf_ref and sim_affinity (Line3D::similarity, line3D.cc:1467-1553) live in l3d_dev.h: host and device, so that
+// tests/cpp/sim_affinity.cpp can pin them on the CPU
 
 // candidate c = surviving match c of the global pool (views ascending, segments ascending, list order)
 // [lo, hi): the candidates whose similarity THIS launch computes -- all of them on one GPU; with the affinity fill

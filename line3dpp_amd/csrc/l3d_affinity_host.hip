@@ -28,11 +28,13 @@ static int affinity_collinear(l3d_ctx* c) {
     L3D_HIP_CHECK(hipStreamSynchronize(st));
     L3D_HIP_CHECK(hipMemcpy(&n_coll, c->d_scal.p + 9, 4, hipMemcpyDeviceToHost));
     L3D_HIP_CHECK(c->d_coll_idx.reserve(std::max<uint32_t>(n_coll, 1)));
+    c->coll_n_idx = n_coll;
     L3D_HIP_CHECK(launch_collin(1, c->d_views.p, V, max_M, c->d_seg_base.p, c->collinearity_t, nullptr, c->d_coll_off.p,
                                 c->d_coll_idx.p, st));
     // ---- similarities of the child and own candidates ----
-    std::vector<uint32_t> off[2], seg[2];
-    std::vector<float> sim[2];
+    // (kept in the context for l3d_debug_affinity_records: the device buffers of mode 0 are overwritten by mode 1)
+    std::vector<uint32_t>(&off)[2] = c->coll_item_off, (&seg)[2] = c->coll_item_seg;
+    std::vector<float>(&sim)[2] = c->coll_item_sim;
     const uint32_t n_items[2] = {N, H};
     for (int mode = 0; mode < 2; ++mode) {
         const uint32_t n = n_items[mode];
@@ -132,6 +134,8 @@ static int affinity_prepare(l3d_ctx* c) {
     const uint32_t V = (uint32_t)c->order.size();
     c->edges.clear(); c->l2g.clear();
     c->aff_n_edges = 0; c->aff_n_rows = 0; c->aff_host_valid = true;
+    c->aff_rec_mode = -1; c->aff_rec_diffused = false; c->coll_n_idx = 0;
+    for (int mode = 0; mode < 2; ++mode) { c->coll_item_off[mode].clear(); c->coll_item_seg[mode].clear(); c->coll_item_sim[mode].clear(); }
     // med_scene_depth_lines_, line3D.cc:1759-1774
     std::vector<float> sd;
     for (auto* v : c->order) if (v->median_depth > kEps) sd.push_back(v->median_depth);
@@ -176,7 +180,7 @@ static int affinity_rest(l3d_ctx* c) {
             if (c->ev_on(7)) L3D_HIP_CHECK(hipEventRecord(c->ev[7], st));
             L3D_HIP_CHECK(hipStreamSynchronize(st));
             c->tm.affinity_ms = ev_ms(c, 6, 7);
-            c->affinity_done = true;
+            c->affinity_done = true; c->aff_rec_mode = 1;
             return L3D_OK;
         }
         L3D_HIP_CHECK(c->d_touch_flag.reserve(2 * (size_t)N + 1));
@@ -206,7 +210,7 @@ static int affinity_rest(l3d_ctx* c) {
     L3D_HIP_CHECK(hipStreamSynchronize(st));
     if (counts_pending) { c->aff_n_edges = 2 * c->h_cnt.p[12]; c->aff_n_rows = c->h_cnt.p[13]; c->aff_host_valid = false; }
     c->tm.affinity_ms = ev_ms(c, 6, 7);
-    c->affinity_done = true;
+    c->affinity_done = true; c->aff_rec_mode = 0;
     return L3D_OK;
 }
 
@@ -274,7 +278,7 @@ int l3d_affinity_shard_begin(l3d_ctx* c, uint32_t rank, uint32_t world, void** s
     if (rc != L3D_OK) return rc;
     *simv = c->d_simv.p;
     for (uint32_t r = 0; r < world; ++r) { first[r] = c->tail_base_n[r]; count[r] = c->tail_base_n[r + 1] - c->tail_base_n[r]; }
-    c->aff_shard_open = true;
+    c->aff_shard_open = true; c->aff_rec_mode = 2;
     frame.keep();   // the views stay translated until l3d_affinity_shard_finish / _abort (or the next l3d_match_begin)
     return L3D_OK;
 }
@@ -286,7 +290,9 @@ int l3d_affinity_shard_finish(l3d_ctx* c) {
         return fail(L3D_ERR_STATE, "l3d_affinity_shard_finish follows l3d_affinity_shard_begin and the exchange of the similarities");
     const Translated frame(*c, true);   // translated by l3d_affinity_shard_begin
     c->aff_shard_open = false;
-    return affinity_rest(c);
+    const int rc = affinity_rest(c);
+    if (rc != L3D_OK) c->aff_rec_mode = -1;   // the fill is closed and not finished: nothing for l3d_debug_affinity_records
+    return rc;
 }
 
 // closes an open sharded fill WITHOUT the bookkeeping pass (a rank whose peer failed: the other ranks' similarities never
@@ -296,8 +302,77 @@ int l3d_affinity_shard_abort(l3d_ctx* c) {
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     if (!c->aff_shard_open) return L3D_OK;
     const Translated frame(*c, true);   // translated by l3d_affinity_shard_begin
-    c->aff_shard_open = false;
+    c->aff_shard_open = false; c->aff_rec_mode = -1;
     (void)hipStreamSynchronize(c->stream);
+    return L3D_OK;
+}
+
+// Test hook (include/l3dpp_hip.h): what every stage of the affinity fill left behind, copied out as it lies -- stream
+// synchronisation and device-to-host copies only: no kernel, nothing written on the device.
+int l3d_debug_affinity_records(l3d_ctx* c, int query_only, l3d_affinity_records* out) {
+    if (!c || !out) return fail(L3D_ERR_ARG, "null argument");
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    if (c->state != l3d_ctx::MATCHED || c->aff_rec_mode < 0)
+        return fail(L3D_ERR_STATE, "l3d_debug_affinity_records: no affinity step has run on the current matches");
+    const uint32_t V = (uint32_t)c->order.size(), G = c->G, N = c->n_surv, H = c->n_hyps;
+    const int mode = c->aff_rec_mode;
+    const bool ran = N > 0 && H > 0;            // affinity_prepare / _sim / _rest do nothing otherwise
+    const uint32_t n = ran ? N : 0;
+    out->N = N; out->H = H; out->G = G; out->V = V;
+    out->n_cand = n; out->mode = (uint32_t)mode; out->diffused = c->aff_rec_diffused ? 1u : 0u;
+    out->n_edges = mode == 2 ? 0 : c->aff_n_edges; out->n_rows = mode == 2 ? 0 : c->aff_n_rows;
+    out->n_coll = mode == 1 ? c->coll_n_idx : 0;
+    out->n_child = mode == 1 ? (uint32_t)c->coll_item_seg[0].size() : 0;
+    out->n_own = mode == 1 ? (uint32_t)c->coll_item_seg[1].size() : 0;
+    out->epos_total = 0; out->touch_total = 0;
+    out->two_sigA_sqr = c->two_sigA_sqr; out->med_scene_depth_lines = c->med_scene_depth_lines;
+    if (query_only) return L3D_OK;
+    (void)hipSetDevice(c->device);
+    L3D_HIP_CHECK(hipStreamSynchronize(c->stream));
+    auto fetch = [](void* dst, const void* src, size_t bytes) -> hipError_t {
+        return dst && bytes ? hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) : hipSuccess;
+    };
+    auto host = [](void* dst, const void* src, size_t bytes) { if (dst && bytes) std::memcpy(dst, src, bytes); };
+    // the inputs (phase B's tail wrote them; the fill only reads them)
+    L3D_HIP_CHECK(fetch(out->hyps, c->d_hyps.p, (size_t)H * sizeof(HypRec)));
+    L3D_HIP_CHECK(fetch(out->surv_off, c->d_surv_off.p, ((size_t)G + 1) * 4));
+    L3D_HIP_CHECK(fetch(out->surv_sg, c->d_surv_sg.p, (size_t)N * 4));
+    L3D_HIP_CHECK(fetch(out->surv_tg, c->d_surv_tg.p, (size_t)N * 4));
+    L3D_HIP_CHECK(fetch(out->hyp_of_seg, c->d_hyp_of_seg.p, (size_t)G * 4));
+    L3D_HIP_CHECK(fetch(out->medians, c->d_med + 8, (size_t)V * 4));
+    if (!ran) return L3D_OK;
+    if (out->view_k || out->msdl_dev) {
+        std::vector<ViewAff> va((size_t)V + 1);
+        L3D_HIP_CHECK(fetch(va.data(), c->d_vaff.p, va.size() * sizeof(ViewAff)));
+        if (out->view_k) for (uint32_t vi = 0; vi < V; ++vi) out->view_k[vi] = va[vi].k;
+        if (out->msdl_dev) *out->msdl_dev = va[V].k;
+    }
+    L3D_HIP_CHECK(fetch(out->simv, c->d_simv.p, (size_t)n * 4));
+    L3D_HIP_CHECK(fetch(out->cand_a, c->d_ca.p, (size_t)n * 4));
+    L3D_HIP_CHECK(fetch(out->cand_b, c->d_cb.p, (size_t)n * 4));
+    if (mode == 0) {
+        uint32_t totals[2] = {0, 0};
+        L3D_HIP_CHECK(fetch(totals, c->d_scal.p + 3, 8));
+        out->epos_total = totals[0]; out->touch_total = totals[1];
+        L3D_HIP_CHECK(fetch(out->flag, c->d_flag.p, (size_t)n * 4));
+        L3D_HIP_CHECK(fetch(out->epos, c->d_epos.p, (size_t)n * 4));
+        L3D_HIP_CHECK(fetch(out->first_touch, c->d_first_touch.p, (size_t)H * 4));
+        L3D_HIP_CHECK(fetch(out->touch_flag, c->d_touch_flag.p, (2 * (size_t)n + 1) * 4));
+        L3D_HIP_CHECK(fetch(out->touch_rank, c->d_touch_rank.p, 2 * (size_t)n * 4));
+        if (!c->aff_rec_diffused) L3D_HIP_CHECK(fetch(out->edges, c->d_edges.p, (size_t)c->aff_n_edges * sizeof(l3d_cledge)));
+        L3D_HIP_CHECK(fetch(out->l2g, c->d_l2g.p, (size_t)c->aff_n_rows * sizeof(l3d_segment2d)));
+    } else if (mode == 1) {
+        L3D_HIP_CHECK(fetch(out->coll_off, c->d_coll_off.p, ((size_t)G + 1) * 4));
+        L3D_HIP_CHECK(fetch(out->coll_idx, c->d_coll_idx.p, (size_t)c->coll_n_idx * 4));
+        host(out->child_off, c->coll_item_off[0].data(), c->coll_item_off[0].size() * 4);
+        host(out->child_seg, c->coll_item_seg[0].data(), c->coll_item_seg[0].size() * 4);
+        host(out->child_sim, c->coll_item_sim[0].data(), c->coll_item_sim[0].size() * 4);
+        host(out->own_off, c->coll_item_off[1].data(), c->coll_item_off[1].size() * 4);
+        host(out->own_seg, c->coll_item_seg[1].data(), c->coll_item_seg[1].size() * 4);
+        host(out->own_sim, c->coll_item_sim[1].data(), c->coll_item_sim[1].size() * 4);
+        if (!c->aff_rec_diffused) L3D_HIP_CHECK(fetch(out->edges, c->d_edges.p, (size_t)c->aff_n_edges * sizeof(l3d_cledge)));
+        host(out->l2g, c->l2g.data(), c->l2g.size() * sizeof(l3d_segment2d));
+    }
     return L3D_OK;
 }
 
@@ -329,6 +404,7 @@ int l3d_reconstruct_3d_lines(l3d_ctx* c, uint32_t visibility_t, int perform_diff
         if (e == hipSuccess) e = out.reserve(nnz);
         if (e == hipSuccess) e = launch_rdd(c->d_edges.p, nnz, n_rows, 10 /* L3D_DEF_RDD_MAX_ITER */, out.p, ws.p, wb, c->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(c->d_edges.p, out.p, (size_t)nnz * sizeof(l3d_cledge), hipMemcpyDeviceToDevice, c->stream);
+        c->aff_rec_diffused = true;
         c->edges.resize(nnz);
         if (e == hipSuccess) e = hipMemcpyAsync(c->edges.data(), out.p, (size_t)nnz * sizeof(l3d_cledge), hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);

@@ -478,7 +478,7 @@ static int add_view(l3d_ctx* c, uint32_t camID, const float* segs4, uint32_t M, 
     c->order.clear();
     for (auto& kv : c->views) { kv.second->index = (uint32_t)c->order.size(); c->order.push_back(kv.second.get()); }
     c->state = l3d_ctx::IDLE;
-    c->affinity_done = false;
+    c->affinity_done = false; c->aff_rec_mode = -1;
     return L3D_OK;
 }
 
@@ -522,7 +522,7 @@ int l3d_match_begin(l3d_ctx* c, const l3d_match_params* p) {
     c->const_regularization_depth = p->const_regularization_depth;
     if (c->sigma_p < 0.0f) { c->fixed3Dregularizer = true; c->sigma_p = std::fabs(c->sigma_p); }
     else { c->fixed3Dregularizer = false; c->sigma_p = std::fmax(0.1f, c->sigma_p); }
-    c->affinity_done = false;
+    c->affinity_done = false; c->aff_rec_mode = -1;
     c->lines_done = false;
     c->lines_merged = false;
     c->n_hyps = 0;

@@ -302,6 +302,14 @@ struct l3d_ctx {
     DevBuf<uint32_t> d_flag, d_epos, d_first_touch, d_touch_flag, d_touch_rank;
     DevBuf<l3d_cledge> d_edges;
     DevBuf<l3d_segment2d> d_l2g;
+    // what l3d_debug_affinity_records may hand out: -1 nothing (no affinity step on the current matches), 0 the parallel
+    // path's buffers, 1 the collinear path's, 2 the similarities only (between l3d_affinity_shard_begin and _finish)
+    int aff_rec_mode = -1;
+    bool aff_rec_diffused = false;                  // d_edges holds the diffused matrix (l3d_reconstruct_3d_lines)
+    // candidate streams of the collinear path (0: children of a passing primary, 1: own links), kept for that hook
+    std::vector<uint32_t> coll_item_off[2], coll_item_seg[2];
+    std::vector<float> coll_item_sim[2];
+    uint32_t coll_n_idx = 0;                        // entries of d_coll_idx
     std::vector<l3d_cledge> edges;
     std::vector<l3d_segment2d> l2g;
     std::vector<ReconLine> lines3D;                 // lines3D_ (original frame)

@@ -307,3 +307,77 @@ def sharded_list_pass(sc, world, **match_kw):
             return ctxs
         assert rcs[0] == -10, rcs               # L3D_ERR_RETRY: pools enlarged on every rank alike, repeat the step
     raise AssertionError("the pools never became large enough")
+
+
+def sharded_tail(sc, world, **match_kw):
+    """matchImages sharded over `world` contexts on one GPU up to l3d_tail_shard_commit, without a process group (the
+    sequence of tests/test_gpu_parity.py's sharded-tail emulation): pairs matched by the planned halo shards, slot indices
+    copied where the exchange would put them, the list pass and the tail per rank's views, the tail's parts copied, commit.
+    Returns (contexts, [(surviving matches, best hypotheses) per rank]); l3d_affinity_shard_begin may follow."""
+    import torch
+    from line3dpp_amd import dist
+    from line3dpp_amd.api import Line3D
+    dev = torch.device("cuda", 0)
+    ctxs = []
+    for _ in range(world):
+        g = Line3D()
+        g.add_scene(sc)
+        assert g.matchBegin(**match_kw)
+        ctxs.append(g)
+    pairs, slot_off = ctxs[0].pairs()
+    plan = dist.plan_halo(pairs, ctxs[0]._M, world)
+    vb, pb, runs, needs = plan["view_bounds"], plan["pair_bounds"], plan["runs"], plan["needs"]
+    bufs = []
+    for r, g in enumerate(ctxs):
+        assert g.shardOptions(min(needs[r] + [r]), False)
+        assert g.matchPairs(int(pb[r]), int(pb[r + 1] - pb[r]))
+        for _, f, n in runs[r]:
+            assert g.packSlotIndices(f, n)
+        ptr, n_slots = g.slot_index_buffer()
+        bufs.append(dist.device_tensor(ptr, n_slots * 4, dev))
+    off = [int(o) for o in slot_off] + [int(n_slots)]
+    for r in range(world):
+        for q, f, n in runs[r]:
+            bufs[q][4 * off[f]:4 * off[f + n]].copy_(bufs[r][4 * off[f]:4 * off[f + n]])
+    torch.cuda.synchronize()
+    for q, g in enumerate(ctxs):
+        for r in range(world):
+            for qq, f, n in runs[r]:
+                if qq == q:
+                    assert g.expandSlotIndices(f, n)
+    for attempt in range(8):
+        slabs = []
+        for r, g in enumerate(ctxs):
+            sl = g.listsShardViews(r, world, int(vb[r]), int(vb[r + 1]))
+            assert sl is not None and len(sl) == 4
+            slabs.append(sl)
+        for k in range(4):
+            sb = slabs[0][k][1]
+            fulls = [dist.device_tensor(sl[k][2], sb * world, dev) for sl in slabs]
+            for r in range(world):
+                for q in range(world):
+                    if q != r and (k == 3 or r in needs[q]):      # records: only to the ranks whose chain walks them
+                        fulls[q][r * sb:(r + 1) * sb].copy_(fulls[r][r * sb:(r + 1) * sb])
+        torch.cuda.synchronize()
+        res = [g.tailShardCount() for g in ctxs]
+        assert len({rc for rc, _, _ in res}) == 1, "every rank takes the same decision (all of them see all pool counters)"
+        if res[0][0] == 0:
+            break
+        assert res[0][0] == -10, res                 # L3D_ERR_RETRY: pools enlarged on every rank alike
+    else:
+        raise AssertionError("the pools never became large enough")
+    counts = [(n, h) for _, n, h in res]
+    layouts = [g.tailShardLayout(world, counts, [int(v) for v in vb]) for g in ctxs]
+    assert all(l is not None and len(l) == 9 for l in layouts)
+    for k in range(9):
+        elt, parts = layouts[0][k][1], layouts[0][k][2]
+        assert all(l[k][1] == elt and l[k][2] == parts for l in layouts), "every rank derives the same layout"
+        total = max(f + n for f, n in parts) * elt
+        fulls = [dist.device_tensor(l[k][0], total, dev) for l in layouts]
+        for r, (f, n) in enumerate(parts):
+            for q in range(world):
+                if q != r and n:
+                    fulls[q][f * elt:(f + n) * elt].copy_(fulls[r][f * elt:(f + n) * elt])
+    torch.cuda.synchronize()
+    assert [g.tailShardCommit() for g in ctxs] == [0] * world
+    return ctxs, counts

@@ -55,3 +55,18 @@ def test_prefilter_without_reciprocals_never_rejects_an_accepted_pair(tmp_path):
     out = subprocess.run([exe], capture_output=True, text=True)
     assert out.returncode == 0, out.stdout
     assert "covered" in out.stdout and " 0 lost" in out.stdout
+
+
+def test_affinity_similarity_form_and_symmetry(tmp_path):
+    """l3d_dev.h: sim_affinity (k_affinity.hip takes ONE exponential, of the minimum of the five arguments) against the
+    literal form of Line3D::similarity (line3D.cc:1467-1553: five exponentials, then the fmin chain), bit for bit, and
+    sim(h1, h2) == sim(h2, h1) bit for bit, on 3.2 million random and forced hypotheses: lengths below L3D_EPS, float dot
+    products above 1 (the clamp), exactly 90 degrees, depths at the cutoff, med_scene_depth_lines at 0 and around L3D_EPS,
+    regularisers of 0 (NaN at distance 0, -inf beyond), all four position terms NaN."""
+    exe = str(tmp_path / "sim_affinity")
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-I/opt/rocm/include", "-D__HIP_PLATFORM_AMD__",
+                           os.path.join(ROOT, "tests", "cpp", "sim_affinity.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0, out.stdout
+    assert "identical, 0 mismatches" in out.stdout and "symmetric, 0 asymmetric" in out.stdout
+    assert "an arm was not reached" not in out.stdout
