@@ -32,17 +32,11 @@ __global__ __launch_bounds__(kCmpTile) void k_compare(CmpArgs a) {
     unsigned long long best_bits = ~0ull;
     uint32_t best_r = 0xFFFFFFFFu, n_acc = 0;
     double best_frac = 0.0;
-    // the references of this slice: chunks [slice * slice_chunks, + slice_chunks), cut at n_r (never empty: the host
-    // derives n_slices from slice_chunks)
-    const unsigned long long ref0 = (unsigned long long)slice * a.slice_chunks * kCmpChunk;
-    const unsigned long long ref_end = ref0 + (unsigned long long)a.slice_chunks * kCmpChunk;
-    const uint32_t r_begin = (uint32_t)(ref0 < a.n_r ? ref0 : a.n_r), r_end = (uint32_t)(ref_end < a.n_r ? ref_end : a.n_r);
+    uint32_t r_begin, r_end;
+    cmp_slice_range(a.n_r, slice, a.slice_chunks, r_begin, r_end);
     for (uint32_t r0 = r_begin; r0 < r_end; r0 += kCmpChunk) {
         const uint32_t n = min(kCmpChunk, r_end - r0);
-        __syncthreads();                                                         // the previous chunk has been read
-        for (uint32_t i = threadIdx.x; i < 6 * n; i += kCmpTile) s_p[i] = a.r[6 * (size_t)r0 + i];
-        if (threadIdx.x < n) s_line[threadIdx.x] = a.r_line[r0 + threadIdx.x];
-        __syncthreads();
+        cmp_stage_chunk(s_p, s_line, a.r, a.r_line, r0, n);
         for (uint32_t k = 0; k < n; ++k) {
             // steps 1-6: l3d_kernels.h
             cmp_pair(me, s_p + 6 * k, s_line[k], a.exclude_same_line != 0, a.max_d2, a.min_cos2, a.min_overlap, [&](double D2, double frac) {

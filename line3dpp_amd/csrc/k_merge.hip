@@ -18,15 +18,6 @@
 namespace l3d {
 namespace {
 
-// the references of a slice: chunks [slice * slice_chunks, + slice_chunks), cut at n (never empty: the host derives
-// n_slices from slice_chunks)
-__device__ __forceinline__ void slice_range(const MrgArgs& a, uint32_t slice, uint32_t& r_begin, uint32_t& r_end) {
-    const unsigned long long ref0 = (unsigned long long)slice * a.slice_chunks * kCmpChunk;
-    const unsigned long long ref1 = ref0 + (unsigned long long)a.slice_chunks * kCmpChunk;
-    r_begin = (uint32_t)(ref0 < a.n ? ref0 : a.n);
-    r_end = (uint32_t)(ref1 < a.n ? ref1 : a.n);
-}
-
 // WRITE = false: count; WRITE = true: the same walk, writing from the scanned offset on
 template <bool WRITE>
 __device__ __forceinline__ void merge_walk(const MrgArgs& a) {
@@ -44,13 +35,10 @@ __device__ __forceinline__ void merge_walk(const MrgArgs& a) {
     const CmpQuery me = cmp_query(a.segs + 6 * (size_t)(in_range ? q : 0), in_range ? a.line[q] : 0u, in_range);
     uint32_t n_acc = 0;
     uint32_t r_begin, r_end;
-    slice_range(a, slice, r_begin, r_end);
+    cmp_slice_range(a.n, slice, a.slice_chunks, r_begin, r_end);
     for (uint32_t r0 = r_begin; r0 < r_end; r0 += kCmpChunk) {
         const uint32_t n = min(kCmpChunk, r_end - r0);
-        __syncthreads();                                                         // the previous chunk has been read
-        for (uint32_t i = threadIdx.x; i < 6 * n; i += kCmpTile) s_p[i] = a.segs[6 * (size_t)r0 + i];
-        if (threadIdx.x < n) s_line[threadIdx.x] = a.line[r0 + threadIdx.x];
-        __syncthreads();
+        cmp_stage_chunk(s_p, s_line, a.segs, a.line, r0, n);
         for (uint32_t k = 0; k < n; ++k) {
             cmp_pair(me, s_p + 6 * k, s_line[k], true, a.max_d2, a.min_cos2, a.min_overlap, [&](double, double) {
                 if (WRITE) {

@@ -26,26 +26,18 @@ static_assert(sizeof(AssocOut) == sizeof(l3d_association) && sizeof(AssocOut) ==
 static_assert(sizeof(ProjRecord) == sizeof(l3d_projected_segment), "record layout");
 static_assert(kAssocSegmentMask == L3D_PROJ_SEGMENT_MASK, "segment mask");
 
-size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 int check_params(const l3d_associate_params* p) {
     if (!p) return fail(L3D_ERR_ARG, "null argument");
-    if (!(p->max_distance >= 0.0) || !std::isfinite(p->max_distance)) return fail(L3D_ERR_ARG, "max_distance must be finite and not negative");
-    if (!(p->min_cos2 >= 0.0 && p->min_cos2 <= 1.0)) return fail(L3D_ERR_ARG, "min_cos2 must lie in [0, 1]");
-    if (!(p->min_overlap >= 0.0 && p->min_overlap <= 1.0)) return fail(L3D_ERR_ARG, "min_overlap must lie in [0, 1]");
-    return L3D_OK;
+    return check_thresholds(p->max_distance, p->min_cos2, p->min_overlap);
 }
 
 // Arguments already checked.  n_rec[c] records of camera c in rec, camera after camera; seg[c] = its n_seg[c] segments;
-// out: one association per segment, camera after camera.  kernel_ms (may be null): events around every launch, summed.
+// out: one association per segment, camera after camera.  kernel_ms (may be null): the time of every launch, summed.
 int associate_core(ProjWork& w, hipStream_t st, uint32_t n_cams, const uint32_t* n_rec, const l3d_projected_segment* rec,
                    const uint32_t* n_seg, const float* const* seg, const l3d_associate_params& p, l3d_association* out,
                    float* kernel_ms) {
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    if (kernel_ms) {
-        *kernel_ms = 0.0f;
-        if (hipEventCreate(&ev[0]) != hipSuccess || hipEventCreate(&ev[1]) != hipSuccess) return fail(L3D_ERR_HIP, "association: no event");
-    }
+    KernelTimer timer(kernel_ms);
+    if (!timer.ok()) return fail(L3D_ERR_HIP, "association: no event");
     int rc = L3D_OK;
     uint64_t rec_at = 0, seg_at = 0;
     std::vector<AssocCam> cams;
@@ -66,8 +58,9 @@ int associate_core(ProjWork& w, hipStream_t st, uint32_t n_cams, const uint32_t*
         const uint32_t g = c1 - c0;
         if (g_seg) {
             const size_t b_cam = sizeof(AssocCam) * g, b_rec = 32 * (size_t)g_rec, b_seg = 16 * (size_t)g_seg, b_out = 24 * (size_t)g_seg;
-            const size_t o_cam = 0, o_rec = up256(o_cam + b_cam), o_seg = up256(o_rec + b_rec), in_bytes = o_seg + b_seg;
-            const size_t o_out = up256(in_bytes), total = o_out + b_out;
+            Layout lay;
+            const size_t o_cam = lay.take(b_cam), o_rec = lay.take(b_rec), o_seg = lay.take(b_seg), in_bytes = lay.at;
+            const size_t o_out = lay.take(b_out), total = lay.at;
             if (w.h.reserve(total) != hipSuccess || w.d.reserve(total) != hipSuccess) { rc = fail(L3D_ERR_HIP, "association: allocation failed"); break; }
             char* h = w.h.p; char* d = w.d.p;
             std::memcpy(h + o_cam, cams.data(), b_cam);
@@ -77,14 +70,14 @@ int associate_core(ProjWork& w, hipStream_t st, uint32_t n_cams, const uint32_t*
             AssocArgs a{(const AssocCam*)(d + o_cam), g, (const float4*)(d + o_seg), (const ProjRecord*)(d + o_rec), (AssocOut*)(d + o_out),
                         p.max_distance * p.max_distance, p.min_cos2, p.min_overlap};
             hipError_t e = hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, st);
-            if (e == hipSuccess && kernel_ms) e = hipEventRecord(ev[0], st);
+            if (e == hipSuccess) e = timer.start(st);
             if (e == hipSuccess) e = launch_associate(a, (uint32_t)g_tiles, st);
-            if (e == hipSuccess && kernel_ms) e = hipEventRecord(ev[1], st);
+            if (e == hipSuccess) e = timer.stop(st);
             if (e == hipSuccess) e = hipMemcpyAsync(h + o_out, d + o_out, b_out, hipMemcpyDeviceToHost, st);
             if (e == hipSuccess) e = hipStreamSynchronize(st);
             if (e != hipSuccess) { rc = fail(L3D_ERR_HIP, std::string("association: ") + hipGetErrorString(e)); break; }
             g_assoc_launches.fetch_add(1, std::memory_order_relaxed);
-            if (kernel_ms) *kernel_ms += ev_ms(ev[0], ev[1]);
+            timer.add();
             const AssocOut* res = (const AssocOut*)(h + o_out);
             for (size_t i = 0; i < (size_t)g_seg; ++i) {
                 const AssocOut& r = res[i];
@@ -94,7 +87,6 @@ int associate_core(ProjWork& w, hipStream_t st, uint32_t n_cams, const uint32_t*
         rec_at += g_rec; seg_at += g_seg;
         c0 = c1;
     }
-    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
     return rc;
 }
 
@@ -143,8 +135,7 @@ int l3d_associate_view_segments(l3d_ctx* c, uint32_t n_views, const uint32_t* ca
     if (int rc = check_params(params)) return rc;
     if (!(near_plane > 0.0) || !std::isfinite(near_plane)) return fail(L3D_ERR_ARG, "the near plane must be positive and finite");
     std::lock_guard<std::recursive_mutex> lk(c->mu);
-    if (c->state == l3d_ctx::BEGUN || c->aff_shard_open) return fail(L3D_ERR_STATE, "segments are associated while a split call is open");
-    if (!c->lines_done) return fail(L3D_ERR_STATE, "no 3D lines to associate with: l3d_reconstruct_3d_lines has not run");
+    if (int rc = lines_ready(c, "segments are associated", "associate with")) return rc;
     std::vector<const HostView*> views(n_views);
     std::vector<uint32_t> sorted(camIDs, camIDs + n_views);
     std::sort(sorted.begin(), sorted.end());
@@ -171,12 +162,7 @@ int l3d_associate_view_segments(l3d_ctx* c, uint32_t n_views, const uint32_t* ca
         return L3D_OK;
     }
     std::vector<l3d_camera> cams(n_views);
-    for (uint32_t k = 0; k < n_views; ++k) {
-        const HostView& v = *views[k];
-        std::memcpy(cams[k].K, v.K.m, 72); std::memcpy(cams[k].R, v.R.m, 72);
-        cams[k].t[0] = v.t.x; cams[k].t[1] = v.t.y; cams[k].t[2] = v.t.z;
-        cams[k].width = v.width; cams[k].height = v.height;
-    }
+    for (uint32_t k = 0; k < n_views; ++k) cams[k] = camera_of(*views[k]);
     std::vector<uint32_t> n_rec;
     if (int rc = project_context_lines(c, n_views, cams.data(), near_plane, n_rec)) return rc;
     for (uint32_t k = 0; k < n_views; ++k)

@@ -6,6 +6,7 @@
 //   l3d_output.hip         get3Dlines and the result writers (TXT / OBJ / STL)
 //   l3d_lineopt.hip        line bundling (optimizeClusters) between the clustering and the final 3D segments
 //   l3d_seam.hip           the accelerator-seam entries (cudawrapper.h:54-80) with CPU-path semantics
+//   l3d_model.hip          what the stages on the 3D lines as a flat model share (project, associate, compare, merge)
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -19,6 +20,7 @@
 
 #include "l3d_host.h"
 #include "l3d_lists.h"
+#include "l3d_model.h"
 #include "l3d_recon.h"
 
 struct l3d_ctx;
@@ -136,6 +138,30 @@ struct ProjWork {
 size_t projection_budget(const ProjWork& w);   // l3d_project.hip: the budget in force
 // l3d_project.hip: stage 1 on the context's lines into c->proj_records, camera after camera (the caller holds the mutex)
 int project_context_lines(::l3d_ctx* c, uint32_t n_cams, const l3d_camera* cams, double near_plane, std::vector<uint32_t>& counts);
+
+// ---- l3d_model.hip: what the stages on a flat model of 3D segments share (the sizes: l3d_model.h) ----
+int check_thresholds(double max_distance, double min_cos2, double min_overlap);   // of the three parameter structs
+// A caller's model: fewer than 2^30 segments, arrays set, coordinates within 2^100.  side names it in the messages
+// ("the <side> side ..."); null: "the model ...", "segment i ...".
+int check_model(const char* side, size_t n, const double* segs, const uint32_t* line);
+// lines3D_ of the context, flattened as l3d_get_3d_lines flattens it
+void context_segments(const ::l3d_ctx* c, std::vector<double>& P6, std::vector<uint32_t>& line);
+// the context forms' opening (mutex held): "<busy> while a split call is open" (null: not checked), "no 3D lines to <verb>: ..."
+int lines_ready(const ::l3d_ctx* c, const char* busy, const char* verb);
+l3d_camera camera_of(const HostView& v);
+// Optional kernel timing of a call.  Null `into` (a stateless form, a context below timing level 2): no event, nothing
+// recorded.  Else *into is zeroed, start / stop record around launches and add(), after a synchronise, adds their time.
+struct KernelTimer {
+    explicit KernelTimer(float* into);
+    KernelTimer(const KernelTimer&) = delete; KernelTimer& operator=(const KernelTimer&) = delete;
+    ~KernelTimer();
+    bool ok() const { return !into_ || (ev_[0] && ev_[1]); }   // false: an event could not be created
+    hipError_t start(hipStream_t st) { return into_ ? hipEventRecord(ev_[0], st) : hipSuccess; }
+    hipError_t stop(hipStream_t st) { return into_ ? hipEventRecord(ev_[1], st) : hipSuccess; }
+    void add() { if (into_) *into_ += ev_ms(ev_[0], ev_[1]); }
+private:
+    float* into_; hipEvent_t ev_[2] = {nullptr, nullptr};
+};
 
 }  // namespace l3d
 

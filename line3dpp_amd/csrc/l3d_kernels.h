@@ -360,6 +360,22 @@ __device__ __forceinline__ void cmp_pair(const CmpQuery& q, const double* r6, ui
     if (!(frac >= min_overlap)) return;
     accept(D2, frac);
 }
+// The references of a slice, for k_compare.hip and k_merge.hip alike: chunks [slice * slice_chunks, + slice_chunks) of
+// kCmpChunk, cut at n_refs (never empty: the host derives n_slices from slice_chunks, slice_plan of l3d_model.h).
+__device__ __forceinline__ void cmp_slice_range(uint32_t n_refs, uint32_t slice, uint32_t slice_chunks, uint32_t& r_begin, uint32_t& r_end) {
+    const unsigned long long ref0 = (unsigned long long)slice * slice_chunks * kCmpChunk;
+    const unsigned long long ref1 = ref0 + (unsigned long long)slice_chunks * kCmpChunk;
+    r_begin = (uint32_t)(ref0 < n_refs ? ref0 : n_refs);
+    r_end = (uint32_t)(ref1 < n_refs ? ref1 : n_refs);
+}
+// The n <= kCmpChunk references from r0 on staged into LDS, coalesced, by the whole workgroup: every lane calls it, the
+// lanes beyond the last query too.
+__device__ __forceinline__ void cmp_stage_chunk(double* s_p, uint32_t* s_line, const double* refs, const uint32_t* ref_line, uint32_t r0, uint32_t n) {
+    __syncthreads();                                                             // the previous chunk has been read
+    for (uint32_t i = threadIdx.x; i < 6 * n; i += kCmpTile) s_p[i] = refs[6 * (size_t)r0 + i];
+    if (threadIdx.x < n) s_line[threadIdx.x] = ref_line[r0 + threadIdx.x];
+    __syncthreads();
+}
 hipError_t launch_compare(const CmpArgs& a, hipStream_t st);         // tiles x slices; writes out (one slice) or part
 hipError_t launch_compare_merge(const CmpArgs& a, hipStream_t st);   // part -> out
 // l3d_compare.hip, test hooks read through l3d_debug_counter

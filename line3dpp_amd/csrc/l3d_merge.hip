@@ -20,83 +20,51 @@ using namespace l3d;
 
 namespace {
 
-constexpr uint32_t kMrgMaxSegments = 1u << 30;
 constexpr uint64_t kMrgMaxPairs = 1ull << 28;
 constexpr uint32_t kMrgNoWrap = 1u << 16;                 // up to here n (n - 1) pairs fit the 32-bit scan
 constexpr size_t kMrgCountBudget = (size_t)256 << 20;     // the counts stay within this
-constexpr double kMrgMaxCoord = 0x1p100;
 static_assert(sizeof(l3d_merge_params) == 32 && sizeof(l3d_merge_line_info) == 16 && sizeof(l3d_merge_summary) == 80, "merge structs");
 static_assert(sizeof(MrgPair) == 8, "pair layout");
 
-size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 int check_params(const l3d_merge_params* p) {
     if (!p) return fail(L3D_ERR_ARG, "null argument");
-    if (!(p->max_distance >= 0.0) || !std::isfinite(p->max_distance)) return fail(L3D_ERR_ARG, "max_distance must be finite and not negative");
-    if (!(p->min_cos2 >= 0.0 && p->min_cos2 <= 1.0)) return fail(L3D_ERR_ARG, "min_cos2 must lie in [0, 1]");
-    if (!(p->min_overlap >= 0.0 && p->min_overlap <= 1.0)) return fail(L3D_ERR_ARG, "min_overlap must lie in [0, 1]");
+    if (int rc = check_thresholds(p->max_distance, p->min_cos2, p->min_overlap)) return rc;
     if (p->reserved != 0) return fail(L3D_ERR_ARG, "reserved must be 0");
     return L3D_OK;
 }
 
-int check_model(uint32_t n, const double* segs, const uint32_t* line) {
-    if (n >= kMrgMaxSegments) return fail(L3D_ERR_LIMIT, "the model has 2^30 or more segments");
-    if (n && (!segs || !line)) return fail(L3D_ERR_ARG, "null argument");
-    for (size_t i = 0; i < 6 * (size_t)n; ++i)
-        if (!(std::fabs(segs[i]) <= kMrgMaxCoord))     // (NaN and the infinities fail it too)
-            return fail(L3D_ERR_ARG, "segment " + std::to_string(i / 6) + " has a coordinate that is not finite or beyond 2^100");
-    return L3D_OK;
-}
-
-// §18's rule: one chunk per slice unless asked otherwise, the counts capped at kMrgCountBudget
-void slicing(uint32_t n, uint32_t asked_chunks, uint32_t& n_slices, uint32_t& slice_chunks) {
-    const uint32_t n_chunks = (n + kCmpChunk - 1) / kCmpChunk;
-    const uint32_t cap = (uint32_t)std::max<size_t>(1, kMrgCountBudget / (sizeof(uint32_t) * (size_t)n));
-    slice_chunks = asked_chunks ? std::min(asked_chunks, n_chunks) : 1;
-    n_slices = (n_chunks + slice_chunks - 1) / slice_chunks;
-    if (n_slices <= cap) return;
-    n_slices = cap;
-    slice_chunks = (n_chunks + n_slices - 1) / n_slices;
-    n_slices = (n_chunks + slice_chunks - 1) / slice_chunks;       // no slice is empty
-}
-
-// ---- stage 1: the accepted pairs, ascending (q, r).  n > 0, arguments checked.  kernel_ms (may be null): events around
-// the count pass with its scan, and around the write pass, summed.
+// ---- stage 1: the accepted pairs, ascending (q, r).  n > 0, arguments checked.  kernel_ms (may be null): the time of
+// the count pass with its scan, and of the write pass, summed.  Slices by §18's rule, the counts within kMrgCountBudget.
 int merge_pairs(ProjWork& w, hipStream_t st, uint32_t n, const double* segs, const uint32_t* line, const l3d_merge_params& p,
                 std::vector<MrgPair>& pairs, float* kernel_ms) {
     pairs.clear();
-    uint32_t n_slices = 0, slice_chunks = 0;
-    slicing(n, p.slice_chunks, n_slices, slice_chunks);
+    const SlicePlan plan = slice_plan(n, n, p.slice_chunks, sizeof(uint32_t), kMrgCountBudget);
+    const uint32_t n_slices = plan.n_slices;
     const size_t cells = (size_t)n * n_slices;
     const size_t b_seg = 48 * (size_t)n, b_line = 4 * (size_t)n, b_cnt = 4 * (cells + 2);   // counts, the total, the wrap flag
-    const size_t o_line = up256(b_seg), in_bytes = o_line + b_line, o_cnt = up256(in_bytes), total = o_cnt + b_cnt;
+    Layout lay;
+    const size_t o_seg = lay.take(b_seg), o_line = lay.take(b_line), in_bytes = lay.at, o_cnt = lay.take(b_cnt), total = lay.at;
     if (w.h.reserve(in_bytes) != hipSuccess || w.d.reserve(total) != hipSuccess ||
         w.scan_ws.reserve_zeroed(scan_ws_words(cells, 4), st) != hipSuccess)
         return fail(L3D_ERR_HIP, "merge: allocation failed");
     char* d = w.d.p;
-    std::memcpy(w.h.p, segs, b_seg);
+    std::memcpy(w.h.p + o_seg, segs, b_seg);
     std::memcpy(w.h.p + o_line, line, b_line);
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    if (kernel_ms) {
-        *kernel_ms = 0.0f;
-        if (hipEventCreate(&ev[0]) != hipSuccess || hipEventCreate(&ev[1]) != hipSuccess) {
-            for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-            return fail(L3D_ERR_HIP, "merge: no event");
-        }
-    }
-    MrgArgs a{(const double*)d, (const uint32_t*)(d + o_line), n, slice_chunks, n_slices, p.max_distance * p.max_distance, p.min_cos2,
+    KernelTimer timer(kernel_ms);
+    if (!timer.ok()) return fail(L3D_ERR_HIP, "merge: no event");
+    MrgArgs a{(const double*)(d + o_seg), (const uint32_t*)(d + o_line), n, plan.slice_chunks, n_slices, p.max_distance * p.max_distance, p.min_cos2,
               p.min_overlap, (uint32_t*)(d + o_cnt), nullptr, 0u, (uint32_t*)(d + o_cnt) + cells + 1};
     uint32_t tail[2] = {0, 0};                             // the total and the wrap flag
     hipError_t e = hipMemcpyAsync(d, w.h.p, in_bytes, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemsetAsync(a.wrapped, 0, 4, st);
-    if (e == hipSuccess && kernel_ms) e = hipEventRecord(ev[0], st);
+    if (e == hipSuccess) e = timer.start(st);
     if (e == hipSuccess) e = launch_merge_count(a, st);
     if (e == hipSuccess) e = launch_scan(a.counts, (uint32_t)cells, a.counts, w.scan_ws.p, nullptr, st);
     if (e == hipSuccess && n > kMrgNoWrap) e = launch_merge_check(a, st);
-    if (e == hipSuccess && kernel_ms) e = hipEventRecord(ev[1], st);
+    if (e == hipSuccess) e = timer.stop(st);
     if (e == hipSuccess) e = hipMemcpyAsync(tail, a.counts + cells, 8, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e == hipSuccess && kernel_ms) *kernel_ms += ev_ms(ev[0], ev[1]);
+    if (e == hipSuccess) timer.add();
     int rc = L3D_OK;
     if (e == hipSuccess) {
         g_mrg_count_launches.fetch_add(1, std::memory_order_relaxed);
@@ -105,24 +73,20 @@ int merge_pairs(ProjWork& w, hipStream_t st, uint32_t n, const double* segs, con
     }
     const size_t n_pairs = tail[0];
     if (e == hipSuccess && rc == L3D_OK && n_pairs) {      // (no pair: no write pass)
-        if (w.keys.reserve(n_pairs) != hipSuccess || w.h.reserve(8 * n_pairs) != hipSuccess) {
-            for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x);
-            return fail(L3D_ERR_HIP, "merge: allocation failed");
-        }
+        if (w.keys.reserve(n_pairs) != hipSuccess || w.h.reserve(8 * n_pairs) != hipSuccess) return fail(L3D_ERR_HIP, "merge: allocation failed");
         a.pairs = (MrgPair*)w.keys.p; a.n_pairs = (uint32_t)n_pairs;
-        if (kernel_ms) e = hipEventRecord(ev[0], st);
+        e = timer.start(st);
         if (e == hipSuccess) e = launch_merge_write(a, st);
-        if (e == hipSuccess && kernel_ms) e = hipEventRecord(ev[1], st);
+        if (e == hipSuccess) e = timer.stop(st);
         if (e == hipSuccess) e = hipMemcpyAsync(w.h.p, a.pairs, 8 * n_pairs, hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e == hipSuccess && kernel_ms) *kernel_ms += ev_ms(ev[0], ev[1]);
+        if (e == hipSuccess) timer.add();
         if (e == hipSuccess) {
             g_mrg_write_launches.fetch_add(1, std::memory_order_relaxed);
             const MrgPair* got = (const MrgPair*)w.h.p;
             pairs.assign(got, got + n_pairs);
         }
     }
-    for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x);
     if (e != hipSuccess) return fail(L3D_ERR_HIP, std::string("merge: ") + hipGetErrorString(e));
     if (rc == L3D_OK) g_mrg_pairs.store(n_pairs, std::memory_order_relaxed);
     return rc;
@@ -293,7 +257,7 @@ int l3d_merge_segments(int device, uint32_t n, const double* segs6, const uint32
                        l3d_merge_summary* summary) {
     if (int rc = check_params(params)) return rc;
     if (!out_n_segs || !out_n_lines) return fail(L3D_ERR_ARG, "null argument");
-    if (int rc = check_model(n, segs6, line)) return rc;
+    if (int rc = check_model(nullptr, n, segs6, line)) return rc;
     if (n && (!out_line_map || !out_segs6 || !out_seg_line || !out_line_info)) return fail(L3D_ERR_ARG, "null argument");
     if (out_seg_cap < n) return fail(L3D_ERR_ARG, "out_seg_cap is smaller than the number of segments");
     if (n && out_line_cap < distinct_lines(n, line)) return fail(L3D_ERR_ARG, "out_line_cap is smaller than the number of distinct lines");
@@ -319,17 +283,10 @@ int l3d_merge_lines(l3d_ctx* c, const l3d_merge_params* params, l3d_merge_summar
     if (!c) return fail(L3D_ERR_ARG, "null argument");
     if (int rc = check_params(params)) return rc;
     std::lock_guard<std::recursive_mutex> lk(c->mu);
-    if (c->state == l3d_ctx::BEGUN || c->aff_shard_open) return fail(L3D_ERR_STATE, "lines are merged while a split call is open");
-    if (!c->lines_done) return fail(L3D_ERR_STATE, "no 3D lines to merge: l3d_reconstruct_3d_lines has not run");
-    // lines3D_ of the context, flattened as l3d_get_3d_lines flattens it
+    if (int rc = lines_ready(c, "lines are merged", "merge")) return rc;
     std::vector<double> P6; std::vector<uint32_t> line;
-    for (size_t i = 0; i < c->lines3D.size(); ++i)
-        for (const ReconSeg3D& s : c->lines3D[i].collinear) {
-            const double p[6] = {s.P1.x, s.P1.y, s.P1.z, s.P2.x, s.P2.y, s.P2.z};
-            P6.insert(P6.end(), p, p + 6);
-            line.push_back((uint32_t)i);
-        }
-    if (int rc = check_model((uint32_t)std::min<size_t>(line.size(), 0xFFFFFFFFu), P6.data(), line.data())) return rc;
+    context_segments(c, P6, line);
+    if (int rc = check_model(nullptr, line.size(), P6.data(), line.data())) return rc;
     const uint32_t n = (uint32_t)line.size();
     Merged m;
     if (n) {

@@ -21,21 +21,22 @@ constexpr uint32_t kProjMaxGroup = 4096;       // cameras per group at most (the
 constexpr uint32_t kProjMaxSide = 65535;       // image sides: a camera's pixels are counted in 32 bits
 static_assert(sizeof(ProjRecord) == sizeof(l3d_projected_segment) && sizeof(ProjRecord) == 32, "record layout");
 
-size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-size_t budget_of(const ProjWork& w) { return w.budget ? w.budget : kProjBudget; }
-
 int hip_fail(const char* where, hipError_t e) { return fail(L3D_ERR_HIP, std::string(where) + ": " + hipGetErrorString(e)); }
 
 int check_near(double near_plane) {
     if (!(near_plane > 0.0) || !std::isfinite(near_plane)) return fail(L3D_ERR_ARG, "the near plane must be positive and finite");
     return L3D_OK;
 }
+int check_camera_size(uint32_t c, const l3d_camera& cam) {
+    if (!cam.width || !cam.height) return fail(L3D_ERR_ARG, "camera " + std::to_string(c) + " has a side of zero pixels");
+    if (cam.width > kProjMaxSide || cam.height > kProjMaxSide)
+        return fail(L3D_ERR_LIMIT, "camera " + std::to_string(c) + " has a side of more than 65535 pixels");
+    return L3D_OK;
+}
 int check_cameras(uint32_t n_cams, const l3d_camera* cams) {
     if (n_cams && !cams) return fail(L3D_ERR_ARG, "null argument");
     for (uint32_t c = 0; c < n_cams; ++c) {
-        if (!cams[c].width || !cams[c].height) return fail(L3D_ERR_ARG, "camera " + std::to_string(c) + " has a side of zero pixels");
-        if (cams[c].width > kProjMaxSide || cams[c].height > kProjMaxSide)
-            return fail(L3D_ERR_LIMIT, "camera " + std::to_string(c) + " has a side of more than 65535 pixels");
+        if (int rc = check_camera_size(c, cams[c])) return rc;
         bool finite = true;
         for (int k = 0; k < 9; ++k) finite = finite && std::isfinite(cams[c].K[k]) && std::isfinite(cams[c].R[k]);
         for (int k = 0; k < 3; ++k) finite = finite && std::isfinite(cams[c].t[k]);
@@ -78,16 +79,16 @@ int project_core(ProjWork& w, hipStream_t st, uint32_t n_cams, const l3d_camera*
     for (uint32_t c = 0; c < n_cams; ++c) counts[c] = 0;
     if (!n_cams || !n_seg) return L3D_OK;
     const size_t per_cam = 68 * (size_t)n_seg;
-    const uint32_t g_max = (uint32_t)std::max<size_t>(1, std::min<size_t>(std::min<size_t>(kProjMaxGroup, budget_of(w) / per_cam),
+    const uint32_t g_max = (uint32_t)std::max<size_t>(1, std::min<size_t>(std::min<size_t>(kProjMaxGroup, projection_budget(w) / per_cam),
                                                                            ((size_t)1 << 31) / n_seg));
     for (uint32_t c0 = 0; c0 < n_cams; c0 += g_max) {
         const uint32_t g = std::min(g_max, n_cams - c0);
         const size_t n = (size_t)g * n_seg;
-        const size_t o_cam = 0, o_P = up256(o_cam + sizeof(ProjCam) * g), o_line = up256(o_P + 48 * (size_t)n_seg);
-        const size_t in_bytes = o_line + 4 * (size_t)n_seg;
-        const size_t o_bounds = up256(in_bytes), o_vis = up256(o_bounds + 4 * ((size_t)g + 1)), o_rec = up256(o_vis + 4 * (n + 1));
-        const size_t o_out = up256(o_rec + 32 * n), total = o_out + 32 * n;
-        if (w.h.reserve(up256(in_bytes) + 4 * ((size_t)g + 1)) != hipSuccess || w.d.reserve(total) != hipSuccess ||
+        Layout lay;
+        const size_t o_cam = lay.take(sizeof(ProjCam) * g), o_P = lay.take(48 * (size_t)n_seg), o_line = lay.take(4 * (size_t)n_seg);
+        const size_t in_bytes = lay.at, o_bounds = lay.take(4 * ((size_t)g + 1)), host_bytes = lay.at;
+        const size_t o_vis = lay.take(4 * (n + 1)), o_rec = lay.take(32 * n), o_out = lay.take(32 * n), total = lay.at;
+        if (w.h.reserve(host_bytes) != hipSuccess || w.d.reserve(total) != hipSuccess ||
             w.scan_ws.reserve_zeroed(scan_ws_words(n, 4), st) != hipSuccess)
             return fail(L3D_ERR_HIP, "projection: allocation failed");
         char* h = w.h.p; char* d = w.d.p;
@@ -99,7 +100,7 @@ int project_core(ProjWork& w, hipStream_t st, uint32_t n_cams, const l3d_camera*
         }
         std::memcpy(h + o_P, P6, 48 * (size_t)n_seg);
         std::memcpy(h + o_line, line, 4 * (size_t)n_seg);
-        uint32_t* h_bounds = (uint32_t*)(h + up256(in_bytes));
+        uint32_t* h_bounds = (uint32_t*)(h + o_bounds);
         ProjArgs a{(const ProjCam*)(d + o_cam), g, n_seg, (const double*)(d + o_P), (const uint32_t*)(d + o_line), near_plane,
                    (ProjRecord*)(d + o_rec), (uint32_t*)(d + o_vis), (ProjRecord*)(d + o_out), (uint32_t*)(d + o_bounds)};
         hipError_t e = hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, st);
@@ -135,16 +136,6 @@ int gather_segments(uint32_t n_seg, const l3d_segment3d* segs, const uint32_t* l
     }
     return L3D_OK;
 }
-// lines3D_ of the context, flattened as l3d_get_3d_lines flattens it
-void context_segments(const l3d_ctx* c, std::vector<double>& P6, std::vector<uint32_t>& line) {
-    P6.clear(); line.clear();
-    for (size_t i = 0; i < c->lines3D.size(); ++i)
-        for (const ReconSeg3D& s : c->lines3D[i].collinear) {
-            const double p[6] = {s.P1.x, s.P1.y, s.P1.z, s.P2.x, s.P2.y, s.P2.z};
-            P6.insert(P6.end(), p, p + 6);
-            line.push_back((uint32_t)i);
-        }
-}
 
 // ---- stages 2 and 3 ---------------------------------------------------------------------------------------------------
 struct MapJob {
@@ -166,7 +157,7 @@ int maps_core(ProjWork& w, hipStream_t st, const MapJob& j) {
         std::vector<MapCam> mc;
         while (c1 < j.n_cams && c1 - c0 < kProjMaxGroup) {
             const uint64_t pix = (uint64_t)j.size[c1].first * j.size[c1].second;
-            if (c1 > c0 && (n_pix + pix) * 8 > budget_of(w)) break;
+            if (c1 > c0 && (n_pix + pix) * 8 > projection_budget(w)) break;
             MapCam m{};
             m.width = j.size[c1].first; m.height = j.size[c1].second; m.rec0 = (uint32_t)n_rec; m.pix0 = n_pix; m.rgb_off = 3 * n_pix;
             if (j.images) {
@@ -194,9 +185,10 @@ int maps_core(ProjWork& w, hipStream_t st, const MapJob& j) {
             }
         if (step_bound >= ((uint64_t)1 << 32)) return fail(L3D_ERR_LIMIT, "more than 2^32 raster steps in a group of cameras");
         const size_t b_cam = sizeof(MapCam) * g, b_rec = 32 * (size_t)n_rec, b_col = j.colors ? 3 * (size_t)j.n_lines : 0;
-        const size_t o_cam = 0, o_rec = up256(o_cam + b_cam), o_col = up256(o_rec + b_rec), in_bytes = o_col + b_col;
-        const size_t o_steps = up256(in_bytes), o_ids = up256(o_steps + 4 * ((size_t)n_rec + 1)), o_iz = up256(o_ids + 4 * n_pix);
-        const size_t o_img = up256(o_iz + 4 * n_pix), o_rgb = up256(o_img + img_bytes), total = o_rgb + (j.images ? 3 * n_pix : 0);
+        Layout lay;
+        const size_t o_cam = lay.take(b_cam), o_rec = lay.take(b_rec), o_col = lay.take(b_col), in_bytes = lay.at;
+        const size_t o_steps = lay.take(4 * ((size_t)n_rec + 1)), o_ids = lay.take(4 * n_pix), o_iz = lay.take(4 * n_pix);
+        const size_t o_img = lay.take(img_bytes), o_rgb = lay.take(j.images ? 3 * n_pix : 0), total = lay.at;
         if (w.h.reserve(in_bytes) != hipSuccess || w.d.reserve(total) != hipSuccess ||
             (j.raster && (w.keys.reserve(n_pix) != hipSuccess || w.scan_ws.reserve_zeroed(scan_ws_words(n_rec, 4), st) != hipSuccess)))
             return fail(L3D_ERR_HIP, "line maps: allocation failed");
@@ -267,9 +259,13 @@ std::vector<std::pair<uint32_t, uint32_t>> camera_sizes(uint32_t n_cams, const l
     return s;
 }
 
-// stage 1 on the context's lines: counts (may be NULL) and c->proj_records.  The caller holds the mutex.
-int project_context(l3d_ctx* c, uint32_t n_cams, const l3d_camera* cams, double near_plane, std::vector<uint32_t>& counts) {
-    if (!c->lines_done) return fail(L3D_ERR_STATE, "no 3D lines to project: l3d_reconstruct_3d_lines has not run");
+}  // namespace
+
+// shared with l3d_associate.hip: the budget of a group of cameras, and stage 1 on the context's lines (mutex held)
+namespace l3d {
+size_t projection_budget(const ProjWork& w) { return w.budget ? w.budget : kProjBudget; }
+int project_context_lines(l3d_ctx* c, uint32_t n_cams, const l3d_camera* cams, double near_plane, std::vector<uint32_t>& counts) {
+    if (int rc = lines_ready(c, nullptr, "project")) return rc;
     if (int rc = set_device(c->device)) return rc;
     std::vector<double> P6; std::vector<uint32_t> line;
     context_segments(c, P6, line);
@@ -277,15 +273,6 @@ int project_context(l3d_ctx* c, uint32_t n_cams, const l3d_camera* cams, double 
     counts.assign(n_cams, 0);
     return project_core(c->proj, c->stream, n_cams, cams, (uint32_t)line.size(), P6.data(), line.data(), near_plane, counts.data(),
                         c->proj_records);
-}
-
-}  // namespace
-
-// what l3d_associate.hip shares with the stages above: the budget of a group of cameras, and stage 1 on the context's lines
-namespace l3d {
-size_t projection_budget(const ProjWork& w) { return budget_of(w); }
-int project_context_lines(l3d_ctx* c, uint32_t n_cams, const l3d_camera* cams, double near_plane, std::vector<uint32_t>& counts) {
-    return project_context(c, n_cams, cams, near_plane, counts);
 }
 }  // namespace l3d
 
@@ -319,11 +306,8 @@ int l3d_render_line_maps(int device, uint32_t n_cams, const l3d_camera* cams, co
     if (!cams || !n_records_per_cam) return fail(L3D_ERR_ARG, "null argument");
     if (int rc = check_thickness(thickness)) return rc;
     if (int rc = check_pointers(n_cams, line_id_planes)) return rc;
-    for (uint32_t c = 0; c < n_cams; ++c) {
-        if (!cams[c].width || !cams[c].height) return fail(L3D_ERR_ARG, "camera " + std::to_string(c) + " has a side of zero pixels");
-        if (cams[c].width > kProjMaxSide || cams[c].height > kProjMaxSide)
-            return fail(L3D_ERR_LIMIT, "camera " + std::to_string(c) + " has a side of more than 65535 pixels");
-    }
+    for (uint32_t c = 0; c < n_cams; ++c)            // (the sizes only: K, R and t are not read here)
+        if (int rc = check_camera_size(c, cams[c])) return rc;
     uint64_t n_rec = 0;
     for (uint32_t c = 0; c < n_cams; ++c) n_rec += n_records_per_cam[c];
     if (int rc = check_records(n_rec, records)) return rc;
@@ -357,10 +341,7 @@ int l3d_view_camera(l3d_ctx* c, uint32_t camID, l3d_camera* cam) {
     auto f = c->views.find(camID);
     if (f == c->views.end()) return fail(L3D_ERR_ARG, "unknown camera ID");
     if (c->state == l3d_ctx::BEGUN || c->aff_shard_open) return fail(L3D_ERR_STATE, "the views are translated while a split call is open");
-    const HostView& v = *f->second;
-    std::memcpy(cam->K, v.K.m, 72); std::memcpy(cam->R, v.R.m, 72);
-    cam->t[0] = v.t.x; cam->t[1] = v.t.y; cam->t[2] = v.t.z;
-    cam->width = v.width; cam->height = v.height;
+    *cam = camera_of(*f->second);
     return L3D_OK;
 }
 
@@ -377,7 +358,7 @@ int l3d_project_lines(l3d_ctx* c, uint32_t n_cams, const l3d_camera* cams, doubl
     if (int rc = check_cameras(n_cams, cams)) return rc;
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     std::vector<uint32_t> cnt;
-    if (int rc = project_context(c, n_cams, cams, near_plane, cnt)) return rc;
+    if (int rc = project_context_lines(c, n_cams, cams, near_plane, cnt)) return rc;
     for (uint32_t k = 0; k < n_cams; ++k) counts[k] = cnt[k];
     return L3D_OK;
 }
@@ -399,7 +380,7 @@ int l3d_render_lines(l3d_ctx* c, uint32_t n_cams, const l3d_camera* cams, double
     if (int rc = check_pointers(n_cams, line_id_planes)) return rc;
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     std::vector<uint32_t> cnt;
-    if (int rc = project_context(c, n_cams, cams, near_plane, cnt)) return rc;
+    if (int rc = project_context_lines(c, n_cams, cams, near_plane, cnt)) return rc;
     if (!n_cams) return L3D_OK;
     MapJob j;
     j.n_cams = n_cams; j.size = camera_sizes(n_cams, cams); j.raster = true; j.n_rec = cnt.data(); j.rec = c->proj_records.data();
@@ -419,7 +400,7 @@ int l3d_draw_lines(l3d_ctx* c, uint32_t n_cams, const l3d_camera* cams, const l3
     if (int rc = check_pointers(n_cams, out_rgb)) return rc;
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     std::vector<uint32_t> cnt;
-    if (int rc = project_context(c, n_cams, cams, near_plane, cnt)) return rc;
+    if (int rc = project_context_lines(c, n_cams, cams, near_plane, cnt)) return rc;
     if (!n_cams) return L3D_OK;
     MapJob j;
     j.n_cams = n_cams; j.size = sizes; j.raster = true; j.n_rec = cnt.data(); j.rec = c->proj_records.data(); j.thickness = thickness;
