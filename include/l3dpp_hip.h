@@ -734,6 +734,29 @@ typedef struct l3d_affinity_records {
 } l3d_affinity_records;
 int l3d_debug_affinity_records(l3d_ctx*, int query_only, l3d_affinity_records* out);
 
+/* Test hook: the layout of the RAGGED slot buffer of a keep-all call (kNN <= 0, single pass) as k_keep_pair_info and
+ * k_keep_assemble left it on the device, copied out as it lies -- stream synchronisation and device-to-host copies only: no
+ * kernel, nothing written on the device.  L3D_ERR_STATE unless the context's current matches are ragged (after
+ * l3d_match_pairs of a keep-all call that took the single pass, until the next l3d_match_begin / l3d_match_abort).
+ * Two-call form as above: query_only != 0 fills in the sizes; then the caller points the buffers at host arrays of those
+ * sizes and calls again with query_only == 0.  A buffer may be NULL (that array is not copied). */
+typedef struct l3d_keep_rows {
+    /* out: sizes and the host's state */
+    uint32_t n_rows, n_pairs;         /* source rows of all pairs of the call, pairs */
+    uint32_t n_blocks;                /* blocks of 1 024 slots that hold a slot: ceil(n_slots / 1024) */
+    uint32_t keep_cap;                /* records per row of the scratch, as the context keeps it for its next call */
+    uint32_t tgt16, reserved;         /* the device holds inv_tgt as 16-bit entries (handed out widened) */
+    uint64_t n_slots;                 /* slots of the call = what the context sizes its next call's outputs from */
+    /* in: host buffers */
+    uint32_t* row_start;              /* n_rows + 1: first slot of every row; [n_rows] = n_slots */
+    uint32_t* row_pair;               /* n_rows: pair of a row */
+    uint32_t* blk_row;                /* n_blocks: the row that holds slot 1024 b */
+    uint32_t* pair_info;              /* 4 n_pairs: {first slot, longest row, slots lo, slots hi} */
+    uint32_t* slot_row;               /* n_slots: source segment of a slot (row inside its pair) */
+    uint32_t* inv_tgt;                /* n_slots: target segment of a slot that hands an inverse match over, 0xFFFFFFFF else */
+} l3d_keep_rows;
+int l3d_debug_keep_rows(l3d_ctx*, int query_only, l3d_keep_rows* out);
+
 /* ---- (2) seam layer ------------------------------------------------------------------ */
 
 /* Replaces match_lines_GPU (cudawrapper.h:54-63; caller Line3D::matchingGPU line3D.cc:1040-1074)

@@ -681,6 +681,27 @@ class Line3D:
             out["edges"] = None
         return out
 
+    def keep_rows(self):
+        """l3d_debug_keep_rows (test hook): the layout of a keep-all call's ragged slot buffer as it lies on the device ->
+        dict: the sizes (n_rows, n_pairs, n_blocks, keep_cap, tgt16, n_slots) and the arrays row_start [n_rows + 1], row_pair,
+        blk_row [n_blocks], pair_info [n_pairs, 4] = {first slot, longest row, slots lo, slots hi}, slot_row and inv_tgt
+        [n_slots].  None (and last_status) unless the context's current matches are ragged."""
+        from ._lib import KeepRows
+        t = KeepRows()
+        if not self._check(self.L.l3d_debug_keep_rows(self.h, 1, C.byref(t)), "keep_rows"):
+            return None
+        u32 = np.uint32
+        bufs = dict(row_start=np.zeros(t.n_rows + 1, u32), row_pair=np.zeros(t.n_rows, u32), blk_row=np.zeros(t.n_blocks, u32),
+                    pair_info=np.zeros((t.n_pairs, 4), u32), slot_row=np.zeros(t.n_slots, u32), inv_tgt=np.zeros(t.n_slots, u32))
+        for k, a in bufs.items():
+            setattr(t, k, a.ctypes.data if a.size else None)
+        if not self._check(self.L.l3d_debug_keep_rows(self.h, 0, C.byref(t)), "keep_rows"):
+            return None
+        out = {k: int(getattr(t, k)) for k in KeepRows.SIZES if k != "reserved"}
+        out["n_slots"] = int(t.n_slots)
+        out.update(bufs)
+        return out
+
     def setTimingLevel(self, level):
         """l3d_set_timing_level: 1 = the match kernel only (default), 2 = every phase timed with HIP events (profiling), 0 = none"""
         return self._check(self.L.l3d_set_timing_level(self.h, int(level)), "setTimingLevel")

@@ -81,6 +81,40 @@ int l3d_get_pair_slots(l3d_ctx* c, uint32_t pi, l3d_slot* out, uint64_t cap, uin
     return L3D_OK;
 }
 
+// Test hook (include/l3dpp_hip.h): the layout of a keep-all call's ragged slot buffer as k_keep_pair_info and k_keep_assemble
+// left it, copied out as it lies -- stream synchronisation and device-to-host copies only: no kernel, nothing written on the
+// device.
+int l3d_debug_keep_rows(l3d_ctx* c, int query_only, l3d_keep_rows* out) {
+    if (!c || !out) return fail(L3D_ERR_ARG, "null argument");
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    if (c->state == l3d_ctx::IDLE || !c->ragged || c->pairs.empty() || !c->pair_done[0])
+        return fail(L3D_ERR_STATE, "l3d_debug_keep_rows: the context's current matches are not ragged");
+    const uint32_t R = c->n_rows_total, P = (uint32_t)c->pairs.size();
+    const uint64_t S = c->n_slots;
+    const uint32_t nb = (uint32_t)((S + kKeepBlock - 1) / kKeepBlock);
+    out->n_rows = R; out->n_pairs = P; out->n_blocks = nb; out->keep_cap = c->keep_cap;
+    out->tgt16 = c->tgt16; out->reserved = 0; out->n_slots = S;
+    if (query_only) return L3D_OK;
+    (void)hipSetDevice(c->device);
+    L3D_HIP_CHECK(hipStreamSynchronize(c->stream));
+    auto fetch = [](void* dst, const void* src, size_t bytes) -> hipError_t {
+        return dst && bytes ? hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) : hipSuccess;
+    };
+    L3D_HIP_CHECK(fetch(out->row_start, c->d_row_start.p, ((size_t)R + 1) * 4));
+    L3D_HIP_CHECK(fetch(out->row_pair, c->d_row_pair.p, (size_t)R * 4));
+    L3D_HIP_CHECK(fetch(out->blk_row, c->d_blk_row.p, (size_t)nb * 4));
+    L3D_HIP_CHECK(fetch(out->pair_info, c->d_keep_info.p, (size_t)P * sizeof(uint4)));
+    L3D_HIP_CHECK(fetch(out->slot_row, c->d_slot_row.p, (size_t)S * 4));
+    if (out->inv_tgt && S) {
+        if (c->tgt16) {
+            std::vector<uint16_t> t16(S);
+            L3D_HIP_CHECK(fetch(t16.data(), c->d_inv_tgt.p, (size_t)S * 2));
+            for (uint64_t i = 0; i < S; ++i) out->inv_tgt[i] = t16[i] == 0xFFFFu ? kEmpty : t16[i];
+        } else L3D_HIP_CHECK(fetch(out->inv_tgt, c->d_inv_tgt.p, (size_t)S * 4));
+    }
+    return L3D_OK;
+}
+
 int l3d_num_best(l3d_ctx* c, uint32_t* n) {
     if (!c || !n) return fail(L3D_ERR_ARG, "null argument");
     *n = c->state == l3d_ctx::MATCHED ? c->n_hyps : 0;

@@ -381,3 +381,38 @@ def sharded_tail(sc, world, **match_kw):
     torch.cuda.synchronize()
     assert [g.tailShardCommit() for g in ctxs] == [0] * world
     return ctxs, counts
+
+
+def _assert_slot_liveness(g, present_pairs=None, min_alive=1):
+    """The list pass decides whether a fresh hypothesis is alive from the stream hyp_p (NaN = not alive, k_lists.hip), not
+    from the slot's kSlotAlive flag: every producer of slots (the match epilogue, k_orient_all, k_keep_assemble, the halo
+    expansion) must write both alike.  Over every slot of the present pairs (all of them when present_pairs is None): a slot
+    with a target is alive in hyp_p exactly when its flags say so, and then hyp_p holds its (d_p1, d_p2) bit for bit; a slot
+    without a target is not alive (the uniform-row sweep of the list pass reads it too).  Returns (alive, rejected)."""
+    import torch
+    from line3dpp_amd import dist
+    from line3dpp_amd._lib import SLOT_DTYPE
+    hyp = g.fresh_hyp()                              # (returns when the context's stream is done)
+    assert hyp is not None
+    ptr, n = g.slot_buffer()
+    assert hyp.shape == (n, 2) and n > 0
+    slots = dist.device_tensor(ptr, n * 32, torch.device("cuda", 0)).cpu().numpy().view(SLOT_DTYPE)
+    mask = np.ones(n, bool)
+    if present_pairs is not None:
+        off = [int(o) for o in g.pairs()[1]] + [n]
+        mask[:] = False
+        for p in present_pairs:
+            mask[off[p]:off[p + 1]] = True
+    present = mask & (slots["tgt_seg"] != EMPTY)
+    flag_alive = (slots["flags"] & 1) != 0
+    hyp_alive = ~np.isnan(hyp[:, 0])
+    bad = np.nonzero(present & (flag_alive != hyp_alive))[0]
+    assert not len(bad), f"{len(bad)} present slots whose hyp_p disagrees with kSlotAlive, first {bad[:5]}"
+    bad = np.nonzero(mask & ~present & hyp_alive)[0]
+    assert not len(bad), f"{len(bad)} slots without a target that hyp_p calls alive, first {bad[:5]}"
+    alive = present & flag_alive
+    bits = hyp.view(np.uint32)
+    assert np.array_equal(bits[alive, 0], slots["d_p1"].view(np.uint32)[alive])
+    assert np.array_equal(bits[alive, 1], slots["d_p2"].view(np.uint32)[alive])
+    assert int(alive.sum()) >= min_alive
+    return int(alive.sum()), int((present & ~flag_alive).sum())

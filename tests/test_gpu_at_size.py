@@ -111,13 +111,15 @@ def test_slice_of_c2_c4_at_configured_size(config, count, mid):
 
 
 def test_keep_all_mode_at_c1_size_through_the_culled_walk(monkeypatch):
-    """kNN <= 0 (every accepted match is kept, in ascending target order: line3D.cc:982-992).  Until round 3 this mode
-    streamed every pair unculled in both of its passes; since round 4 the COUNT pass takes the epipolar-band walk (a
-    count does not depend on the order; the fill pass keeps streaming: its arrival order is the reference's order).  Full
-    C1 phase A: 32 sampled directed pairs bit for bit and in the reference's order against matchingCPU of the
-    restatement (pinned byte for byte on the reference's own code), with and without the culled count pass
-    (L3D_KEEPALL_NO_CULL=1) giving the same slots, the culled form faster; then the whole pipeline in this mode against
-    the reference's own code on a quarter-size scene (its scoring is quadratic in the list length)."""
+    """kNN <= 0 (every accepted match is kept, in ascending target order: line3D.cc:982-992).  The default form is ONE pass
+    through the epipolar-band walk that keeps what it accepts, and an assembly that puts every row into ascending target
+    order (ragged rows).  L3D_KEEPALL_NO_CULL=1 selects the older two-pass form with BOTH passes streamed
+    unculled (a count pass, rows padded to the pair's longest, a fill pass whose arrival order is the reference's order).
+    `culled_pairs` counts the pairs whose launch took the culled walk: every pair in the default form, none under the
+    switch.  Full C1 phase A: 32 sampled directed pairs bit for bit and in the reference's order against matchingCPU of the
+    restatement (pinned byte for byte on the reference's own code), the two forms giving the same slots through the padded
+    accessor, the culled single pass faster; then the whole pipeline in this mode against the reference's own code on a
+    quarter-size scene (its scoring is quadratic in the list length)."""
     from line3dpp_amd.api import Line3D
     from line3dpp_amd.scene import make_scene
     sc = make_config("C1")
@@ -138,11 +140,11 @@ def test_keep_all_mode_at_c1_size_through_the_culled_walk(monkeypatch):
             tm = g.timings()
             if rep == 0:
                 assert g.matchAbort()
-        # (GPU time of the two kernels -- count and fill -- and of the culling set-up; match_pairs_ms also spans the host's
-        # sizing of the rows between the two passes)
+        # (GPU time of the call's kernels -- the pass, the scan and the assembly, or count and fill under the switch -- and
+        # of the culling set-up; match_pairs_ms also spans the host's read-back of the pair table or its sizing of the rows)
         out[name] = (g, tm["match_kernel_ms"] + tm["cull_prepare_ms"], tm["culled_pairs"])
     (gc, ms_c, culled), (gu, ms_u, unculled) = out["culled"], out["unculled"]
-    assert culled == n_pairs and unculled == 0            # (the count pass takes the culled walk, the fill pass streams)
+    assert culled == n_pairs and unculled == 0            # (the single pass takes the culled walk; under the switch nothing does)
     rng = np.random.default_rng(5)
     sample = rng.choice(n_pairs, 32, replace=False)
     for pi in sample:
@@ -162,7 +164,7 @@ def test_keep_all_mode_at_c1_size_through_the_culled_walk(monkeypatch):
         total += r["n_cpu"]
     o.end_match()
     assert total > 500_000
-    print(f"keep-all C1 phase A: culled count pass {ms_c:.2f} ms, both passes unculled {ms_u:.2f} ms ({ms_u / ms_c:.2f} x), {total} matches in 32 sampled pairs identical")
+    print(f"keep-all C1 phase A: culled single pass {ms_c:.2f} ms, two passes unculled {ms_u:.2f} ms ({ms_u / ms_c:.2f} x), {total} matches in 32 sampled pairs identical")
     assert ms_u > 1.1 * ms_c, (ms_c, ms_u)
     gc.matchAbort(); gu.matchAbort(); gc.close(); gu.close()
     # the whole pipeline in this mode, against the reference's own code
