@@ -935,7 +935,8 @@ int l3d_associate_view_segments(l3d_ctx*, uint32_t n_views, const uint32_t* camI
  * min_overlap of q lies within r's extent; with exclude_same_line, iff also line(q) != line(r).  Of the accepted
  * references a query gets the one with the smallest distance (the larger of its two end points' distances), of equal
  * distances the one with the smaller index.  fp64, the contract of DESIGN §18.  The caller aligns the models: no
- * similarity transform is estimated. */
+ * similarity transform is estimated here -- l3d_align_segments / l3d_align_lines below estimate one and
+ * deliver the comparison of the aligned models. */
 typedef struct l3d_compare_params {
     double max_distance;         /* model units, finite, >= 0: a 3D model has no natural unit, so there is no default */
     double min_cos2;             /* in [0, 1]: cos^2 of the largest angle between query and reference */
@@ -1036,6 +1037,74 @@ int l3d_merge_segments(int device, uint32_t n, const double* segs6, const uint32
  * of the last l3d_project_lines are dropped.  l3d_output_filename carries MERGED_<max_distance>__ in front of vis_ until
  * the next l3d_reconstruct_3d_lines.  L3D_ERR_STATE without reconstructed lines or while a split call is open. */
 int l3d_merge_lines(l3d_ctx*, const l3d_merge_params* params, l3d_merge_summary* summary);
+
+/* ---- two 3D line models aligned: the similarity transform between them (GPU: k_align.hip) ---------------
+ * No reference counterpart.  Two models as above, Q (moved) and R (fixed), in frames that differ by a similarity
+ * transform y = scale * R(q) x + t.  Iterated closest lines: per iteration Q is transformed, matched against R by the
+ * pair test of l3d_compare_segments (within `gate`, which starts at start_distance, halves per iteration and ends at
+ * max_distance), the 7x7 normal equations of the matched end points' distances from their reference lines are summed on
+ * the device and solved on the host, and the transform is updated about the centre of R's bounding box.  fp64, the
+ * contract of DESIGN §23.  A start within reach is the caller's: NULL means identity. */
+typedef struct l3d_similarity {     /* 64 bytes */
+    double scale;                /* finite, > 0 */
+    double q[4];                 /* rotation as a quaternion (w, x, y, z); q.q finite and > 0, normalised on entry */
+    double t[3];                 /* finite */
+} l3d_similarity;
+typedef struct l3d_align_params {   /* 64 bytes */
+    double max_distance;         /* as in l3d_compare_params: the gate of the last iterations and of the delivered comparison */
+    double min_cos2;
+    double min_overlap;
+    double start_distance;       /* 0: the gate is max_distance throughout; else finite and >= max_distance */
+    double step_tolerance;       /* finite, > 0: converged when the gate is max_distance and the step is at most this */
+    uint32_t max_iterations;     /* 1 .. 256 */
+    uint32_t min_matches;        /* >= 1: fewer matched queries stop the iteration (L3D_ALIGN_TOO_FEW) */
+    uint32_t estimate_scale;     /* 0 or 1; 0: the scale stays the initial one */
+    uint32_t slice_chunks;       /* as in l3d_compare_params: no output depends on it */
+    uint32_t reserved[2];        /* must be 0 */
+} l3d_align_params;
+enum { L3D_ALIGN_CONVERGED = 0, L3D_ALIGN_MAX_ITERATIONS = 1, L3D_ALIGN_TOO_FEW = 2, L3D_ALIGN_DEGENERATE = 3 };
+typedef struct l3d_align_summary {  /* 64 bytes */
+    uint32_t status;             /* L3D_ALIGN_* */
+    uint32_t iterations;         /* iterations run = trace entries written (one that stopped without an update included) */
+    uint64_t n_matched;          /* queries matched at max_distance under the final transform */
+    double rms;                  /* sqrt(cost / (2 n_matched)) of them: the end points' distance from their reference lines */
+    double last_step;            /* the step of the last update (0: none was made) */
+    double diag;                 /* the diagonal of R's bounding box */
+    double center[3];            /* its midpoint, about which the updates rotate and scale */
+} l3d_align_summary;
+/* one iteration (432 bytes).  sums: H (28, the upper triangle row by row), b (7), cost, count. */
+typedef struct l3d_align_iteration {
+    double gate;
+    double sums[37];
+    double delta[7];             /* rotation (3), scale, translation (3); all 0 where the iteration stopped without a solve */
+    l3d_similarity similarity;   /* after the update (unchanged where none was made) */
+    uint64_t n_matched;
+} l3d_align_iteration;
+/* Stateless, host pointers.  Both models are uploaded once; per iteration the transform, the comparison's launches and the
+ * normal kernel run, 37 doubles per tile of 256 queries come down and the host solves.  Then the delivery pass: Q under
+ * the final transform compared with R at max_distance (out_q [n_q]) and, with out_r [n_r], R with it.  initial: NULL =
+ * identity.  out_similarity and summary are required; out_segs6 [n_q x 6] (the transformed Q), out_q, out_r and trace
+ * [max_iterations] may be NULL.  Everything is written after all has run and stays untouched on any error.  Checked
+ * before any device work: L3D_ERR_LIMIT for 2^30 or more segments on a side; L3D_ERR_ARG for a null pointer where one is
+ * needed, a coordinate not finite or beyond 2^100, a threshold outside its range, start_distance below max_distance or
+ * not finite, step_tolerance not finite or not > 0, max_iterations outside 1..256, min_matches 0, estimate_scale > 1,
+ * reserved != 0, an initial similarity that is not finite or has scale <= 0 or a zero quaternion, and R's bounding box a
+ * point.  An empty Q or R: L3D_OK, status L3D_ALIGN_TOO_FEW, the initial transform returned, zero iterations. */
+int l3d_align_segments(int device, uint32_t n_q, const double* q_segs6, const uint32_t* q_line, uint32_t n_r,
+                       const double* r_segs6, const uint32_t* r_line, const l3d_align_params* params,
+                       const l3d_similarity* initial, l3d_similarity* out_similarity, l3d_align_summary* summary,
+                       double* out_segs6, l3d_line_match* out_q, l3d_line_match* out_r, l3d_align_iteration* trace);
+/* The same with Q = the context's lines, flattened as for l3d_compare_lines, aligned to the model `other` as R; on the
+ * context's stream.  The context is NOT modified: out_segs6 receives the moved copy.  L3D_ERR_STATE without reconstructed
+ * lines or while a split call is open. */
+int l3d_align_lines(l3d_ctx*, uint32_t n_other, const double* other_segs6, const uint32_t* other_line,
+                    const l3d_align_params* params, const l3d_similarity* initial, l3d_similarity* out_similarity,
+                    l3d_align_summary* summary, double* out_segs6, l3d_line_match* out_mine, l3d_line_match* out_other,
+                    l3d_align_iteration* trace);
+/* Host only: out_segs6 [n x 6] = the similarity applied to both end points of every segment -- its quaternion divided by
+ * its norm first, as every pass of the calls above applies one -- by the function the device runs: bit-equal to out_segs6
+ * of an alignment that returned this similarity.  L3D_ERR_ARG for a null pointer or a similarity as refused above. */
+int l3d_transform_segments(uint32_t n, const double* segs6, const l3d_similarity* similarity, double* out_segs6);
 
 #ifdef __cplusplus
 }

@@ -13,6 +13,7 @@
 //     associateSegments([camID,] out, max_distance, max_angle, min_overlap)   (... and the 2D segments that observe them)
 //     compareLines(other, mine, theirs, max_distance, max_angle, min_overlap)   (... and compared with another model)
 //     mergeLines(max_distance, max_angle, min_overlap)                           (... and their near-duplicates merged)
+//     alignLines(other, similarity, summary, max_distance, start_distance, ...)  (... and aligned to a model in another frame)
 //
 // Same names, argument order, defaults (commons.h:40-70) and error behaviour as the reference: errors
 // are printed with the "[L3D++] ERROR:" prefix and the call returns (void), no exceptions
@@ -517,6 +518,56 @@ public:
         b.resize(line.size());
         mine.swap(a);
         theirs.swap(b);
+    }
+
+    // This model aligned to another one (no reference counterpart; DESIGN §23, k_align.hip): the similarity transform
+    // y = scale * R(q) x + t that moves the lines of the last reconstruct3Dlines onto `other`, a model of the same scene
+    // in another frame, by iterated closest lines from `initial` (null: identity); the gate of a match halves from
+    // start_distance (0: none) down to max_distance, both in the units of `other`.  similarity and summary receive the
+    // result; moved (may be null): this model's flat segments under the transform, 6 doubles each; mine / theirs (may be
+    // null): the comparison of the aligned models at max_distance, as compareLines returns it.  The model itself is NOT
+    // changed.  Errors are printed and leave every output as it was.
+    void alignLines(const std::vector<FinalLine3D>& other, l3d_similarity& similarity, l3d_align_summary& summary,
+                    const double max_distance, const double start_distance = 0.0, const l3d_similarity* initial = nullptr,
+                    const bool estimate_scale = true, const double max_angle = 10.0, const double min_overlap = 0.5,
+                    std::vector<double>* moved = nullptr, std::vector<l3d_line_match>* mine = nullptr,
+                    std::vector<l3d_line_match>* theirs = nullptr) {
+        if (!(max_angle >= 0.0 && max_angle <= 90.0)) {
+            std::cout << prefix_err_ << "alignLines: max_angle must lie in [0, 90] degrees" << std::endl;
+            return;
+        }
+        const double cosine = std::cos(max_angle * (3.14159265358979323846 / 180.0));
+        const l3d_align_params par{max_distance, cosine * cosine, min_overlap, start_distance, 1e-9, 50u, 8u, estimate_scale ? 1u : 0u, 0u, {0u, 0u}};
+        std::vector<double> segs;
+        std::vector<uint32_t> line;
+        for (size_t i = 0; i < other.size(); ++i)
+            for (const l3d_segment3d& s : other[i].collinear3Dsegments_) {
+                segs.insert(segs.end(), s.P1, s.P1 + 3);
+                segs.insert(segs.end(), s.P2, s.P2 + 3);
+                line.push_back((uint32_t)i);
+            }
+        uint32_t ns = 0;
+        if (l3d_num_3d_lines(ctx_, nullptr, &ns, nullptr) != L3D_OK) {
+            std::cout << prefix_err_ << "alignLines: " << l3d_last_error() << std::endl;
+            return;
+        }
+        std::vector<double> m(6 * (size_t)(ns ? ns : 1));
+        std::vector<l3d_line_match> a(ns ? ns : 1), b(line.empty() ? 1 : line.size());
+        l3d_similarity sim;
+        l3d_align_summary sum;
+        if (l3d_align_lines(ctx_, (uint32_t)line.size(), segs.data(), line.data(), &par, initial, &sim, &sum, m.data(), a.data(),
+                            b.data(), nullptr) != L3D_OK) {
+            std::cout << prefix_err_ << "alignLines: " << l3d_last_error() << std::endl;
+            return;
+        }
+        similarity = sim;
+        summary = sum;
+        m.resize(6 * (size_t)ns);
+        a.resize(ns);
+        b.resize(line.size());
+        if (moved) moved->swap(m);
+        if (mine) mine->swap(a);
+        if (theirs) theirs->swap(b);
     }
 
     // The near-duplicate lines of this model merged (no reference counterpart; DESIGN §19, k_merge.hip): lines joined by

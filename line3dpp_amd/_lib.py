@@ -39,6 +39,12 @@ assert ASSOCIATION_DTYPE.itemsize == 24
 LINE_MATCH_DTYPE = np.dtype([("segment", "<i4"), ("line", "<u4"), ("n_accepted", "<u4"), ("overlap", "<f4"),
                              ("distance", "<f8")])
 assert LINE_MATCH_DTYPE.itemsize == 24
+# l3d_similarity and l3d_align_iteration: one entry of an alignment's trace
+SIMILARITY_DTYPE = np.dtype([("scale", "<f8"), ("q", "<f8", 4), ("t", "<f8", 3)])
+ALIGN_ITERATION_DTYPE = np.dtype([("gate", "<f8"), ("sums", "<f8", 37), ("delta", "<f8", 7), ("similarity", SIMILARITY_DTYPE),
+                                  ("n_matched", "<u8")])
+assert SIMILARITY_DTYPE.itemsize == 64 and ALIGN_ITERATION_DTYPE.itemsize == 432
+ALIGN_STATUS = ("CONVERGED", "MAX_ITERATIONS", "TOO_FEW", "DEGENERATE")
 # l3d_merge_line_info: one line of a merged model
 MERGE_LINE_INFO_DTYPE = np.dtype([("n_members", "<u4"), ("label", "<u4"), ("max_offset", "<f8")])
 assert MERGE_LINE_INFO_DTYPE.itemsize == 16
@@ -163,6 +169,25 @@ class MergeSummary(C.Structure):
                 ("max_offset", C.c_double)]
 
 
+class Similarity(C.Structure):
+    """l3d_similarity (include/l3dpp_hip.h): y = scale * R(q) x + t, q = (w, x, y, z)"""
+    _fields_ = [("scale", C.c_double), ("q", C.c_double * 4), ("t", C.c_double * 3)]
+
+
+class AlignParams(C.Structure):
+    """l3d_align_params (include/l3dpp_hip.h)"""
+    _fields_ = [("max_distance", C.c_double), ("min_cos2", C.c_double), ("min_overlap", C.c_double),
+                ("start_distance", C.c_double), ("step_tolerance", C.c_double), ("max_iterations", C.c_uint32),
+                ("min_matches", C.c_uint32), ("estimate_scale", C.c_uint32), ("slice_chunks", C.c_uint32),
+                ("reserved", C.c_uint32 * 2)]
+
+
+class AlignSummary(C.Structure):
+    """l3d_align_summary (include/l3dpp_hip.h)"""
+    _fields_ = [("status", C.c_uint32), ("iterations", C.c_uint32), ("n_matched", C.c_uint64), ("rms", C.c_double),
+                ("last_step", C.c_double), ("diag", C.c_double), ("center", C.c_double * 3)]
+
+
 class DetectStats(C.Structure):
     """l3d_detect_stats (include/l3dpp_hip.h)"""
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("raw_segments", C.c_uint32), ("segments", C.c_uint32),
@@ -250,6 +275,7 @@ EXPORTS = [
     "l3d_associate_segments", "l3d_associate_view_segments",
     "l3d_compare_segments", "l3d_compare_lines",
     "l3d_merge_segments", "l3d_merge_lines",
+    "l3d_align_segments", "l3d_align_lines", "l3d_transform_segments",
 ]
 
 _lib = None
@@ -391,6 +417,11 @@ def load():
     L.l3d_merge_segments.argtypes = [i32, u32, vp, vp, C.POINTER(MergeParams), vp, u32, vp, vp, C.POINTER(u32), u32, vp,
                                      C.POINTER(u32), C.POINTER(MergeSummary)]
     L.l3d_merge_lines.argtypes = [vp, C.POINTER(MergeParams), C.POINTER(MergeSummary)]
+    L.l3d_align_segments.argtypes = [i32, u32, vp, vp, u32, vp, vp, C.POINTER(AlignParams), C.POINTER(Similarity),
+                                     C.POINTER(Similarity), C.POINTER(AlignSummary), vp, vp, vp, vp]
+    L.l3d_align_lines.argtypes = [vp, u32, vp, vp, C.POINTER(AlignParams), C.POINTER(Similarity), C.POINTER(Similarity),
+                                  C.POINTER(AlignSummary), vp, vp, vp, vp]
+    L.l3d_transform_segments.argtypes = [u32, vp, C.POINTER(Similarity), vp]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("l3d_last_error", "l3d_build_info", "l3d_create", "l3d_destroy"):

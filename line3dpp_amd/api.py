@@ -15,7 +15,7 @@ import threading
 import numpy as np
 
 from . import _lib, lsd
-from ._lib import (ASSOCIATION_DTYPE, CLEDGE_DTYPE, EMPTY, FLOAT4_DTYPE, LINE_MATCH_DTYPE, MATCH_DTYPE, MERGE_LINE_INFO_DTYPE,
+from ._lib import (ALIGN_ITERATION_DTYPE, ALIGN_STATUS, ASSOCIATION_DTYPE, CLEDGE_DTYPE, EMPTY, FLOAT4_DTYPE, LINE_MATCH_DTYPE, MATCH_DTYPE, MERGE_LINE_INFO_DTYPE,
                    PROJECTED_SEGMENT_DTYPE, SEGMENT2D_DTYPE,
                    SEGMENT3D_DTYPE, SLOT_DTYPE, MatchParams, Timings, ptr)
 
@@ -505,6 +505,33 @@ class Line3D:
             return None
         return merge_summary_dict(s)
 
+    # ---- this model aligned to another one (no reference counterpart) -------------------------------------
+    def alignLines(self, other, max_distance, start_distance=0.0, initial=None, estimate_scale=True, max_angle=10.0,
+                   min_overlap=0.5, step_tolerance=1e-9, max_iterations=50, min_matches=8, slice_chunks=0):
+        """the similarity transform that moves the 3D lines of the last reconstruct3Dlines onto `other` (as in
+        compareLines), by iterated closest lines from `initial` (a similarity dict, a 3x4 / 4x4 matrix, or None =
+        identity) -> the dict of align_segments: the similarity, its matrix, the summary, the moved copy of this model's
+        flat segments, the matches of both sides after alignment and the trace; None after an error.  The context's
+        lines are NOT modified."""
+        if isinstance(other, Line3D):
+            other = other.get3Dlines()
+        try:
+            par = align_params(max_distance, start_distance, max_angle, min_overlap, step_tolerance, max_iterations, min_matches,
+                               estimate_scale, slice_chunks)
+            init = _similarity_struct(initial)
+            segs, line = flatten_lines(other)
+        except (ValueError, KeyError, TypeError) as e:
+            print(f"{self.PREFIX}ERROR: alignLines: {e}")
+            self.last_status = -1
+            return None
+        nl = C.c_uint32(); ns = C.c_uint32(); nr = C.c_uint32()
+        if not self._check(self.L.l3d_num_3d_lines(self.h, C.byref(nl), C.byref(ns), C.byref(nr)), "alignLines"):
+            return None
+        out = _AlignOutputs(ns.value, len(line), par.max_iterations)
+        if not self._check(self.L.l3d_align_lines(self.h, len(line), ptr(segs), ptr(line), C.byref(par), init, *out.pointers()), "alignLines"):
+            return None
+        return out.result()
+
     def set_projection_budget(self, n_bytes):
         """test hook: device-memory budget of a group of cameras in the four calls above (0: the default)"""
         self.L.l3d_set_projection_budget(self.h, int(n_bytes))
@@ -882,6 +909,164 @@ def merge_segments(segs, line, max_distance, max_angle=10.0, min_overlap=0.5, sl
     if rc != 0:
         raise RuntimeError(f"l3d_merge_segments failed [{rc}]: {_lib.last_error()}")
     return out[:n_segs.value], out_line[:n_segs.value], line_map[:n], info[:n_lines.value], merge_summary_dict(summary)
+
+
+def align_params(max_distance, start_distance=0.0, max_angle=10.0, min_overlap=0.5, step_tolerance=1e-9, max_iterations=50,
+                 min_matches=8, estimate_scale=True, slice_chunks=0):
+    """l3d_align_params from the wrappers' arguments, by compare_params' degree rule"""
+    p = compare_params(max_distance, max_angle, min_overlap, False, slice_chunks)
+    return _lib.AlignParams(p.max_distance, p.min_cos2, p.min_overlap, float(start_distance), float(step_tolerance),
+                            int(max_iterations), int(min_matches), int(bool(estimate_scale)), p.slice_chunks, (0, 0))
+
+
+def rotation_from_quaternion(q):
+    """R(q) of a quaternion (w, x, y, z), divided by its norm first: the nine expressions of DESIGN §23"""
+    q = np.asarray(q, np.float64).reshape(4)
+    w, x, y, z = q / np.sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3])
+    return np.array([[1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - w * z), 2.0 * (x * z + w * y)],
+                     [2.0 * (x * y + w * z), 1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z - w * x)],
+                     [2.0 * (x * z - w * y), 2.0 * (y * z + w * x), 1.0 - 2.0 * (x * x + y * y)]])
+
+
+def similarity_matrix(similarity):
+    """a similarity dict (scale, q = (w, x, y, z), t) -> the 4x4 matrix [[scale R(q), t], [0, 0, 0, 1]]"""
+    M = np.eye(4)
+    M[:3, :3] = float(similarity["scale"]) * rotation_from_quaternion(similarity["q"])
+    M[:3, 3] = np.asarray(similarity["t"], np.float64).reshape(3)
+    return M
+
+
+def similarity_from_matrix(M):
+    """a 3x4 or 4x4 matrix [scale R, t] -> the similarity dict; ValueError where the left block is no scaled rotation"""
+    M = np.asarray(M, np.float64)
+    if M.shape not in ((3, 4), (4, 4)) or not np.isfinite(M).all():
+        raise ValueError("a similarity is a finite 3x4 or 4x4 matrix")
+    A = M[:3, :3]
+    det = float(np.linalg.det(A))
+    if not det > 0.0:
+        raise ValueError("the matrix holds no rotation: its determinant is not positive")
+    scale = det ** (1.0 / 3.0)
+    R = A / scale
+    if not np.allclose(R @ R.T, np.eye(3), atol=1e-6):
+        raise ValueError("the matrix's left block is not a scaled rotation")
+    # the largest of the four diagonal forms keeps the division away from zero
+    tr = R[0, 0] + R[1, 1] + R[2, 2]
+    cand = [tr, R[0, 0] - R[1, 1] - R[2, 2], R[1, 1] - R[0, 0] - R[2, 2], R[2, 2] - R[0, 0] - R[1, 1]]
+    k = int(np.argmax(cand))
+    r = np.sqrt(1.0 + cand[k])
+    if k == 0:
+        q = [0.5 * r, (R[2, 1] - R[1, 2]) / (2 * r), (R[0, 2] - R[2, 0]) / (2 * r), (R[1, 0] - R[0, 1]) / (2 * r)]
+    elif k == 1:
+        q = [(R[2, 1] - R[1, 2]) / (2 * r), 0.5 * r, (R[0, 1] + R[1, 0]) / (2 * r), (R[0, 2] + R[2, 0]) / (2 * r)]
+    elif k == 2:
+        q = [(R[0, 2] - R[2, 0]) / (2 * r), (R[0, 1] + R[1, 0]) / (2 * r), 0.5 * r, (R[1, 2] + R[2, 1]) / (2 * r)]
+    else:
+        q = [(R[1, 0] - R[0, 1]) / (2 * r), (R[0, 2] + R[2, 0]) / (2 * r), (R[1, 2] + R[2, 1]) / (2 * r), 0.5 * r]
+    q = np.array(q)
+    if q[0] < 0:
+        q = -q
+    return dict(scale=float(scale), q=q / np.linalg.norm(q), t=M[:3, 3].copy())
+
+
+def similarity_from_points(src, dst, with_scale=True):
+    """the similarity that maps the points src [n, 3] onto dst [n, 3] in the least-squares sense (Umeyama's closed form,
+    numpy on the host): how a caller gets `initial` from corresponding camera centres or tie points -> similarity dict"""
+    src = np.asarray(src, np.float64).reshape(-1, 3); dst = np.asarray(dst, np.float64).reshape(-1, 3)
+    if len(src) != len(dst) or len(src) < 3:
+        raise ValueError("three or more corresponding points on either side")
+    ms, md = src.mean(0), dst.mean(0)
+    a, b = src - ms, dst - md
+    U, S, Vt = np.linalg.svd(b.T @ a / len(src))
+    D = np.ones(3)
+    if np.linalg.det(U) * np.linalg.det(Vt) < 0:
+        D[2] = -1.0
+    R = U @ np.diag(D) @ Vt
+    var = (a * a).sum() / len(src)
+    if not var > 0.0:
+        raise ValueError("the source points coincide")
+    scale = float((S * D).sum() / var) if with_scale else 1.0
+    M = np.zeros((3, 4))
+    M[:, :3] = scale * R
+    M[:, 3] = md - scale * (R @ ms)
+    out = similarity_from_matrix(M)
+    out["scale"] = scale
+    return out
+
+
+def _similarity_struct(similarity):
+    """None, a similarity dict or a 3x4 / 4x4 matrix -> a pointer argument for the C-ABI (None: identity)"""
+    if similarity is None:
+        return None
+    if not isinstance(similarity, dict):
+        similarity = similarity_from_matrix(similarity)
+    q = np.asarray(similarity["q"], np.float64).reshape(4); t = np.asarray(similarity["t"], np.float64).reshape(3)
+    return C.pointer(_lib.Similarity(float(similarity["scale"]), (C.c_double * 4)(*q), (C.c_double * 3)(*t)))
+
+
+def similarity_dict(s):
+    return dict(scale=float(s.scale), q=np.array(s.q[:], np.float64), t=np.array(s.t[:], np.float64))
+
+
+def align_summary_dict(s):
+    d = dict(status=ALIGN_STATUS[s.status], iterations=int(s.iterations), n_matched=int(s.n_matched), rms=float(s.rms),
+             last_step=float(s.last_step), diag=float(s.diag), center=np.array(s.center[:], np.float64))
+    return d
+
+
+class _AlignOutputs:
+    """the output arguments of l3d_align_segments / l3d_align_lines, and the dict the wrappers return from them"""
+
+    def __init__(self, n_q, n_r, max_iterations):
+        self.n_q, self.n_r = n_q, n_r
+        self.similarity = _lib.Similarity(); self.summary = _lib.AlignSummary()
+        self.segs = np.zeros((max(n_q, 1), 6), np.float64)
+        self.mq = np.zeros(max(n_q, 1), LINE_MATCH_DTYPE); self.mr = np.zeros(max(n_r, 1), LINE_MATCH_DTYPE)
+        self.trace = np.zeros(max(int(max_iterations), 1), ALIGN_ITERATION_DTYPE)
+
+    def pointers(self):
+        return (C.byref(self.similarity), C.byref(self.summary), ptr(self.segs), ptr(self.mq), ptr(self.mr), ptr(self.trace))
+
+    def result(self):
+        sim = similarity_dict(self.similarity)
+        summary = align_summary_dict(self.summary)
+        return dict(similarity=sim, matrix=similarity_matrix(sim), summary=summary, segments=self.segs[:self.n_q],
+                    matches_q=self.mq[:self.n_q], matches_r=self.mr[:self.n_r], trace=self.trace[:summary["iterations"]])
+
+
+def align_segments(q_segs, q_line, r_segs, r_line, max_distance, start_distance=0.0, initial=None, estimate_scale=True,
+                   max_angle=10.0, min_overlap=0.5, step_tolerance=1e-9, max_iterations=50, min_matches=8, slice_chunks=0,
+                   device=0):
+    """l3d_align_segments: the similarity transform that moves the model Q onto the model R (segs [n, 6]
+    float64 with a line index each), by iterated closest lines from `initial` (a similarity dict, a 3x4 / 4x4 matrix,
+    None = identity) with the gate halving from start_distance down to max_distance -> a dict: similarity (scale, q, t),
+    matrix (4x4), summary (status as a name, iterations, n_matched, rms, last_step, diag, center), segments (Q moved),
+    matches_q / matches_r (LINE_MATCH_DTYPE, the aligned models compared at max_distance) and trace (one
+    ALIGN_ITERATION_DTYPE entry per iteration)"""
+    L = _lib.load()
+    q = np.ascontiguousarray(q_segs, np.float64).reshape(-1, 6); r = np.ascontiguousarray(r_segs, np.float64).reshape(-1, 6)
+    ql = np.ascontiguousarray(q_line, np.uint32).reshape(-1); rl = np.ascontiguousarray(r_line, np.uint32).reshape(-1)
+    if len(ql) != len(q) or len(rl) != len(r):
+        raise ValueError("one line index per segment")
+    par = align_params(max_distance, start_distance, max_angle, min_overlap, step_tolerance, max_iterations, min_matches,
+                       estimate_scale, slice_chunks)
+    out = _AlignOutputs(len(q), len(r), par.max_iterations)
+    rc = L.l3d_align_segments(int(device), len(q), ptr(q), ptr(ql), len(r), ptr(r), ptr(rl), C.byref(par), _similarity_struct(initial),
+                              *out.pointers())
+    if rc != 0:
+        raise RuntimeError(f"l3d_align_segments failed [{rc}]: {_lib.last_error()}")
+    return out.result()
+
+
+def transform_segments(segs, similarity):
+    """l3d_transform_segments: segs [n, 6] under a similarity (dict or matrix), on the host by the function the device
+    runs -> [n, 6] float64"""
+    L = _lib.load()
+    s = np.ascontiguousarray(segs, np.float64).reshape(-1, 6)
+    out = np.zeros((max(len(s), 1), 6), np.float64)
+    rc = L.l3d_transform_segments(len(s), ptr(s), _similarity_struct(similarity), ptr(out))
+    if rc != 0:
+        raise RuntimeError(f"l3d_transform_segments failed [{rc}]: {_lib.last_error()}")
+    return out[:len(s)]
 
 
 def render_line_maps(cams, records, thickness=1, device=0):

@@ -39,6 +39,20 @@ L3D_HD d3 mul33(const double* A, const d3& v) {
             (A[6] * v.x + A[7] * v.y) + A[8] * v.z};
 }
 
+// ---- the similarity transform of the alignment (host and device: k_align.hip, l3d_align.hip) ----
+// R(q) of a unit quaternion q = (w, x, y, z), row-major: the nine expressions of the contract
+L3D_HD void sim_rotation(const double q[4], double R[9]) {
+    const double w = q[0], x = q[1], y = q[2], z = q[3];
+    R[0] = 1.0 - 2.0 * (y * y + z * z); R[1] = 2.0 * (x * y - w * z);       R[2] = 2.0 * (x * z + w * y);
+    R[3] = 2.0 * (x * y + w * z);       R[4] = 1.0 - 2.0 * (x * x + z * z); R[5] = 2.0 * (y * z - w * x);
+    R[6] = 2.0 * (x * z - w * y);       R[7] = 2.0 * (y * z + w * x);       R[8] = 1.0 - 2.0 * (x * x + y * y);
+}
+// y_i = scale * (R_i0 x0 + R_i1 x1 + R_i2 x2) + t_i
+L3D_HD void sim_point(double scale, const double R[9], const double t[3], const double* x, double* y) {
+    const d3 v = mul33(R, d3{x[0], x[1], x[2]});
+    y[0] = scale * v.x + t[0]; y[1] = scale * v.y + t[1]; y[2] = scale * v.z + t[2];
+}
+
 // ---- IEEE double division and square root without the range scaffolding ------------------------------------------------
 // hipcc expands a / b into v_div_scale x2, v_rcp_f64, two Newton steps, q = a*y, r = fma(-b,q,a), v_div_fmas, v_div_fixup
 // (59 issue cycles per wave, tools/valu_calib.hip) and sqrt into v_rsq_f64 + Goldschmidt with ldexp scaling and a class

@@ -399,4 +399,23 @@ hipError_t launch_merge_check(const MrgArgs& a, hipStream_t st);
 // l3d_merge.hip, test hooks read through l3d_debug_counter
 extern std::atomic<uint64_t> g_mrg_count_launches, g_mrg_write_launches, g_mrg_slices, g_mrg_pairs, g_mrg_kernel_ns;
 
+// ---- k_align.hip: the similarity transform applied, and the normal equations of an alignment step (host
+// side: l3d_align.hip) ----
+constexpr uint32_t kAlnTerms = 37;       // H (28: the upper triangle of 7 x 7, row by row), b (7), cost, count
+struct AlnTransformArgs {
+    const double* in; double* out; uint32_t n;   // [n] x (P1, P2)
+    double scale, q[4], t[3];                    // q of unit length
+};
+struct AlnNormalArgs {
+    const double* q; uint32_t n_q;           // the transformed queries
+    const double* r; uint32_t n_r;           // the references
+    const CmpOut* match;                    // [n_q] the comparison's records: segment = the reference, -1: none
+    double c[3];                             // the centre the update rotates and scales about
+    double* tiles;                           // [ceil(n_q / kCmpTile) x kAlnTerms]
+};
+hipError_t launch_align_transform(const AlnTransformArgs& a, hipStream_t st);
+hipError_t launch_align_normal(const AlnNormalArgs& a, hipStream_t st);
+// l3d_align.hip, test hooks read through l3d_debug_counter
+extern std::atomic<uint64_t> g_aln_iterations, g_aln_normal_launches, g_aln_kernel_ns;
+
 }  // namespace l3d
