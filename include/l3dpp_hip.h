@@ -1106,6 +1106,78 @@ int l3d_align_lines(l3d_ctx*, uint32_t n_other, const double* other_segs6, const
  * of an alignment that returned this similarity.  L3D_ERR_ARG for a null pointer or a similarity as refused above. */
 int l3d_transform_segments(uint32_t n, const double* segs6, const l3d_similarity* similarity, double* out_segs6);
 
+/* ---- where 3D lines meet: junctions and the wireframe graph (GPU: k_wireframe.hip) ----------------------
+ * No reference counterpart.  One model as above: a flat array of 3D segments with a line index per segment (any values).
+ * Two segments a < b of different lines form a junction iff neither is a point, the angle between them is at least the
+ * one whose squared sine is min_sin2, their carriers come within max_distance of each other, and the point where they do
+ * lies on both segments or at most max_extension beyond an end.  An end of a segment within max_extension of that point
+ * is "at" the junction (L: both segments end there, T: one does, X: they cross).  Junctions that share an end of a
+ * segment, or lie within max_distance of each other inside one, form one vertex; the ends that meet nothing are vertices
+ * too, and every segment gives the edges between its consecutive vertices.  The model itself is not modified.  fp64, the
+ * contract of DESIGN §24. */
+typedef struct l3d_wireframe_params {   /* 32 bytes */
+    double max_distance;         /* model units, finite, >= 0, no default: the gap between the two carriers where they come closest */
+    double max_extension;        /* model units, finite, >= 0: how far beyond a segment's end the meeting point may lie, and
+                                    the width of the end zone */
+    double min_sin2;             /* in [0, 1]: sin^2 of the smallest angle between the two */
+    uint32_t slice_chunks;       /* 0: the library chooses; else chunks of 256 references per slice.  No output depends on it */
+    uint32_t reserved;           /* must be 0 */
+} l3d_wireframe_params;
+enum { L3D_WF_L = 1, L3D_WF_T = 2, L3D_WF_X = 4 };               /* kind of a junction; the bits of a vertex's kinds */
+enum { L3D_WF_AT_P1 = 0, L3D_WF_AT_P2 = 1, L3D_WF_INTERIOR = 2 }; /* where on a segment a junction lies */
+/* a junction (72 bytes), in ascending (a, b) order */
+typedef struct l3d_wf_junction {
+    uint32_t a, b;               /* the two segments, a < b */
+    uint32_t kind;               /* L3D_WF_L, _T or _X */
+    uint32_t class_a, class_b;   /* L3D_WF_AT_P1, _AT_P2 or _INTERIOR, on a and on b */
+    uint32_t vertex;             /* the vertex it belongs to */
+    double sa, sb;               /* the closest points of the carriers: P1 + s (P2 - P1) on a and on b */
+    double gap;                  /* their distance */
+    double J[3];                 /* their midpoint */
+} l3d_wf_junction;
+/* a vertex (48 bytes): the junction vertices, numbered by their smallest junction, then the free ends in (segment, end) order */
+typedef struct l3d_wf_vertex {
+    double P[3];                 /* the mean of its junctions' J; a free end: the end point itself */
+    double spread;               /* the largest distance of a member's J from P.  Vertices form by chaining: this is how a
+                                    caller sees one that went far */
+    uint32_t n_junctions;        /* 0: a free end */
+    uint32_t kinds;              /* the kinds of its junctions, or-ed */
+    uint32_t degree;             /* incident edges */
+    uint32_t component;          /* connected component of the graph, numbered by their smallest vertex */
+} l3d_wf_vertex;
+/* an edge (16 bytes): a piece of `segment` between two consecutive vertices on it, in ascending segment order */
+typedef struct l3d_wf_edge { uint32_t v0, v1, segment, line; } l3d_wf_edge;
+/* (120 bytes); length_total is added sequentially in ascending index order */
+typedef struct l3d_wireframe_summary {
+    uint64_t n_segments, n_point_segments, n_junctions;
+    uint64_t n_L, n_T, n_X;
+    uint64_t n_vertices, n_junction_vertices, n_free_ends;
+    uint64_t n_edges, n_components;
+    uint64_t largest_component;  /* in edges */
+    double length_total;         /* of the segments */
+    double max_gap, max_spread;
+} l3d_wireframe_summary;
+typedef struct l3d_wireframe l3d_wireframe;
+/* Stateless, host pointers.  segs6 [n x 6], line [n].  The result is not bounded by n, so it lives in a handle: *out, to be
+ * closed by l3d_wireframe_close.  Checked before any device work, *out untouched: L3D_ERR_LIMIT for 2^30 or more segments;
+ * L3D_ERR_ARG for a null pointer, a coordinate that is not finite or beyond 2^100 (the message names the segment),
+ * max_distance or max_extension negative or not finite, min_sin2 outside [0, 1] or NaN, reserved != 0.  More than 2^28
+ * junctions: L3D_ERR_LIMIT, found after the count pass, *out untouched.  n = 0: L3D_OK, an empty graph, a summary of zeros. */
+int l3d_wireframe_segments(int device, uint32_t n, const double* segs6, const uint32_t* line, const l3d_wireframe_params* params,
+                           l3d_wireframe** out);
+/* The same on the context's lines (flattened as for l3d_compare_lines), on the context's stream.  The context is NOT
+ * modified.  L3D_ERR_STATE without reconstructed lines or while a split call is open. */
+int l3d_wireframe_lines(l3d_ctx*, const l3d_wireframe_params* params, l3d_wireframe** out);
+/* the sizes of the three arrays; any pointer may be NULL */
+int l3d_wireframe_counts(const l3d_wireframe*, uint64_t* n_junctions, uint64_t* n_vertices, uint64_t* n_edges);
+/* the arrays, of the sizes l3d_wireframe_counts states, and the summary; any pointer may be NULL */
+int l3d_wireframe_get(const l3d_wireframe*, l3d_wf_junction* junctions, l3d_wf_vertex* vertices, l3d_wf_edge* edges,
+                      l3d_wireframe_summary* summary);
+/* "v x y z" (%.17g) per vertex in vertex order, then "l i j" (1-based) per edge in edge order.  L3D_ERR_IO where the file
+ * cannot be written. */
+int l3d_wireframe_save_obj(const l3d_wireframe*, const char* path);
+void l3d_wireframe_close(l3d_wireframe*);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,6 +14,7 @@
 //     compareLines(other, mine, theirs, max_distance, max_angle, min_overlap)   (... and compared with another model)
 //     mergeLines(max_distance, max_angle, min_overlap)                           (... and their near-duplicates merged)
 //     alignLines(other, similarity, summary, max_distance, start_distance, ...)  (... and aligned to a model in another frame)
+//     wireframe(max_distance, max_extension, min_angle)                          (... and where they meet: junctions, vertices, edges)
 //
 // Same names, argument order, defaults (commons.h:40-70) and error behaviour as the reference: errors
 // are printed with the "[L3D++] ERROR:" prefix and the call returns (void), no exceptions
@@ -585,6 +586,41 @@ public:
         const double cosine = std::cos(max_angle * (3.14159265358979323846 / 180.0));
         const l3d_merge_params par{max_distance, cosine * cosine, min_overlap, 0u, 0u};
         if (l3d_merge_lines(ctx_, &par, summary) != L3D_OK) std::cout << prefix_err_ << "mergeLines: " << l3d_last_error() << std::endl;
+    }
+
+    // Where the lines of this model meet (no reference counterpart; DESIGN §24, k_wireframe.hip): two segments of
+    // different lines whose carriers come within max_distance of each other, at an angle of at least min_angle, at a
+    // point on both or at most max_extension beyond an end, form a junction; the junctions and the ends that meet nothing
+    // are the vertices, the pieces of the segments between them the edges.  Segments are the flat collinear3Dsegments_ of
+    // get3Dlines, line after line.  max_distance and max_extension (negative: max_distance) in model units, min_angle in
+    // degrees [0, 90].  The model itself is NOT changed.  Errors are printed and give an empty result with ok = false.
+    struct Wireframe {
+        bool ok = false;
+        std::vector<l3d_wf_junction> junctions;
+        std::vector<l3d_wf_vertex> vertices;
+        std::vector<l3d_wf_edge> edges;
+        l3d_wireframe_summary summary{};
+    };
+    Wireframe wireframe(const double max_distance, const double max_extension = -1.0, const double min_angle = 10.0) {
+        Wireframe w;
+        if (!(min_angle >= 0.0 && min_angle <= 90.0)) {
+            std::cout << prefix_err_ << "wireframe: min_angle must lie in [0, 90] degrees" << std::endl;
+            return w;
+        }
+        const double sine = std::sin(min_angle * (3.14159265358979323846 / 180.0));
+        const l3d_wireframe_params par{max_distance, max_extension < 0.0 ? max_distance : max_extension, sine * sine, 0u, 0u};
+        l3d_wireframe* h = nullptr;
+        if (l3d_wireframe_lines(ctx_, &par, &h) != L3D_OK) {
+            std::cout << prefix_err_ << "wireframe: " << l3d_last_error() << std::endl;
+            return w;
+        }
+        uint64_t nj = 0, nv = 0, ne = 0;
+        l3d_wireframe_counts(h, &nj, &nv, &ne);
+        w.junctions.resize(nj); w.vertices.resize(nv); w.edges.resize(ne);
+        l3d_wireframe_get(h, w.junctions.data(), w.vertices.data(), w.edges.data(), &w.summary);
+        l3d_wireframe_close(h);
+        w.ok = true;
+        return w;
     }
 
     // The 3D lines drawn over inImg (cv::Mat, Image8U or ImageBuf8U, 8-bit with 1 or 3 channels, of the camera's size):

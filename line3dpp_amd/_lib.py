@@ -48,6 +48,15 @@ ALIGN_STATUS = ("CONVERGED", "MAX_ITERATIONS", "TOO_FEW", "DEGENERATE")
 # l3d_merge_line_info: one line of a merged model
 MERGE_LINE_INFO_DTYPE = np.dtype([("n_members", "<u4"), ("label", "<u4"), ("max_offset", "<f8")])
 assert MERGE_LINE_INFO_DTYPE.itemsize == 16
+# l3d_wf_junction, l3d_wf_vertex, l3d_wf_edge: the wireframe of a model
+WF_JUNCTION_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("kind", "<u4"), ("class_a", "<u4"), ("class_b", "<u4"), ("vertex", "<u4"),
+                              ("sa", "<f8"), ("sb", "<f8"), ("gap", "<f8"), ("J", "<f8", 3)])
+WF_VERTEX_DTYPE = np.dtype([("P", "<f8", 3), ("spread", "<f8"), ("n_junctions", "<u4"), ("kinds", "<u4"), ("degree", "<u4"),
+                            ("component", "<u4")])
+WF_EDGE_DTYPE = np.dtype([("v0", "<u4"), ("v1", "<u4"), ("segment", "<u4"), ("line", "<u4")])
+assert WF_JUNCTION_DTYPE.itemsize == 72 and WF_VERTEX_DTYPE.itemsize == 48 and WF_EDGE_DTYPE.itemsize == 16
+WF_L, WF_T, WF_X = 1, 2, 4                      # kind of a junction, the bits of a vertex's kinds
+WF_AT_P1, WF_AT_P2, WF_INTERIOR = 0, 1, 2       # class_a, class_b
 EMPTY = 0xFFFFFFFF
 L3D_ERR_NO_SEGMENTS = -5
 L3D_ERR_IO = -11
@@ -169,6 +178,19 @@ class MergeSummary(C.Structure):
                 ("max_offset", C.c_double)]
 
 
+class WireframeParams(C.Structure):
+    """l3d_wireframe_params (include/l3dpp_hip.h)"""
+    _fields_ = [("max_distance", C.c_double), ("max_extension", C.c_double), ("min_sin2", C.c_double),
+                ("slice_chunks", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class WireframeSummary(C.Structure):
+    """l3d_wireframe_summary (include/l3dpp_hip.h)"""
+    _fields_ = [(n, C.c_uint64) for n in ("n_segments", "n_point_segments", "n_junctions", "n_L", "n_T", "n_X", "n_vertices",
+                                          "n_junction_vertices", "n_free_ends", "n_edges", "n_components", "largest_component")] + \
+        [(n, C.c_double) for n in ("length_total", "max_gap", "max_spread")]
+
+
 class Similarity(C.Structure):
     """l3d_similarity (include/l3dpp_hip.h): y = scale * R(q) x + t, q = (w, x, y, z)"""
     _fields_ = [("scale", C.c_double), ("q", C.c_double * 4), ("t", C.c_double * 3)]
@@ -276,6 +298,8 @@ EXPORTS = [
     "l3d_compare_segments", "l3d_compare_lines",
     "l3d_merge_segments", "l3d_merge_lines",
     "l3d_align_segments", "l3d_align_lines", "l3d_transform_segments",
+    "l3d_wireframe_segments", "l3d_wireframe_lines", "l3d_wireframe_counts", "l3d_wireframe_get", "l3d_wireframe_save_obj",
+    "l3d_wireframe_close",
 ]
 
 _lib = None
@@ -422,6 +446,12 @@ def load():
     L.l3d_align_lines.argtypes = [vp, u32, vp, vp, C.POINTER(AlignParams), C.POINTER(Similarity), C.POINTER(Similarity),
                                   C.POINTER(AlignSummary), vp, vp, vp, vp]
     L.l3d_transform_segments.argtypes = [u32, vp, C.POINTER(Similarity), vp]
+    L.l3d_wireframe_segments.argtypes = [i32, u32, vp, vp, C.POINTER(WireframeParams), C.POINTER(vp)]
+    L.l3d_wireframe_lines.argtypes = [vp, C.POINTER(WireframeParams), C.POINTER(vp)]
+    L.l3d_wireframe_counts.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+    L.l3d_wireframe_get.argtypes = [vp, vp, vp, vp, C.POINTER(WireframeSummary)]
+    L.l3d_wireframe_save_obj.argtypes = [vp, C.c_char_p]
+    L.l3d_wireframe_close.argtypes = [vp]; L.l3d_wireframe_close.restype = None
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("l3d_last_error", "l3d_build_info", "l3d_create", "l3d_destroy"):

@@ -505,6 +505,22 @@ class Line3D:
             return None
         return merge_summary_dict(s)
 
+    # ---- where the lines meet (no reference counterpart) ---------------------------------------------------
+    def wireframe(self, max_distance, max_extension=None, min_angle=10.0, slice_chunks=0, obj_path=None):
+        """the junctions of the 3D lines of the last reconstruct3Dlines and the graph they form -> the dict of
+        build_wireframe (its segments are flatten_lines' of get3Dlines); None after an error.  The lines themselves are
+        NOT modified."""
+        try:
+            par = wireframe_params(max_distance, max_extension, min_angle, slice_chunks)
+        except (ValueError, TypeError) as e:
+            print(f"{self.PREFIX}ERROR: wireframe: {e}")
+            self.last_status = -1
+            return None
+        h = C.c_void_p()
+        if not self._check(self.L.l3d_wireframe_lines(self.h, C.byref(par), C.byref(h)), "wireframe"):
+            return None
+        return take_wireframe(h, obj_path)
+
     # ---- this model aligned to another one (DESIGN §23; no reference counterpart) -------------------------------------
     def alignLines(self, other, max_distance, start_distance=0.0, initial=None, estimate_scale=True, max_angle=10.0,
                    min_overlap=0.5, step_tolerance=1e-9, max_iterations=50, min_matches=8, slice_chunks=0):
@@ -909,6 +925,65 @@ def merge_segments(segs, line, max_distance, max_angle=10.0, min_overlap=0.5, sl
     if rc != 0:
         raise RuntimeError(f"l3d_merge_segments failed [{rc}]: {_lib.last_error()}")
     return out[:n_segs.value], out_line[:n_segs.value], line_map[:n], info[:n_lines.value], merge_summary_dict(summary)
+
+
+def wireframe_params(max_distance, max_extension=None, min_angle=10.0, slice_chunks=0):
+    """l3d_wireframe_params from the wrappers' arguments: max_extension None = max_distance; min_sin2 =
+    sin(radians(min_angle))^2, min_angle in [0, 90] (compare_params' degree rule)"""
+    if not 0.0 <= float(min_angle) <= 90.0:
+        raise ValueError("min_angle must lie in [0, 90] degrees")
+    sin = float(np.sin(np.radians(np.float64(min_angle))))
+    return _lib.WireframeParams(float(max_distance), float(max_distance if max_extension is None else max_extension), sin * sin,
+                                int(slice_chunks), 0)
+
+
+def wireframe_summary_dict(s):
+    return {f: getattr(s, f) for f, _ in _lib.WireframeSummary._fields_}
+
+
+def take_wireframe(handle, obj_path=None):
+    """the arrays and the summary out of an l3d_wireframe handle, which is closed -> dict(junctions: WF_JUNCTION_DTYPE,
+    vertices: WF_VERTEX_DTYPE, edges: WF_EDGE_DTYPE, summary: dict).  obj_path: l3d_wireframe_save_obj writes it first"""
+    L = _lib.load()
+    try:
+        if obj_path is not None and L.l3d_wireframe_save_obj(handle, str(obj_path).encode()) != 0:
+            raise RuntimeError(f"l3d_wireframe_save_obj failed: {_lib.last_error()}")
+        nj = C.c_uint64(); nv = C.c_uint64(); ne = C.c_uint64(); s = _lib.WireframeSummary()
+        L.l3d_wireframe_counts(handle, C.byref(nj), C.byref(nv), C.byref(ne))
+        j = np.zeros(max(nj.value, 1), _lib.WF_JUNCTION_DTYPE); v = np.zeros(max(nv.value, 1), _lib.WF_VERTEX_DTYPE)
+        e = np.zeros(max(ne.value, 1), _lib.WF_EDGE_DTYPE)
+        L.l3d_wireframe_get(handle, ptr(j), ptr(v), ptr(e), C.byref(s))
+    finally:
+        L.l3d_wireframe_close(handle)
+    return dict(junctions=j[:nj.value], vertices=v[:nv.value], edges=e[:ne.value], summary=wireframe_summary_dict(s))
+
+
+def build_wireframe(segs, line, max_distance, max_extension=None, min_angle=10.0, slice_chunks=0, device=0, obj_path=None):
+    """l3d_wireframe_segments: one model of 3D segments, segs [n, 6] float64 (P1, P2) with a line index each ->
+    dict(junctions, vertices, edges: structured arrays, summary: a dict): where the lines meet, the vertices these
+    junctions and the free ends form, and every segment cut into the edges between its vertices.  max_distance and
+    max_extension (None: max_distance) in model units, min_angle in degrees [0, 90]."""
+    L = _lib.load()
+    s = np.ascontiguousarray(segs, np.float64).reshape(-1, 6)
+    ln = np.ascontiguousarray(line, np.uint32).reshape(-1)
+    if len(ln) != len(s):
+        raise ValueError("one line index per segment")
+    par = wireframe_params(max_distance, max_extension, min_angle, slice_chunks)
+    h = C.c_void_p()
+    rc = L.l3d_wireframe_segments(int(device), len(s), ptr(s), ptr(ln), C.byref(par), C.byref(h))
+    if rc != 0:
+        raise RuntimeError(f"l3d_wireframe_segments failed [{rc}]: {_lib.last_error()}")
+    return take_wireframe(h, obj_path)
+
+
+def write_wireframe_obj(wireframe, path):
+    """a wireframe as build_wireframe returns it -> an OBJ file, the bytes of l3d_wireframe_save_obj: "v x y z" at %.17g per
+    vertex, then "l i j" (1-based) per edge"""
+    with open(path, "w") as f:
+        for v in wireframe["vertices"]:
+            f.write("v %.17g %.17g %.17g\n" % (float(v["P"][0]), float(v["P"][1]), float(v["P"][2])))
+        for e in wireframe["edges"]:
+            f.write("l %d %d\n" % (int(e["v0"]) + 1, int(e["v1"]) + 1))
 
 
 def align_params(max_distance, start_distance=0.0, max_angle=10.0, min_overlap=0.5, step_tolerance=1e-9, max_iterations=50,

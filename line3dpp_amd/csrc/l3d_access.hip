@@ -217,6 +217,13 @@ unsigned long long l3d_debug_counter(const char* name) {
     if (name && std::string(name) == "align_iterations") return g_aln_iterations.load(std::memory_order_relaxed);
     if (name && std::string(name) == "align_normal_launches") return g_aln_normal_launches.load(std::memory_order_relaxed);
     if (name && std::string(name) == "align_kernel_ns") return g_aln_kernel_ns.load(std::memory_order_relaxed);
+    if (name && std::string(name) == "wf_count_launches") return g_wf_count_launches.load(std::memory_order_relaxed);
+    if (name && std::string(name) == "wf_write_launches") return g_wf_write_launches.load(std::memory_order_relaxed);
+    if (name && std::string(name) == "wf_slices") return g_wf_slices.load(std::memory_order_relaxed);
+    if (name && std::string(name) == "wf_junctions") return g_wf_junctions.load(std::memory_order_relaxed);
+    if (name && std::string(name) == "wf_skipped_blocks") return g_wf_skipped_blocks.load(std::memory_order_relaxed);
+    if (name && std::string(name) == "wf_kernel_ns") return g_wf_kernel_ns.load(std::memory_order_relaxed);
+    if (name && std::string(name) == "wf_count_ns") return g_wf_count_ns.load(std::memory_order_relaxed);
     if (name && std::string(name) == "live_device_blocks") return g_live_blocks[0].load(std::memory_order_relaxed);
     if (name && std::string(name) == "live_pinned_blocks") return g_live_blocks[1].load(std::memory_order_relaxed);
     static const char* const kSeamSupport[4] = {"seam_support_wave_lists", "seam_support_group_staged_lists",

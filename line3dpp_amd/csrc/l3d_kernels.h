@@ -399,6 +399,25 @@ hipError_t launch_merge_check(const MrgArgs& a, hipStream_t st);
 // l3d_merge.hip, test hooks read through l3d_debug_counter
 extern std::atomic<uint64_t> g_mrg_count_launches, g_mrg_write_launches, g_mrg_slices, g_mrg_pairs, g_mrg_kernel_ns;
 
+// ---- k_wireframe.hip: the junctions of one model, as a list (host side: l3d_wireframe.hip) ----
+// k_merge's two walks over k_compare's tiling, over the pairs a < b only.
+struct WfJunction { uint32_t a, b; double sa, sb, gap2; };   // = WfRecord of l3d_wireframe.h
+static_assert(sizeof(WfJunction) == 32, "junction record layout");
+struct WfArgs {
+    const double* segs; const uint32_t* line; uint32_t n;    // [n] x (P1, P2), their lines: queries and references alike
+    uint32_t slice_chunks, n_slices;
+    double max_d2, max_extension, min_sin2;  // max_distance * max_distance, the reach beyond an end, the squared sine
+    uint32_t* counts;                        // [n * n_slices + 1]: k_wf_count's counts at [q * n_slices + slice], then
+                                             // their exclusive scan in place (the total behind the last one)
+    WfJunction* out; uint32_t n_out;         // [n_out = the total], written by k_wf_write
+    uint32_t* wrapped;                       // k_wf_check: set to 1 where the 32-bit scan has wrapped
+};
+hipError_t launch_wf_count(const WfArgs& a, hipStream_t st);
+hipError_t launch_wf_write(const WfArgs& a, hipStream_t st);
+hipError_t launch_wf_check(const WfArgs& a, hipStream_t st);
+// l3d_wireframe.hip, test hooks read through l3d_debug_counter
+extern std::atomic<uint64_t> g_wf_count_launches, g_wf_write_launches, g_wf_slices, g_wf_junctions, g_wf_skipped_blocks, g_wf_kernel_ns, g_wf_count_ns;
+
 // ---- k_align.hip: the similarity transform applied, and the normal equations of an alignment step (host
 // side: l3d_align.hip) ----
 constexpr uint32_t kAlnTerms = 37;       // H (28: the upper triangle of 7 x 7, row by row), b (7), cost, count
