@@ -108,39 +108,7 @@ __device__ __forceinline__ float ord2f(uint32_t o) {
     return __uint_as_float((o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o);
 }
 
-// ---- similarityForScoring (line3D.cc:1417-1446) for hypotheses a (the scored one) and b of the same 2D segment ----
-// Decision form: "similarityForScoring > L3D_DEF_MIN_SIMILARITY_3D" without transcendentals.
-// sim = fmin(sim_a, fmin(e1, e2)) > 0.5 <=> every non-NaN component is > 0.5 (fmin skips NaNs; all NaN -> false).
-// expf and acos are monotone, so each component test is a comparison of its float argument with a threshold the host
-// found by bisection with the libm the reference itself would use (sim_thresholds, l3d_api.hip):
-//     expf(y) > 0.5f                           <=>  y > y_thr
-//     expf(-angle(x)^2 / two_sigA_sqr) > 0.5f  <=>  x >= x_hi || x <= x_lo     (x = clamped float dot product)
-__device__ __forceinline__ bool sim_decide(const d3 dira, bool zeroa, float adp1, float adp2, float reg1, float reg2,
-                                           const d3 dirb, bool zerob, float bdp1, float bdp2, const SimConst sc) {
-    if (zeroa || zerob) return false;
-    const float d1 = adp1 - bdp1, d2 = adp2 - bdp2;
-    const float y1 = -d1 * d1 / reg1, y2 = -d2 * d2 / reg2;
-    // NaN components drop out of the fmin chain; the angular component is never NaN (x is clamped, sigma_a > 0)
-    if (y1 == y1 && !(y1 > sc.y_thr)) return false;
-    if (y2 == y2 && !(y2 > sc.y_thr)) return false;
-    const float dot_p = (float)dot(dira, dirb);
-    const float x = fmaxf(fminf(dot_p, 1.0f), -1.0f);
-    return x >= sc.x_hi || x <= sc.x_lo;
-}
-
-// Value form, for pairs sim_decide accepted.  acos/exp are evaluated in double and rounded to float (glibc's
-// expf/acos differ from that by < 1 float ulp).  fmin(expf(ya), fmin(expf(y1), expf(y2))) == expf(fmin(ya, fmin(y1,
-// y2))): expf is monotone and fmin skips NaNs on both sides alike -- one exponential instead of three.
-__device__ __forceinline__ float sim_value(const d3 dira, float adp1, float adp2, float reg1, float reg2,
-                                           const d3 dirb, float bdp1, float bdp2, const SimConst sc) {
-    const float d1 = adp1 - bdp1, d2 = adp2 - bdp2;
-    const float y1 = -d1 * d1 / reg1, y2 = -d2 * d2 / reg2;
-    const float dot_p = (float)dot(dira, dirb);
-    float angle = (float)(acos((double)fmaxf(fminf(dot_p, 1.0f), -1.0f)) / M_PI * 180.0f);
-    if (angle > 90.0f) angle = 180.0f - angle;
-    const float ya = -angle * angle / sc.two_sigA_sqr;
-    return (float)exp((double)fminf(ya, fminf(y1, y2)));
-}
+// similarityForScoring: sim_decide / sim_value of l3d_dev.h (the form without the division-free early-out)
 
 // the exact test of one ordered pair (i scored, j supporter) of the segment with invariants sx in view v:
 // scoringCPU's unprojection + spatial regularisers of i (line3D.cc:1233-1248) and similarityForScoring(i, j)
@@ -163,14 +131,7 @@ __device__ __forceinline__ bool exact_support(const ViewDev& v, const ViewDev* _
     return true;
 }
 
-// Conservative squared depth windows of hypothesis i, from slot data alone: similarityForScoring(i, .) > 0.5 needs
-// d^2 < 0.6932 * reg (expf(-d^2/reg) > 0.5), and reg = (dp k)^2 + (|P - C_t| k_t)^2 with |P - C_t| <= dp + |C - C_t|
-// (P = C + ray * dp, unit ray): no unprojection is needed to bound it.  0.72 * 1.001 covers every float rounding.
-__device__ __forceinline__ float window_sq(float dp, float k, float kt, float cc_dist) {
-    const float a = dp * k, b = (dp + cc_dist) * kt;
-    const float r = 0.72f * 1.001f * (a * a + b * b) + 1e-37f;
-    return (r < 1e30f) ? r : __builtin_inff();     // NaN / huge: the whole list is the window
-}
+// (the conservative squared depth windows of a hypothesis: window_sq, l3d_dev.h)
 
 // ---- compare-exchange steps of the sorting networks with SCALAR direction logic ---------------------------------------
 // In a bitonic network, which lanes keep the smaller key of a pair is a fixed pattern of the lane index per stage.

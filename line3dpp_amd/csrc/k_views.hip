@@ -104,46 +104,8 @@ __device__ __forceinline__ d3 entry_dir(const double* C, const SegX& sx, float d
 }
 
 // ---- similarity of two hypotheses of one 2D segment ------------------------------------------------
-// similarityForScoring (line3D.cc:1417-1446) for hypotheses a (the scored one) and b of the same 2D
-// segment.  Decisions are taken on the float quantities the reference compares; acos/exp are
-// evaluated in double and rounded to float (glibc's expf/acos differ from that by < 1 float ulp).
-// Decision form (k_support): "similarityForScoring > L3D_DEF_MIN_SIMILARITY_3D" without transcendentals.
-// sim = fmin(sim_a, fmin(e1, e2)) > 0.5 <=> every non-NaN component is > 0.5 (fmin skips NaNs; all NaN -> false).
-// expf and acos are monotone, so each component test is a comparison of its float argument with a threshold
-// the host found by bisection with the libm the reference itself would use (sim_thresholds, l3d_api.hip):
-//     expf(y) > 0.5f                      <=>  y > y_thr
-//     expf(-angle(x)^2 / two_sigA_sqr) > 0.5f  <=>  x >= x_hi || x <= x_lo     (x = clamped float dot product)
-__device__ __forceinline__ bool sim_decide(const d3 dira, bool zeroa, float adp1, float adp2, float reg1, float reg2,
-                                           const d3 dirb, bool zerob, float bdp1, float bdp2, const SimConst sc) {
-    if (zeroa || zerob) return false;
-    const float d1 = adp1 - bdp1, d2 = adp2 - bdp2;
-    // division-free early-out with a safety margin: d*d > 0.72*reg => y < -0.70 < y_thr even after rounding;
-    // NaN/inf fall through to the exact comparison
-    if (d1 * d1 > 0.72f * reg1 || d2 * d2 > 0.72f * reg2) return false;
-    const float y1 = -d1 * d1 / reg1, y2 = -d2 * d2 / reg2;
-    // NaN components drop out of the fmin chain; the angular component is never NaN (x is clamped, sigma_a > 0)
-    if (y1 == y1 && !(y1 > sc.y_thr)) return false;
-    if (y2 == y2 && !(y2 > sc.y_thr)) return false;
-    const float dot_p = (float)dot(dira, dirb);
-    const float x = fmaxf(fminf(dot_p, 1.0f), -1.0f);
-    return x >= sc.x_hi || x <= sc.x_lo;
-}
-
-// Value form (k_score_all), for pairs sim_decide accepted: similarityForScoring (line3D.cc:1417-1446) without the
-// final threshold.  acos/exp are evaluated in double and rounded to float (glibc's expf/acos differ from that by
-// < 1 float ulp).
-__device__ __forceinline__ float sim_value(const d3 dira, float adp1, float adp2, float reg1, float reg2,
-                                           const d3 dirb, float bdp1, float bdp2, const SimConst sc) {
-    const float d1 = adp1 - bdp1, d2 = adp2 - bdp2;
-    const float y1 = -d1 * d1 / reg1, y2 = -d2 * d2 / reg2;
-    const float dot_p = (float)dot(dira, dirb);
-    float angle = (float)(acos((double)fmaxf(fminf(dot_p, 1.0f), -1.0f)) / M_PI * 180.0f);
-    if (angle > 90.0f) angle = 180.0f - angle;
-    const float ya = -angle * angle / sc.two_sigA_sqr;
-    // fmin(expf(ya), fmin(expf(y1), expf(y2))) == expf(fmin(ya, fmin(y1, y2))): expf is monotone and fmin skips
-    // NaNs on both sides alike -- one exponential instead of three
-    return (float)exp((double)fminf(ya, fminf(y1, y2)));
-}
+// similarityForScoring (line3D.cc:1417-1446): sim_decide / sim_value of l3d_dev.h.  The kernels here take the
+// division-free early-out sim_far in front of sim_decide.
 
 // ---- support bitsets (batched), presence propagation (the chain), scores (batched) ---------------------
 // For hypothesis i of a segment with L potential hypotheses, S_i = { j : cam(j) != cam(i) and
@@ -153,8 +115,8 @@ __device__ __forceinline__ float sim_value(const d3 dira, float adp1, float adp2
 
 
 // The similarity decisions of the hypotheses of one 2D segment (any view) -> support bitset rows.
-// similarityForScoring(i, j) can only exceed 0.5 if |dp1_i - dp1_j| <= sqrt(0.72 * reg1_i) (first early-out of
-// sim_decide), so the hypotheses are rank-sorted by dp1 in LDS and hypothesis i evaluates only the contiguous
+// similarityForScoring(i, j) can only exceed 0.5 if |dp1_i - dp1_j| <= sqrt(0.72 * reg1_i) (the early-out
+// sim_far), so the hypotheses are rank-sorted by dp1 in LDS and hypothesis i evaluates only the contiguous
 // window of candidates inside that radius (found by binary search) instead of all L: O(L^2) cheap compares for
 // the sort + O(L * window) evaluations.  Everything the decision reads is staged in LDS IN SORTED ORDER (the
 // window walk reads consecutive positions: no dependent index load), directions as fp32 -- the angular test is
@@ -166,7 +128,6 @@ __device__ __forceinline__ float sim_value(const d3 dira, float adp1, float adp2
 //            __syncthreads instead of wave barriers
 constexpr uint32_t kStageCap = 192;
 constexpr uint32_t kPoolFloats = 1632;                    // per-wave LDS pool: 8.5 floats per staged hypothesis
-constexpr float kDirSlack = 2e-6f;
 // capacities of a group of wpl waves: staged lists, and lists whose sort keys alone fit (3.5 floats per entry)
 __host__ __device__ constexpr uint32_t support_stage_cap(uint32_t wpl) { return kStageCap * wpl; }
 __host__ __device__ constexpr uint32_t support_sort_cap(uint32_t wpl) { return (kPoolFloats * wpl * 2 / 7) & ~1u; }
@@ -259,7 +220,7 @@ void k_support(uint32_t G, const uint32_t* __restrict__ off, const uint32_t* __r
                 const float a_dp1 = s_sorted[p0], a_dp2 = s_dp2[p0];
                 const uint32_t a_tvf = s_tvf[p0];
                 const float adx = s_dir[3 * p0], ady = s_dir[3 * p0 + 1], adz = s_dir[3 * p0 + 2];
-                float r = sqrtf(0.72f * a_reg1) * 1.0001f + 1e-30f;   // padded against float rounding
+                float r = support_radius(a_reg1);
                 if (!(r < 1e30f)) r = __builtin_inff();               // NaN / huge: the whole list is the window
                 const float kl = a_dp1 - r, kh = a_dp1 + r;
                 uint64_t rw[kRowRegs] = {};
@@ -270,15 +231,16 @@ void k_support(uint32_t G, const uint32_t* __restrict__ off, const uint32_t* __r
                     if (((tvf ^ a_tvf) & 0x7FFFFFFFu) == 0 || ((tvf | a_tvf) >> 31)) return;   // same camera / zero length
                     const float odp1 = s_sorted[p], odp2 = s_dp2[p];
                     const float d1 = a_dp1 - odp1, d2 = a_dp2 - odp2;
-                    if (d1 * d1 > 0.72f * a_reg1 || d2 * d2 > 0.72f * a_reg2) return;   // see sim_decide
+                    if (sim_far(d1, d2, a_reg1, a_reg2)) return;
                     const float y1 = -d1 * d1 / a_reg1, y2 = -d2 * d2 / a_reg2;
                     if (y1 == y1 && !(y1 > sc.y_thr)) return;
                     if (y2 == y2 && !(y2 > sc.y_thr)) return;
                     // angular part: fp32 dot product, exact fp64 redo when it is near a threshold
                     const float xf = fmaxf(fminf(adx * s_dir[3 * p] + ady * s_dir[3 * p + 1] + adz * s_dir[3 * p + 2], 1.0f), -1.0f);
+                    const int ok32 = dir_decide32(xf, sc);
                     bool ok;
-                    if (fabsf(xf - sc.x_hi) > kDirSlack && fabsf(xf - sc.x_lo) > kDirSlack) {
-                        ok = xf >= sc.x_hi || xf <= sc.x_lo;
+                    if (ok32 >= 0) {
+                        ok = ok32 != 0;
                     } else {
                         const float dot_p = (float)dot(entry_dir(v.C, sx, a_dp1, a_dp2), entry_dir(v.C, sx, odp1, odp2));
                         const float x = fmaxf(fminf(dot_p, 1.0f), -1.0f);
@@ -307,7 +269,7 @@ void k_support(uint32_t G, const uint32_t* __restrict__ off, const uint32_t* __r
             const DEntry a = dents[b + i];
             const d3 ad = entry_dir(v.C, sx, a.dp1, a.dp2);
             const bool azero = (a.flags & kDZeroLen) != 0;
-            float r = sqrtf(0.72f * a.reg1) * 1.0001f + 1e-30f;
+            const float r = support_radius(a.reg1);
             uint32_t lo = 0, hi = L;
             if (r < 1e30f) {   // also false for NaN: then the whole list is the window
                 const float kl = a.dp1 - r, kh = a.dp1 + r;
@@ -323,7 +285,8 @@ void k_support(uint32_t G, const uint32_t* __restrict__ off, const uint32_t* __r
                 const uint32_t j = s_sidx[p];
                 const DEntry& o = dents[b + j];
                 if (o.tgt_view == a.tgt_view) continue;
-                if (sim_decide(ad, azero, a.dp1, a.dp2, a.reg1, a.reg2, entry_dir(v.C, sx, o.dp1, o.dp2),
+                if (!sim_far(a.dp1 - o.dp1, a.dp2 - o.dp2, a.reg1, a.reg2) &&
+                    sim_decide(ad, azero, a.dp1, a.dp2, a.reg1, a.reg2, entry_dir(v.C, sx, o.dp1, o.dp2),
                                (o.flags & kDZeroLen) != 0, o.dp1, o.dp2, sc))
                     rows[(size_t)i * W + (j >> 6)] |= 1ull << (j & 63);
             }
@@ -340,6 +303,7 @@ void k_support(uint32_t G, const uint32_t* __restrict__ off, const uint32_t* __r
             for (uint32_t jj = 0; jj < jn; ++jj) {
                 const DEntry& o = dents[b + w * 64 + jj];
                 if (o.tgt_view == a.tgt_view) continue;
+                if (sim_far(a.dp1 - o.dp1, a.dp2 - o.dp2, a.reg1, a.reg2)) continue;
                 word |= (uint64_t)sim_decide(ad, (a.flags & kDZeroLen) != 0, a.dp1, a.dp2, a.reg1, a.reg2,
                                              entry_dir(v.C, sx, o.dp1, o.dp2), (o.flags & kDZeroLen) != 0, o.dp1,
                                              o.dp2, sc) << jj;

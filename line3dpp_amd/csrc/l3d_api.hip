@@ -196,38 +196,6 @@ void orientation_thresholds(double& lo, double& hi) {
     lo = y;
 }
 
-// Thresholds of the decision form of similarityForScoring (k_views.hip sim_decide): the smallest/largest float
-// arguments for which the reference's own expressions (libm expf / acos as line3D.cc:1428,1438,1575 call them)
-// exceed L3D_DEF_MIN_SIMILARITY_3D.  Every expression is monotone in its argument, so bisection over floats
-// finds the exact switch points.
-template <class Pred>
-float first_true(float lo, float hi, Pred pred) {   // pred(lo) false, pred(hi) true, monotone; returns first true
-    for (int it = 0; it < 300; ++it) {
-        const float mid = lo + 0.5f * (hi - lo);
-        if (!(mid > lo && mid < hi)) break;
-        if (pred(mid)) hi = mid; else lo = mid;
-    }
-    return hi;
-}
-SimConst sim_thresholds(float two_sigA_sqr) {
-    SimConst sc;
-    sc.two_sigA_sqr = two_sigA_sqr;
-    const float min_sim = 0.5f;   // L3D_DEF_MIN_SIMILARITY_3D
-    auto pe = [&](float y) { return expf(y) > min_sim; };
-    // y_thr = largest y that fails
-    const float first = first_true(-2.0f, 0.0f, pe);
-    sc.y_thr = std::nextafterf(first, -INFINITY);
-    auto pa = [&](float x) {   // angleBetweenSeg3D(.., undirected) + sim_a, line3D.cc:1571-1583, 1428
-        float angle = (float)(std::acos(std::fmax(std::fmin((double)x, 1.0), -1.0)) / M_PI * 180.0f);
-        if (angle > 90.0f) angle = 180.0f - angle;
-        return expf(-angle * angle / two_sigA_sqr) > min_sim;
-    };
-    if (pa(0.0f)) { sc.x_hi = 0.0f; sc.x_lo = 0.0f; return sc; }   // every direction passes
-    sc.x_hi = first_true(0.0f, 1.0f, pa);
-    sc.x_lo = -first_true(0.0f, 1.0f, [&](float m) { return pa(-m); });
-    return sc;
-}
-
 HostTrace g_trace;   // (l3d_ctx.h)
 
 // ---- process-wide cache of released blocks (l3d_host.h) ----

@@ -101,7 +101,6 @@ struct Translated {
 void make_cull(const double F[9], double ws, double hs, double wt, double ht, PairCull& pc);
 void pair_baseline(const d3& Cs, const d3& Ct, PairDesc& pd);
 void orientation_thresholds(double& lo, double& hi);
-SimConst sim_thresholds(float two_sigA_sqr);
 // L3D_TRACE=1: host-side wall-clock checkpoints of matchImages on stderr (diagnostics)
 struct HostTrace {
     bool on = std::getenv("L3D_TRACE") != nullptr;

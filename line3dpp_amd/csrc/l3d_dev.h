@@ -258,6 +258,105 @@ L3D_HD float sim_affinity(const HypRec& h1, const HypRec& h2, float k1, float md
     return expf_ref(fminf(y_a, fminf(y_p1, y_p2)));
 }
 
+// ---- the scoring similarity (k_lists.hip, k_views.hip; host and device: pinned on the CPU by tests/cpp/sim_scoring.cpp) ----
+// similarityForScoring (line3D.cc:1417-1446) for hypotheses a (the scored one) and b of the same 2D segment.
+// Decision form: "similarityForScoring > L3D_DEF_MIN_SIMILARITY_3D" without transcendentals.
+// sim = fmin(sim_a, fmin(e1, e2)) > 0.5 <=> every non-NaN component is > 0.5 (fmin skips NaNs; all NaN -> false).
+// expf and acos are monotone, so each component test is a comparison of its float argument with a threshold the host
+// found by bisection with the libm the reference itself would use (sim_thresholds below):
+//     expf(y) > 0.5f                           <=>  y > y_thr
+//     expf(-angle(x)^2 / two_sigA_sqr) > 0.5f  <=>  x >= x_hi || x <= x_lo     (x = clamped float dot product)
+L3D_HD bool sim_decide(const d3 dira, bool zeroa, float adp1, float adp2, float reg1, float reg2,
+                       const d3 dirb, bool zerob, float bdp1, float bdp2, const SimConst sc) {
+    if (zeroa || zerob) return false;
+    const float d1 = adp1 - bdp1, d2 = adp2 - bdp2;
+    const float y1 = -d1 * d1 / reg1, y2 = -d2 * d2 / reg2;
+    // NaN components drop out of the fmin chain; the angular component is never NaN (x is clamped, sigma_a > 0)
+    if (y1 == y1 && !(y1 > sc.y_thr)) return false;
+    if (y2 == y2 && !(y2 > sc.y_thr)) return false;
+    const float dot_p = (float)dot(dira, dirb);
+    const float x = fmaxf(fminf(dot_p, 1.0f), -1.0f);
+    return x >= sc.x_hi || x <= sc.x_lo;
+}
+
+// Division-free early-out of k_views.hip, taken in front of sim_decide where a call site wants it (k_lists.hip does not):
+// d*d > 0.72*reg => y < -0.70 < y_thr even after rounding, so sim_decide would say no; NaN/inf compare false and go on
+// to the exact comparison.
+L3D_HD bool sim_far(float d1, float d2, float reg1, float reg2) {
+    return d1 * d1 > 0.72f * reg1 || d2 * d2 > 0.72f * reg2;
+}
+
+// Value form, for pairs sim_decide accepted: similarityForScoring without the final threshold.  acos/exp are evaluated
+// in double and rounded to float (glibc's expf/acos differ from that by < 1 float ulp).  fmin(expf(ya), fmin(expf(y1),
+// expf(y2))) == expf(fmin(ya, fmin(y1, y2))): expf is monotone and fmin skips NaNs on both sides alike -- one exponential
+// instead of three.
+L3D_HD float sim_value(const d3 dira, float adp1, float adp2, float reg1, float reg2,
+                       const d3 dirb, float bdp1, float bdp2, const SimConst sc) {
+    const float d1 = adp1 - bdp1, d2 = adp2 - bdp2;
+    const float y1 = -d1 * d1 / reg1, y2 = -d2 * d2 / reg2;
+    const float dot_p = (float)dot(dira, dirb);
+    float angle = (float)(acos((double)fmaxf(fminf(dot_p, 1.0f), -1.0f)) / M_PI * 180.0f);
+    if (angle > 90.0f) angle = 180.0f - angle;
+    const float ya = -angle * angle / sc.two_sigA_sqr;
+    return (float)exp((double)fminf(ya, fminf(y1, y2)));
+}
+
+// Conservative squared depth windows of hypothesis i, from slot data alone (k_lists.hip): similarityForScoring(i, .) > 0.5
+// needs d^2 < 0.6932 * reg (expf(-d^2/reg) > 0.5), and reg = (dp k)^2 + (|P - C_t| k_t)^2 with |P - C_t| <= dp + |C - C_t|
+// (P = C + ray * dp, unit ray): no unprojection is needed to bound it.  0.72 * 1.001 covers every float rounding.
+L3D_HD float window_sq(float dp, float k, float kt, float cc_dist) {
+    const float a = dp * k, b = (dp + cc_dist) * kt;
+    const float r = 0.72f * 1.001f * (a * a + b * b) + 1e-37f;
+    return (r < 1e30f) ? r : __builtin_inff();     // NaN / huge: the whole list is the window
+}
+// The depth radius of k_support's candidate window (k_views.hip): |dp1_i - dp1_j| <= sqrt(0.72 * reg1_i) is what sim_far
+// lets through, padded against the float rounding of the root and of dp1 -+ r.  NaN or beyond 1e30: the caller takes the
+// whole list as the window.
+L3D_HD float support_radius(float reg1) { return sqrtf(0.72f * reg1) * 1.0001f + 1e-30f; }
+
+// The angular part of the decision from directions rounded to float (k_support's staged lists): xf is the clamped fp32
+// dot product of the two float directions.  Certain when xf is more than kDirSlack away from both thresholds: then the
+// fp64 decision is the same.  Otherwise the caller recomputes the directions in fp64 and decides on those.
+// Both come from the same fp64 directions, so |xf - x| is the rounding of six unit-vector components and of one float dot
+// product: the largest that tests/cpp/sim_scoring.cpp measures, over 5.8 million unprojections next to a threshold with
+// depths, camera centres and baselines across six orders of magnitude, is 1.788e-7 (3 ulp of 1), against a slack of 2e-6.
+constexpr float kDirSlack = 2e-6f;
+L3D_HD int dir_decide32(float xf, const SimConst sc) {   // 1 / 0: certain, the decision; -1: not certain
+    if (fabsf(xf - sc.x_hi) > kDirSlack && fabsf(xf - sc.x_lo) > kDirSlack) return (xf >= sc.x_hi || xf <= sc.x_lo) ? 1 : 0;
+    return -1;
+}
+
+// Thresholds of the decision form: the smallest/largest float arguments for which the reference's own expressions (libm
+// expf / acos as line3D.cc:1428,1438,1575 call them) exceed L3D_DEF_MIN_SIMILARITY_3D.  Every expression is monotone in
+// its argument, so bisection over floats finds the exact switch points.  Host only.
+template <class Pred>
+inline float first_true(float lo, float hi, Pred pred) {   // pred(lo) false, pred(hi) true, monotone; returns first true
+    for (int it = 0; it < 300; ++it) {
+        const float mid = lo + 0.5f * (hi - lo);
+        if (!(mid > lo && mid < hi)) break;
+        if (pred(mid)) hi = mid; else lo = mid;
+    }
+    return hi;
+}
+inline SimConst sim_thresholds(float two_sigA_sqr) {
+    SimConst sc;
+    sc.two_sigA_sqr = two_sigA_sqr;
+    const float min_sim = 0.5f;   // L3D_DEF_MIN_SIMILARITY_3D
+    auto pe = [&](float y) { return expf(y) > min_sim; };
+    // y_thr = largest y that fails
+    const float first = first_true(-2.0f, 0.0f, pe);
+    sc.y_thr = nextafterf(first, -INFINITY);
+    auto pa = [&](float x) {   // angleBetweenSeg3D(.., undirected) + sim_a, line3D.cc:1571-1583, 1428
+        float angle = (float)(acos(fmax(fmin((double)x, 1.0), -1.0)) / M_PI * 180.0f);
+        if (angle > 90.0f) angle = 180.0f - angle;
+        return expf(-angle * angle / two_sigA_sqr) > min_sim;
+    };
+    if (pa(0.0f)) { sc.x_hi = 0.0f; sc.x_lo = 0.0f; return sc; }   // every direction passes
+    sc.x_hi = first_true(0.0f, 1.0f, pa);
+    sc.x_lo = -first_true(0.0f, 1.0f, [&](float m) { return pa(-m); });
+    return sc;
+}
+
 
 // ---- the exact pair test (reference CPU semantics) -----------------------------------------
 

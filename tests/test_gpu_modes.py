@@ -57,14 +57,22 @@ def _assert_same(g, o, sc):
 @pytest.mark.parametrize("params", [dict(epi_overlap=-1.7, sigma_a=-200.0, num_neighbors=0),
                                     dict(sigma_p=-0.05), dict(sigma_p=-0.05, const_reg_depth=20.0),
                                     dict(sigma_a=5.0, sigma_p=1.0), dict(kNN=3, epi_overlap=0.5),
-                                    dict(sigma_p=0.01)])
+                                    dict(sigma_p=0.01),
+                                    dict(sigma_a=0.5), dict(sigma_a=80.0), dict(sigma_a=76.45)])
 def test_parameter_modes_through_the_hip_path(params):
+    """sigma_a = 0.5 puts the angular thresholds of the scoring similarity at 0.59 degrees; 76.45 and 80 are past the
+    switch (76.44) to thresholds of x_hi = x_lo = 0, where every direction passes.  k_lists, k_cand_exact and k_edges of
+    this path cannot be fed hand-built hypotheses, so that they decide right AT a threshold rests on the host pin of the
+    function they share with the seam's kernels (tests/cpp/sim_scoring.cpp, l3d_dev.h: sim_decide) and on the seam's
+    threshold lists (tests/test_gpu_seam.py); here the whole result has to equal the reference's at these settings."""
     sc = make_scene(7, 260, n_neighbors=4, seed=11)
     g = _gpu(sc)
     assert g.matchImages(**_g(params)) and g.computeAffinity()
     r = _assert_same(g, _ref(sc, [params]), sc)
     assert r["surviving"] > 0 or params.get("epi_overlap", 0) < 0 or params.get("sigma_p") == 0.01   # overlap > 0.99 /
     # a 0.1 px regulariser leave next to nothing
+    if params.get("sigma_a", 0) > 76:
+        assert r["surviving"] > 0
 
 
 def test_second_match_images_with_other_parameters():

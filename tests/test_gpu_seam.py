@@ -35,7 +35,7 @@ def _score_and_compare(case):
     from line3dpp_amd.api import score_matches
     want, _, centre = case.reference()
     before = _counters()
-    got = score_matches(case.segs, case.matches4, case.ranges2, case.reg_tgt2, case.RtKinv, centre, S.TWO_SIGA_SQR, case.k)
+    got = score_matches(case.segs, case.matches4, case.ranges2, case.reg_tgt2, case.RtKinv, centre, case.two_sigA_sqr, case.k)
     after = _counters()
     assert got.shape == want.shape and not np.isnan(got).any()
     flipped = np.nonzero((got > 0) != (want > 0))[0]
@@ -76,6 +76,35 @@ def test_score_matches_with_zero_regularisers_drops_the_nan_terms():
     drops the NaN as the reference's does (exact duplicates score through the angular term alone)"""
     got, want = _score_and_compare(S.score_nan_case())
     assert (want > 0).sum() > 100 and (want == 0).sum() > 1000
+
+
+@pytest.mark.parametrize("sigma_a", [0.5, 80.0])
+def test_score_matches_in_every_tier_at_other_sigma_a(sigma_a):
+    """The tier lists and the k = 0 lists again at sigma_a = 0.5 (angular thresholds at 0.59 degrees: many pairs inside the
+    fp32 slack) and at sigma_a = 80 (the x_hi == 0 form of the thresholds: every direction passes).
+    tests/test_seam_host.py shows that both still decide both ways in every length class."""
+    got, want = _score_and_compare(S.score_tier_case(sigma_a=sigma_a))
+    assert len(got) == sum(S.SCORE_LENGTHS) * S.LISTS_PER_LENGTH
+    got, want = _score_and_compare(S.score_nan_case(sigma_a=sigma_a))
+    assert (want > 0).sum() > 100 and (want == 0).sum() > 1000
+
+
+@pytest.mark.parametrize("sigma_a", [10.0, 1.0])
+@pytest.mark.parametrize("tier", S.THRESHOLD_TIERS)
+def test_score_matches_at_the_thresholds_of_the_similarity(tier, sigma_a):
+    """Lists of couples forced to within a few float steps of the thresholds of `similarityForScoring(i, j) > 0.5`
+    (tests/seam_cases.py: score_threshold_case), in every tier of k_support: -d^2 / reg at y_thr - 3 ... + 3 ulp in either
+    depth, and the direction at every float step of dp2 from 24 below to 24 above the step at which the oracle's angular
+    decision flips, half of them inside kDirSlack of the threshold (the fp64 redo of the staged tiers) and half beyond it
+    (the fp32 decision).  Every anchor's score is one decision and one similarity: a `>=` for a `>`, a slack that is too
+    small or a window that loses its last neighbour flips one of them.  tests/test_seam_host.py shows from the oracle alone
+    that the couples flip exactly where they were forced to.  k_lists, k_cand_exact and k_edges of the main path cannot be
+    fed hand-built hypotheses: their behaviour at the thresholds rests on the host pin of the function they share with
+    these kernels (tests/cpp/sim_scoring.cpp)."""
+    case = S.score_threshold_case(tier, sigma_a)
+    got, want = _score_and_compare(case)
+    anchors = case.marks["role"] == "A"
+    assert (want[anchors] > 0).sum() >= 24 and (want[anchors] == 0).sum() >= 24
 
 
 def test_score_matches_single_list_single_segment():

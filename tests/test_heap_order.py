@@ -70,3 +70,24 @@ def test_affinity_similarity_form_and_symmetry(tmp_path):
     assert out.returncode == 0, out.stdout
     assert "identical, 0 mismatches" in out.stdout and "symmetric, 0 asymmetric" in out.stdout
     assert "an arm was not reached" not in out.stdout
+
+
+def test_scoring_similarity_at_its_thresholds(tmp_path):
+    """l3d_dev.h: sim_decide / sim_far / sim_value / window_sq / support_radius / dir_decide32 / sim_thresholds (the
+    decision of phase B, `similarityForScoring(i, j) > 0.5`, taken as comparisons with bisected thresholds inside padded
+    depth windows, the angle in fp32 away from its thresholds) against a literal restatement of line3D.cc:1417-1446 and
+    :1571-1583 with libm's expf, acos and fmin.  Every float within 2^16 ulp of y_thr, x_hi, x_lo, 0 and +-1 for nine
+    sigma_a on both sides of the switch to the x_hi == 0 form (no flip back: the bisection's monotonicity); 6 million tuples
+    forced to within 3 ulp of a threshold in any component, with NaN, -inf, denormal, infinite and overflowing terms, zero
+    lengths and clamped dot products; the early-out over every float exponent of reg; the windows against the farthest
+    depth the reference accepts; the fp32 angle on unprojected directions within 1e-5 of a threshold; the value within one
+    ulp.  The pin prints the three measured numbers: the largest |xf - x|, the smallest window ratio, the one-ulp count."""
+    exe = str(tmp_path / "sim_scoring")
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-I/opt/rocm/include", "-D__HIP_PLATFORM_AMD__",
+                           os.path.join(ROOT, "tests", "cpp", "sim_scoring.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True)
+    print(out.stdout)
+    assert out.returncode == 0, out.stdout
+    assert "identical, 0 mismatches" in out.stdout
+    assert "an arm was not reached" not in out.stdout and "not reached" not in out.stdout
+    assert "0 outside" in out.stdout and "0 of those wrong" in out.stdout and "0 accepted by the reference" in out.stdout

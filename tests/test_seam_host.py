@@ -73,6 +73,88 @@ def test_score_tier_case_decides_both_ways_in_every_class():
 LISTS_TOTAL = sum(S.SCORE_LENGTHS) * S.LISTS_PER_LENGTH
 
 
+@pytest.mark.parametrize("sigma_a", [0.5, 80.0])
+def test_score_tier_case_decides_both_ways_at_other_sigma_a(sigma_a):
+    """The tier lists and the k = 0 lists scored at sigma_a = 0.5 (an angular threshold of 0.59 degrees) and at sigma_a = 80
+    (x_hi == 0: every direction passes) still decide both ways in every length class from 64 up, as at the default."""
+    c = S.score_tier_case(sigma_a=sigma_a)
+    assert c.two_sigA_sqr == 2.0 * sigma_a * sigma_a and c is not S.score_tier_case()
+    want, _, _ = c.reference()
+    default, _, _ = S.score_tier_case().reference()
+    assert not np.isnan(want).any()
+    for L in S.SCORE_LENGTHS:
+        if L >= 64:
+            frac = float((want[c.length_of == L] > 0).mean())
+            print(f"sigma_a {sigma_a}: length {L}: {frac:.3f} positive")
+            assert 0.10 <= frac <= 0.90, (L, frac)
+    # the narrow angle takes supporters away; the wide one changes nothing the default's 8.3 degrees had not accepted already
+    changed = int(((want > 0) != (default > 0)).sum())
+    print(f"sigma_a {sigma_a}: {changed} decisions differ from sigma_a = 10")
+    assert (changed > 100) if sigma_a < 1 else ((want > 0) >= (default > 0)).all()
+    w, _, _ = S.score_nan_case(sigma_a=sigma_a).reference()
+    assert not np.isnan(w).any() and (w > 0).sum() > 100 and (w == 0).sum() > 1000
+
+
+@pytest.mark.parametrize("sigma_a", [10.0, 1.0])
+@pytest.mark.parametrize("tier", S.THRESHOLD_TIERS)
+def test_threshold_couples_flip_where_they_were_forced_to(tier, sigma_a):
+    """What makes a pass of the GPU threshold test mean something, from the generator and the oracle alone: every anchor's
+    score is ONE decision (nothing but its supporter within ten window radii), and the oracle flips exactly at the forced
+    step -- y_thr + n ulp scores for n = 1, 2, 3 and not for n = -3 ... 0, the angular couples score up to the step before
+    s* and not from s* on -- with at least ANCHORS_PER_STEP anchors at every n of the y1 and of the y2 set, and at least 6
+    accepted and 6 rejected angular anchors inside kDirSlack of the flip and as many between one and two kDirSlack."""
+    c = S.score_threshold_case(tier, sigma_a)
+    want, _, _ = c.reference()
+    mk, dp1, cam = c.marks, c.matches4[:, 2], c.matches4[:, 1]
+    assert (c.lengths == tier).all() and len(want) == tier * len(c.lengths) and not np.isnan(want).any()
+    A = mk["role"] == "A"
+    # isolation, in the kernel's own float operations
+    reg1 = S.kernel_reg(dp1, c.k, c.reg_tgt2[:, 0])
+    radius = np.sqrt(np.float32(0.72) * reg1) * np.float32(1.0001)
+    closest = np.inf
+    for i in np.nonzero(mk["couple"] >= 0)[0]:
+        if mk["kind"][i] == "fill":
+            continue
+        others = (c.list_of == c.list_of[i]) & (mk["couple"] != mk["couple"][i])
+        closest = min(closest, float(np.abs(dp1[others] - dp1[i]).min() / radius[i]))
+        mate = (c.list_of == c.list_of[i]) & (mk["couple"] == mk["couple"][i]) & (mk["role"] != mk["role"][i]) & (mk["role"] != "")
+        assert mate.sum() == 1 and cam[mate][0] != cam[i]
+        if mk["kind"][i] == "y1fill" and mk["role"][i] == "A":     # the walk from A to B steps over A's own camera
+            own = (c.list_of == c.list_of[i]) & (mk["kind"] == "fill") & (mk["couple"] == mk["couple"][i])
+            assert own.sum() == 6 and (cam[own] == cam[i]).all()
+            assert ((dp1[own] > dp1[i]) & (dp1[own] < dp1[mate][0])).all()
+    print(f"tier {tier}, sigma_a {sigma_a}: the nearest stranger of a couple member is {closest:.1f} window radii away")
+    assert closest >= 10.0
+    assert not want[mk["kind"] == "pad"].any()
+    for s in range(len(c.lengths)):                                 # the ends of the sorted walk and the rank tie
+        m = c.list_of == s
+        assert mk["couple"][m][dp1[m].argmin()] >= 0 and mk["kind"][m][dp1[m].argmax()] == "top"
+    for kind in ("y2", "angular"):
+        i = np.nonzero(A & (mk["kind"] == kind))[0]
+        assert all(dp1[(mk["couple"] == mk["couple"][j]) & (mk["role"] == "B")][0] == dp1[j] for j in i)
+    # the oracle flips at the forced step
+    for kind in ("y1", "y2", "y1fill", "top"):
+        m = A & (mk["kind"] == kind)
+        if sigma_a < 5 and kind != "top":
+            assert not m.any()
+            continue
+        assert np.array_equal(want[m] > 0, mk["n"][m] > 0), kind
+        counts = {n: int((m & (mk["n"] == n)).sum()) for n in S.Y_STEPS}
+        print(f"  {kind}: anchors per n {counts}")
+        if kind in ("y1", "y2"):
+            assert min(counts.values()) >= S.ANCHORS_PER_STEP
+        elif kind == "y1fill":
+            assert min(counts.values()) >= 1
+    assert (want[A & (mk["kind"] == "top")] > 0).any() or sigma_a < 5
+    m = A & (mk["kind"] == "angular")
+    assert sorted(mk["n"][m].tolist()) == list(S.ANGULAR_STEPS)
+    assert np.array_equal(want[m] > 0, mk["n"][m] < 0)
+    for band in (1, 2):
+        acc = int((m & (mk["band"] == band) & (want > 0)).sum()); rej = int((m & (mk["band"] == band) & (want == 0)).sum())
+        print(f"  angular, band {band} ({'inside kDirSlack' if band == 1 else 'between one and two kDirSlack'}): {acc} accepted, {rej} rejected")
+        assert acc >= 6 and rej >= 6
+
+
 # ---- host-side argument checks: nothing below launches a kernel or needs a device ---------------------------------------
 def _score_raw(c, m4=None, ranges=None):
     L = _lib.load()
