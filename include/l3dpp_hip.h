@@ -757,6 +757,43 @@ typedef struct l3d_keep_rows {
 } l3d_keep_rows;
 int l3d_debug_keep_rows(l3d_ctx*, int query_only, l3d_keep_rows* out);
 
+/* Test hook (host only, no device, no context): the epipolar-band culling set-up of one directed pair as
+ * l3d_match_begin computes it -- the very function it calls.  F: the pair's fundamental matrix, row-major; ws x hs, wt x ht:
+ * the source and the target image.  enabled == 0: the pair is refused and streams unculled (the forms are zero then). */
+typedef struct l3d_cull_forms_info {
+    uint32_t enabled, reserved;
+    double As[3], Bs[3];              /* tau of the epipolar line of a source point p: (As.p) / (Bs.p) */
+    double At[3], Bt[3];              /* tau of a target point q: (At.q) / (Bt.q) */
+} l3d_cull_forms_info;
+int l3d_cull_forms(const double F[9], double ws, double hs, double wt, double ht, l3d_cull_forms_info* out);
+
+/* Test hook (device, read only): the tables k_cull_prepare left behind for one directed pair of the LAST launch of
+ * l3d_match_pairs, copied out as they lie -- stream synchronisation and device-to-host copies only: no kernel, nothing
+ * written on the device, nothing the match kernels read is changed.  The pools belong to the context and are sized by
+ * l3d_match_begin; every launch of l3d_match_pairs that culls writes the regions of ITS pairs anew, and nothing after it
+ * does (phase B reads the slots only).  The hook answers between that launch and l3d_match_finish / l3d_match_abort, for a
+ * pair of that launch; L3D_ERR_STATE otherwise.  Two-call form: query_only != 0 fills in the sizes and the forms without
+ * touching the device; then the caller points the buffers at host arrays of those sizes.  A buffer may be NULL.  A pair that
+ * was not culled -- refused by make_cull, or matched by a launch that did not cull at all (brute-force hook) -- has
+ * enabled == 0 and no tables: sizes 0, forms 0. */
+typedef struct l3d_cull_state {
+    /* out */
+    uint32_t enabled;                 /* make_cull's decision for the pair (0 as well where the launch did not cull) */
+    uint32_t layout_rows;             /* R of the padded class layout the launch laid the source rows out in: 16 (tile form),
+                                         64 (row form); 0: the unpadded layout of the keep-all passes */
+    uint32_t Ms, Mt;
+    uint32_t src_len;                 /* positions of the pair's source region: Ms, or tile_src_cap(Ms, R) */
+    uint32_t n_chunks;                /* ceil(Mt / 64) */
+    double As[3], Bs[3], At[3], Bt[3];
+    /* in: host buffers */
+    uint32_t* src_perm;               /* src_len: source row at a position, 0xFFFFFFFF = padding */
+    float* src_band;                  /* 2 src_len: (lo, hi) of that row */
+    uint32_t* tgt_perm;               /* Mt: target segment at a sorted position */
+    float* tgt_band;                  /* 2 Mt */
+    float* chunk_band;                /* 2 n_chunks: hull of every 64 consecutive targets */
+} l3d_cull_state;
+int l3d_debug_cull(l3d_ctx*, uint32_t pair, int query_only, l3d_cull_state* out);
+
 /* ---- (2) seam layer ------------------------------------------------------------------ */
 
 /* Replaces match_lines_GPU (cudawrapper.h:54-63; caller Line3D::matchingGPU line3D.cc:1040-1074)

@@ -253,6 +253,20 @@ class KeepRows(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in SIZES] + [("n_slots", C.c_uint64)] + [(n, C.c_void_p) for n in BUFFERS]
 
 
+class CullFormsInfo(C.Structure):
+    """l3d_cull_forms_info (include/l3dpp_hip.h)"""
+    _fields_ = [("enabled", C.c_uint32), ("reserved", C.c_uint32), ("As", C.c_double * 3), ("Bs", C.c_double * 3),
+                ("At", C.c_double * 3), ("Bt", C.c_double * 3)]
+
+
+class CullState(C.Structure):
+    """l3d_cull_state (include/l3dpp_hip.h): sizes and forms out, host buffers in"""
+    SIZES = ("enabled", "layout_rows", "Ms", "Mt", "src_len", "n_chunks")
+    FORMS = ("As", "Bs", "At", "Bt")
+    BUFFERS = ("src_perm", "src_band", "tgt_perm", "tgt_band", "chunk_band")
+    _fields_ = [(n, C.c_uint32) for n in SIZES] + [(n, C.c_double * 3) for n in FORMS] + [(n, C.c_void_p) for n in BUFFERS]
+
+
 # l3d_dev.h: HypRec (128 bytes) as l3d_debug_affinity_records hands it out
 HYP_REC_DTYPE = np.dtype([("P1", "<f8", 3), ("P2", "<f8", 3), ("dir", "<f8", 3), ("length", "<f4"), ("valid", "<u4"),
                           ("m", MATCH_DTYPE), ("view", "<u4"), ("pad", "<u4")])
@@ -293,7 +307,7 @@ EXPORTS = [
     "l3d_project_segments", "l3d_render_line_maps", "l3d_draw_line_maps", "l3d_view_camera", "l3d_project_lines",
     "l3d_get_projected_lines", "l3d_render_lines", "l3d_draw_lines", "l3d_set_projection_budget", "l3d_selftest_scan",
     "l3d_debug_lsd_stages", "l3d_match_plan", "l3d_match_tile_rows", "l3d_debug_tail_records",
-    "l3d_debug_affinity_records", "l3d_debug_keep_rows",
+    "l3d_debug_affinity_records", "l3d_debug_keep_rows", "l3d_cull_forms", "l3d_debug_cull",
     "l3d_associate_segments", "l3d_associate_view_segments",
     "l3d_compare_segments", "l3d_compare_lines",
     "l3d_merge_segments", "l3d_merge_lines",
@@ -409,6 +423,8 @@ def load():
     L.l3d_debug_tail_records.argtypes = [vp, i32, C.POINTER(TailRecords)]
     L.l3d_debug_affinity_records.argtypes = [vp, i32, C.POINTER(AffinityRecords)]
     L.l3d_debug_keep_rows.argtypes = [vp, i32, C.POINTER(KeepRows)]
+    L.l3d_cull_forms.argtypes = [vp, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(CullFormsInfo)]
+    L.l3d_debug_cull.argtypes = [vp, u32, i32, C.POINTER(CullState)]
     L.l3d_add_view_image.argtypes = [vp, u32, C.POINTER(Image), C.POINTER(DetectOptions), vp, vp, vp, f32, vp, u32,
                                      C.POINTER(u32)]
     L.l3d_add_view_image_worldpoints.argtypes = [vp, u32, C.POINTER(Image), C.POINTER(DetectOptions), vp, vp, vp, f32,

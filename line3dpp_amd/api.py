@@ -745,6 +745,29 @@ class Line3D:
         out.update(bufs)
         return out
 
+    def cull_state(self, pair_index):
+        """l3d_debug_cull (test hook): the epipolar-band tables k_cull_prepare left for one pair of the last matchPairs launch,
+        as they lie on the device -> dict: enabled, layout_rows (16 / 64: the padded class layout, 0: unpadded), Ms, Mt,
+        src_len, n_chunks, the forms As / Bs / At / Bt, and src_perm [src_len], src_band [src_len, 2], tgt_perm [Mt],
+        tgt_band [Mt, 2], chunk_band [n_chunks, 2] (all empty for a refused pair).  None (and last_status) outside the
+        window between that launch and matchFinish / matchAbort."""
+        from ._lib import CullState
+        t = CullState()
+        if not self._check(self.L.l3d_debug_cull(self.h, int(pair_index), 1, C.byref(t)), "cull_state"):
+            return None
+        u32, f32 = np.uint32, np.float32
+        bufs = dict(src_perm=np.zeros(t.src_len, u32), src_band=np.zeros((t.src_len, 2), f32),
+                    tgt_perm=np.zeros(t.Mt if t.enabled else 0, u32), tgt_band=np.zeros((t.Mt if t.enabled else 0, 2), f32),
+                    chunk_band=np.zeros((t.n_chunks, 2), f32))
+        for k, a in bufs.items():
+            setattr(t, k, a.ctypes.data if a.size else None)
+        if not self._check(self.L.l3d_debug_cull(self.h, int(pair_index), 0, C.byref(t)), "cull_state"):
+            return None
+        out = {k: int(getattr(t, k)) for k in CullState.SIZES}
+        out.update({k: np.array(getattr(t, k)[:]) for k in CullState.FORMS})
+        out.update(bufs)
+        return out
+
     def setTimingLevel(self, level):
         """l3d_set_timing_level: 1 = the match kernel only (default), 2 = every phase timed with HIP events (profiling), 0 = none"""
         return self._check(self.L.l3d_set_timing_level(self.h, int(level)), "setTimingLevel")
@@ -753,6 +776,17 @@ class Line3D:
         t = Timings()
         self.L.l3d_get_timings(self.h, C.byref(t))
         return {f: getattr(t, f) for f, _ in Timings._fields_}
+
+
+def cull_forms(F, ws, hs, wt, ht):
+    """l3d_cull_forms (test hook, host only): the culling set-up of a directed pair as matchBegin computes it, from the
+    fundamental matrix (3 x 3) and the two image sizes -> (As, Bs, At, Bt), or None where the pair is refused"""
+    info = _lib.CullFormsInfo()
+    Fm = np.ascontiguousarray(F, np.float64).reshape(9)
+    rc = _lib.load().l3d_cull_forms(ptr(Fm), float(ws), float(hs), float(wt), float(ht), C.byref(info))
+    if rc != 0:
+        raise RuntimeError(f"l3d_cull_forms: {rc}")
+    return tuple(np.array(getattr(info, k)[:]) for k in ("As", "Bs", "At", "Bt")) if info.enabled else None
 
 
 def camera_dict(cam):

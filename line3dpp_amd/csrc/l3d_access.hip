@@ -115,6 +115,46 @@ int l3d_debug_keep_rows(l3d_ctx* c, int query_only, l3d_keep_rows* out) {
     return L3D_OK;
 }
 
+// Test hooks of the epipolar-band culling (include/l3dpp_hip.h): make_cull as l3d_match_begin calls it, and the
+// tables k_cull_prepare wrote for a pair of the last launch -- copies only, no kernel.
+int l3d_cull_forms(const double F[9], double ws, double hs, double wt, double ht, l3d_cull_forms_info* out) {
+    if (!F || !out) return fail(L3D_ERR_ARG, "null argument");
+    PairCull pc{};
+    make_cull(F, ws, hs, wt, ht, pc);
+    *out = l3d_cull_forms_info{};
+    out->enabled = pc.enabled;
+    if (pc.enabled) { std::memcpy(out->As, pc.As, 24); std::memcpy(out->Bs, pc.Bs, 24); std::memcpy(out->At, pc.At, 24); std::memcpy(out->Bt, pc.Bt, 24); }
+    return L3D_OK;
+}
+
+int l3d_debug_cull(l3d_ctx* c, uint32_t pair, int query_only, l3d_cull_state* out) {
+    if (!c || !out) return fail(L3D_ERR_ARG, "null argument");
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    const auto& cl = c->cull_launch;
+    if (c->state != l3d_ctx::BEGUN || !cl.valid || pair < cl.first || pair - cl.first >= cl.count || pair >= c->cull.size())
+        return fail(L3D_ERR_STATE, "l3d_debug_cull: not a pair of the last launch of an open call");
+    PairCull pc = c->cull[pair];
+    if (!cl.culled) pc.enabled = 0;   // (brute-force hook, or no pair of the launch suited: k_cull_prepare did not run)
+    const PairDesc& pd = c->pairs[pair];
+    out->enabled = pc.enabled; out->layout_rows = cl.layout; out->Ms = pd.Ms; out->Mt = pd.Mt;
+    out->src_len = pc.enabled ? (cl.layout ? tile_src_cap(pd.Ms, cl.layout) : pd.Ms) : 0u;
+    out->n_chunks = pc.enabled ? (pd.Mt + 63) / 64 : 0u;
+    std::memset(out->As, 0, 4 * 24);
+    if (pc.enabled) { std::memcpy(out->As, pc.As, 24); std::memcpy(out->Bs, pc.Bs, 24); std::memcpy(out->At, pc.At, 24); std::memcpy(out->Bt, pc.Bt, 24); }
+    if (query_only || !pc.enabled) return L3D_OK;
+    (void)hipSetDevice(c->device);
+    L3D_HIP_CHECK(hipStreamSynchronize(c->stream));
+    auto fetch = [](void* dst, const void* src, size_t bytes) -> hipError_t {
+        return dst && bytes ? hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) : hipSuccess;
+    };
+    L3D_HIP_CHECK(fetch(out->src_perm, c->d_src_perm.p + pc.s_off, (size_t)out->src_len * 4));
+    L3D_HIP_CHECK(fetch(out->src_band, c->d_src_band.p + pc.s_off, (size_t)out->src_len * 8));
+    L3D_HIP_CHECK(fetch(out->tgt_perm, c->d_tgt_perm.p + pc.t_off, (size_t)pd.Mt * 4));
+    L3D_HIP_CHECK(fetch(out->tgt_band, c->d_tgt_band.p + pc.t_off, (size_t)pd.Mt * 8));
+    L3D_HIP_CHECK(fetch(out->chunk_band, c->d_chunk_band.p + pc.c_off, (size_t)out->n_chunks * 8));
+    return L3D_OK;
+}
+
 int l3d_num_best(l3d_ctx* c, uint32_t* n) {
     if (!c || !n) return fail(L3D_ERR_ARG, "null argument");
     *n = c->state == l3d_ctx::MATCHED ? c->n_hyps : 0;

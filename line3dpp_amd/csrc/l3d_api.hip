@@ -686,6 +686,7 @@ static int match_begin_body(l3d_ctx* c) {
     g_trace.mark(same_scene ? "begin: pair list kept" : "begin: pair list, fundamental matrices, cull descriptors built");
     c->pair_done.assign(c->pairs.size(), 0);
     c->pair_counted.assign(c->pairs.size(), 0);
+    c->cull_launch.valid = false;
     c->ragged = false;
     c->shard_world = 0; c->lists_ready = false; c->lists_prepared = false;
     int rc = upload_views(*c);
@@ -820,6 +821,10 @@ static int run_match_kernel(l3d_ctx* c, int mode, uint32_t first, uint32_t count
         L3D_HIP_CHECK(launch_cull_prepare(c->d_views.p, c->d_pairs.p, first, count, maxM, pools, layout, c->stream));
         L3D_HIP_CHECK(launch_order_items(c->d_pairs.p, first, count, maxMt, pools, (uint32_t)n_work, c->stream));
     }
+    if (mode != 2) {   // (the streamed fill pass of the two-pass keep-all form leaves the count pass' tables as they are)
+        c->cull_launch.valid = true; c->cull_launch.first = first; c->cull_launch.count = count;
+        c->cull_launch.layout = layout; c->cull_launch.culled = pools.cull != nullptr;
+    }
     if (c->ev_on(4)) L3D_HIP_CHECK(hipEventRecord(c->ev[4], c->stream));
     const bool ix16 = plan.ix16;   // 16-bit indices in the kernel's LDS tables (top bit of a row's minpos: tie flag)
     // bounded kNN: the orientation filter of phase B is fused into the epilogue
@@ -905,8 +910,10 @@ static int keep_all_single_pass(l3d_ctx* c, uint32_t first, uint32_t count) {
     uint64_t cap = std::min<uint64_t>({c->d_slots.cap, c->d_slot_row.cap, c->d_hyp_p.cap, c->d_hyp_q.cap,
                                        c->d_inv_tgt.cap * (c->tgt16 ? 2u : 1u), (size_t)0xFFFFFFFFull});
     cap = std::min<uint64_t>(cap, guess + guess / 2);    // (a block cache may hand out far larger arrays: the grid covers `cap`)
+    const uint32_t culled_before = c->tm.culled_pairs;
     for (int attempt = 0;; ++attempt) {
-        if ((uint64_t)R * c->keep_cap * sizeof(Slot) > kKeepScratchMax || attempt > 2) { c->ragged = false; return kKeepAllTwoPass; }
+        if ((uint64_t)R * c->keep_cap * sizeof(Slot) > kKeepScratchMax || attempt > 2) { c->ragged = false; c->tm.culled_pairs = culled_before; return kKeepAllTwoPass; }
+        c->tm.culled_pairs = culled_before;   // (a repeated pass culls the same pairs again: l3d_timings counts pairs, not passes)
         L3D_HIP_CHECK(c->d_keep_rec.reserve((size_t)R * c->keep_cap));
         // (a block mark per kKeepBlock slots of at most min(rows x cap, 2^32) slots)
         const uint32_t n_blk = (uint32_t)(std::min<uint64_t>((uint64_t)R * c->keep_cap, 1ull << 32) / kKeepBlock) + 2;

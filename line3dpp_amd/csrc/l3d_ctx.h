@@ -235,6 +235,7 @@ struct l3d_ctx {
     uint64_t cull_tot[4] = {0, 0, 0, 0};            // pool sizes of the culling set-up of that list
     uint32_t layout_rows = 0;                       // padded class layout of the source pools: rows per work item (0: Ms rows per pair, legacy)
     uint32_t tile_rows = 0;                         // rows per work item of the bounded-kNN launches of this call (0: the row form; k_match.hip)
+    struct { bool valid = false, culled = false; uint32_t first = 0, count = 0, layout = 0; } cull_launch;   // the last launch of this call's l3d_match_pairs: its pairs, the layout k_cull_prepare wrote, whether it ran at all (l3d_debug_cull)
     uint64_t pairs_version = 0;                     // bumped whenever the pair list on the device changes
     struct { uint64_t version = ~0ull; uint32_t first = 0, count = 0, rows = 0; size_t items = 0; const void* dev = nullptr; } work_key;   // d_work holds the items of these pairs
     PinnedBuf<uint32_t> h_segb;

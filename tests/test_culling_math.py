@@ -8,59 +8,7 @@ import pytest
 
 from line3dpp_amd.scene import make_scene
 from oracle.oracle import Oracle
-
-
-def _fundamental(s, t):                       # Line3D::getFundamentalMatrix, line3D.cc:874-892
-    R = t.R @ s.R.T
-    tt = t.t - R @ s.t
-    T = np.array([[0, -tt[2], tt[1]], [tt[2], 0, -tt[0]], [-tt[1], tt[0], 0]])
-    return np.linalg.inv(t.K.T) @ (T @ R) @ np.linalg.inv(s.K)
-
-
-def _cull_forms(F, ws, hs, wt, ht):
-    """As, Bs, At, Bt of make_cull, or None where the host refuses to cull the pair"""
-    cols = [F[:, j] for j in range(3)]
-    e, best = None, 0.0
-    for a, b in ((0, 1), (0, 2), (1, 2)):
-        x = np.cross(cols[a], cols[b]); n = np.linalg.norm(x)
-        if n > best:
-            best, e = n, x / n
-    c = np.array([0.5 * wt, 0.5 * ht, 1.0])
-    m = np.array([e[0] - c[0] * e[2], e[1] - c[1] * e[2]])
-    if np.linalg.norm(m) < 1e-12:
-        return None
-    m /= np.linalg.norm(m)
-    n = np.array([-m[1], m[0], 0.0])
-    At, Bt = np.cross(e, c), np.cross(n, e)
-    st = Bt @ c
-    At, Bt = At / st, Bt / st
-    As, Bs = -(F.T @ c), F.T @ n
-    ss = Bs @ np.array([0.5 * ws, 0.5 * hs, 1.0])
-    As, Bs = As / ss, Bs / ss
-
-    def ok(B, w, h):                          # one sign, with margin, over the (slightly enlarged) image
-        return all(B[0] * x + B[1] * y + B[2] >= 0.1 for x in (-0.05 * w, 1.05 * w) for y in (-0.05 * h, 1.05 * h))
-    return (As, Bs, At, Bt) if ok(Bt, wt, ht) and ok(Bs, ws, hs) else None
-
-
-def _bands(forms, S, T):
-    As, Bs, At, Bt = forms
-
-    def tau(A, B, x, y):
-        return (A[0] * x + A[1] * y + A[2]) / (B[0] * x + B[1] * y + B[2])
-    S = S.astype(np.float64); T = T.astype(np.float64)
-    s1, s2 = tau(As, Bs, S[:, 0], S[:, 1]), tau(As, Bs, S[:, 2], S[:, 3])
-    slo, shi = np.minimum(s1, s2), np.maximum(s1, s2)
-    t1, t2 = tau(At, Bt, T[:, 0], T[:, 1]), tau(At, Bt, T[:, 2], T[:, 3])
-    tlo, thi = np.minimum(t1, t2), np.maximum(t1, t2)
-    # widening: the pencil line parallel to the target segment (tau of its direction), when it can lie in a wedge
-    dx, dy = T[:, 2] - T[:, 0], T[:, 3] - T[:, 1]
-    with np.errstate(divide="ignore", invalid="ignore"):
-        td = (At[0] * dx + At[1] * dy) / (Bt[0] * dx + Bt[1] * dy)
-    inside = (td >= slo.min() - 1.0) & (td <= shi.max() + 1.0)
-    tlo = np.where(inside, np.minimum(tlo, td), tlo); thi = np.where(inside, np.maximum(thi, td), thi)
-    pad = lambda v: 0.01 + 1e-6 * np.abs(v)
-    return slo - pad(slo), shi + pad(shi), tlo - pad(tlo), thi + pad(thi)
+from tests.cull_model import _bands, _cull_forms, _fundamental
 
 
 @pytest.mark.parametrize("n_views,n_segs,nn,seed,radius", [(12, 300, 4, 3, 25.0), (16, 400, 6, 11, 40.0),
