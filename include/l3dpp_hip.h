@@ -1215,6 +1215,84 @@ int l3d_wireframe_get(const l3d_wireframe*, l3d_wf_junction* junctions, l3d_wf_v
 int l3d_wireframe_save_obj(const l3d_wireframe*, const char* path);
 void l3d_wireframe_close(l3d_wireframe*);
 
+/* ---- the planes the 3D lines lie in (GPU: k_planes.hip, selection: l3d_planes.h) ------------------------------
+ * No reference counterpart.  One model as above.  Every junction of §24 -- a pair of non-parallel segments that touch,
+ * found with junction_distance, junction_extension and min_sin2 -- spans a plane hypothesis; every hypothesis is scored on
+ * the device against every segment (a segment is an inlier iff both its end points lie within max_distance of the plane;
+ * the score is the number of inliers and their length as an integer weight), and a sequential selection on the host keeps
+ * the best-supported planes that are neither spanned again by two members of an accepted plane nor share more than half
+ * their weight with one.  A segment may lie in several planes.  The model itself is not modified.  fp64, the contract of
+ * DESIGN §25. */
+typedef struct l3d_planes_params {   /* 64 bytes */
+    double max_distance;         /* model units, finite, >= 0, no default: largest distance of a member's end points from the plane */
+    double junction_distance;    /* §24's max_distance, for the hypotheses */
+    double junction_extension;   /* §24's max_extension */
+    double min_sin2;             /* in [0, 1], as in §24 */
+    double min_length;           /* model units, finite, >= 0: least support (summed member length) of a plane */
+    uint32_t min_segments;       /* >= 1: least number of member segments */
+    uint32_t max_planes;         /* >= 1 */
+    uint32_t max_tests;          /* >= 1: candidates tested against the accepted planes before the selection gives up */
+    uint32_t slice_chunks;       /* 0: the library chooses; else chunks of 256 segments per slice.  No output depends on it */
+    uint32_t reserved[2];        /* must be 0 */
+} l3d_planes_params;
+/* an accepted plane (264 bytes), in order of acceptance */
+typedef struct l3d_pl_plane {
+    uint32_t hypothesis;         /* its index in the junction list */
+    uint32_t a, b;               /* the two segments that span it, a < b */
+    uint32_t n_segments;         /* members */
+    uint32_t n_lines;            /* distinct line indices among them */
+    uint32_t reserved;           /* 0 */
+    uint64_t weight;             /* the members' integer weights, summed: length * 2^scale_exponent, each floored */
+    double N[3], J[3], d;        /* unit normal, the junction's point, d = N.J */
+    double length;               /* of the members, added sequentially */
+    double rms;                  /* of the members' 2 n end-point distances from (N, J) */
+    double centroid[3];          /* of the members' end points */
+    double N_fit[3], d_fit;      /* least-squares plane through them (N_fit.N >= 0), d_fit = N_fit.centroid */
+    double rms_fit;              /* of the end-point distances from it */
+    double corners[4][3];        /* a patch for display in the plane (N, J): the bounding rectangle of the members' end
+                                    points along U = the direction of segment a and V = N x U */
+} l3d_pl_plane;
+/* a membership (8 bytes), in (plane, segment) order */
+typedef struct l3d_pl_member { uint32_t plane, segment; } l3d_pl_member;
+/* the score of a hypothesis (16 bytes), as the device yields it */
+typedef struct l3d_pl_score { uint64_t weight; uint32_t count, reserved; } l3d_pl_score;
+/* (136 bytes) */
+typedef struct l3d_planes_summary {
+    uint64_t n_segments, n_point_segments;
+    uint64_t n_hypotheses, n_dead;          /* junctions; those whose normal has no finite, positive squared length */
+    uint64_t n_candidates;                  /* live hypotheses with min_segments and min_length */
+    uint64_t n_tested, n_dropped, n_rejected;
+    uint64_t n_planes, n_memberships;
+    uint64_t n_segments_in_planes, n_segments_in_several;
+    uint64_t truncated;                     /* 1: max_tests was reached before the candidates or max_planes ran out */
+    int64_t scale_exponent;                 /* weight = floor(length * 2^scale_exponent) */
+    double length_total;                    /* of the segments, added sequentially */
+    double length_in_planes;                /* of the segments in at least one plane, each once */
+    double max_rms;
+} l3d_planes_summary;
+typedef struct l3d_planes l3d_planes;
+/* Stateless, host pointers.  segs6 [n x 6], line [n].  The result lives in a handle: *out, to be closed by
+ * l3d_planes_close.  Checked before any device work, *out untouched: L3D_ERR_LIMIT for 2^30 or more segments; L3D_ERR_ARG
+ * for a null pointer, a coordinate that is not finite or beyond 2^100 (the message names the segment), max_distance,
+ * junction_distance, junction_extension or min_length negative or not finite, min_sin2 outside [0, 1] or NaN,
+ * min_segments, max_planes or max_tests 0, reserved != 0.  More than 2^24 hypotheses: L3D_ERR_LIMIT, found after the
+ * junctions' count pass ("lower junction_distance"), *out untouched.  n = 0: L3D_OK, no plane, a summary of zeros. */
+int l3d_plane_segments(int device, uint32_t n, const double* segs6, const uint32_t* line, const l3d_planes_params* params,
+                       l3d_planes** out);
+/* The same on the context's lines (flattened as for l3d_compare_lines), on the context's stream.  The context is NOT
+ * modified.  L3D_ERR_STATE without reconstructed lines or while a split call is open. */
+int l3d_plane_lines(l3d_ctx*, const l3d_planes_params* params, l3d_planes** out);
+/* the sizes of planes, members and scores; any pointer may be NULL */
+int l3d_planes_counts(const l3d_planes*, uint64_t* n_planes, uint64_t* n_memberships, uint64_t* n_hypotheses);
+/* planes [n_planes], members [n_memberships], seg_planes [n_segments]: the number of planes of every segment, scores
+ * [n_hypotheses]: the device's score of every hypothesis; the summary.  Any pointer may be NULL */
+int l3d_planes_get(const l3d_planes*, l3d_pl_plane* planes, l3d_pl_member* members, uint32_t* seg_planes, l3d_pl_score* scores,
+                   l3d_planes_summary* summary);
+/* four "v x y z" (%.17g), the corners, and one "f i j k l" (1-based) per plane, in plane order.  L3D_ERR_IO where the
+ * file cannot be written. */
+int l3d_planes_save_obj(const l3d_planes*, const char* path);
+void l3d_planes_close(l3d_planes*);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,7 @@
 //     mergeLines(max_distance, max_angle, min_overlap)                           (... and their near-duplicates merged)
 //     alignLines(other, similarity, summary, max_distance, start_distance, ...)  (... and aligned to a model in another frame)
 //     wireframe(max_distance, max_extension, min_angle)                          (... and where they meet: junctions, vertices, edges)
+//     detectPlanes(max_distance, junction_distance, junction_extension, min_angle, ...)   (... and the planes they lie in)
 //
 // Same names, argument order, defaults (commons.h:40-70) and error behaviour as the reference: errors
 // are printed with the "[L3D++] ERROR:" prefix and the call returns (void), no exceptions
@@ -621,6 +622,47 @@ public:
         l3d_wireframe_close(h);
         w.ok = true;
         return w;
+    }
+
+    // The planes the lines of this model lie in (no reference counterpart; DESIGN §25, k_planes.hip): every pair of lines
+    // that meet (as for wireframe, with junction_distance and junction_extension) spans a plane; a segment belongs to it
+    // when both its end points lie within max_distance of it; the best-supported planes with at least min_segments members
+    // of at least min_length in all are kept.  A segment may lie in several planes.  Distances in model units (negative
+    // junction_distance / junction_extension: max_distance), min_angle in degrees [0, 90].  The model itself is NOT
+    // changed.  Errors are printed and give an empty result with ok = false.
+    struct Planes {
+        bool ok = false;
+        std::vector<l3d_pl_plane> planes;
+        std::vector<l3d_pl_member> members;       // (plane, segment), in that order
+        std::vector<uint32_t> seg_planes;         // per segment: the number of its planes
+        std::vector<l3d_pl_score> scores;         // per hypothesis
+        l3d_planes_summary summary{};
+    };
+    Planes detectPlanes(const double max_distance, const double junction_distance = -1.0, const double junction_extension = -1.0,
+                        const double min_angle = 10.0, const double min_length = 0.0, const unsigned int min_segments = 4,
+                        const unsigned int max_planes = 64, const unsigned int max_tests = 4096) {
+        Planes p;
+        if (!(min_angle >= 0.0 && min_angle <= 90.0)) {
+            std::cout << prefix_err_ << "detectPlanes: min_angle must lie in [0, 90] degrees" << std::endl;
+            return p;
+        }
+        const double sine = std::sin(min_angle * (3.14159265358979323846 / 180.0));
+        const l3d_planes_params par{max_distance, junction_distance < 0.0 ? max_distance : junction_distance,
+                                    junction_extension < 0.0 ? max_distance : junction_extension, sine * sine, min_length,
+                                    min_segments, max_planes, max_tests, 0u, {0u, 0u}};
+        l3d_planes* h = nullptr;
+        if (l3d_plane_lines(ctx_, &par, &h) != L3D_OK) {
+            std::cout << prefix_err_ << "detectPlanes: " << l3d_last_error() << std::endl;
+            return p;
+        }
+        uint64_t np = 0, nm = 0, nh = 0;
+        l3d_planes_counts(h, &np, &nm, &nh);
+        l3d_planes_get(h, nullptr, nullptr, nullptr, nullptr, &p.summary);
+        p.planes.resize(np); p.members.resize(nm); p.seg_planes.resize(p.summary.n_segments); p.scores.resize(nh);
+        l3d_planes_get(h, p.planes.data(), p.members.data(), p.seg_planes.data(), p.scores.data(), nullptr);
+        l3d_planes_close(h);
+        p.ok = true;
+        return p;
     }
 
     // The 3D lines drawn over inImg (cv::Mat, Image8U or ImageBuf8U, 8-bit with 1 or 3 channels, of the camera's size):

@@ -55,6 +55,13 @@ WF_VERTEX_DTYPE = np.dtype([("P", "<f8", 3), ("spread", "<f8"), ("n_junctions", 
                             ("component", "<u4")])
 WF_EDGE_DTYPE = np.dtype([("v0", "<u4"), ("v1", "<u4"), ("segment", "<u4"), ("line", "<u4")])
 assert WF_JUNCTION_DTYPE.itemsize == 72 and WF_VERTEX_DTYPE.itemsize == 48 and WF_EDGE_DTYPE.itemsize == 16
+# l3d_pl_plane, l3d_pl_member, l3d_pl_score: the planes of a model
+PL_PLANE_DTYPE = np.dtype([("hypothesis", "<u4"), ("a", "<u4"), ("b", "<u4"), ("n_segments", "<u4"), ("n_lines", "<u4"), ("reserved", "<u4"),
+                           ("weight", "<u8"), ("N", "<f8", 3), ("J", "<f8", 3), ("d", "<f8"), ("length", "<f8"), ("rms", "<f8"),
+                           ("centroid", "<f8", 3), ("N_fit", "<f8", 3), ("d_fit", "<f8"), ("rms_fit", "<f8"), ("corners", "<f8", (4, 3))])
+PL_MEMBER_DTYPE = np.dtype([("plane", "<u4"), ("segment", "<u4")])
+PL_SCORE_DTYPE = np.dtype([("weight", "<u8"), ("count", "<u4"), ("reserved", "<u4")])
+assert PL_PLANE_DTYPE.itemsize == 264 and PL_MEMBER_DTYPE.itemsize == 8 and PL_SCORE_DTYPE.itemsize == 16
 WF_L, WF_T, WF_X = 1, 2, 4                      # kind of a junction, the bits of a vertex's kinds
 WF_AT_P1, WF_AT_P2, WF_INTERIOR = 0, 1, 2       # class_a, class_b
 EMPTY = 0xFFFFFFFF
@@ -191,6 +198,21 @@ class WireframeSummary(C.Structure):
         [(n, C.c_double) for n in ("length_total", "max_gap", "max_spread")]
 
 
+class PlanesParams(C.Structure):
+    """l3d_planes_params (include/l3dpp_hip.h)"""
+    _fields_ = [("max_distance", C.c_double), ("junction_distance", C.c_double), ("junction_extension", C.c_double),
+                ("min_sin2", C.c_double), ("min_length", C.c_double), ("min_segments", C.c_uint32), ("max_planes", C.c_uint32),
+                ("max_tests", C.c_uint32), ("slice_chunks", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class PlanesSummary(C.Structure):
+    """l3d_planes_summary (include/l3dpp_hip.h)"""
+    _fields_ = [(n, C.c_uint64) for n in ("n_segments", "n_point_segments", "n_hypotheses", "n_dead", "n_candidates", "n_tested",
+                                          "n_dropped", "n_rejected", "n_planes", "n_memberships", "n_segments_in_planes",
+                                          "n_segments_in_several", "truncated")] + [("scale_exponent", C.c_int64)] + \
+        [(n, C.c_double) for n in ("length_total", "length_in_planes", "max_rms")]
+
+
 class Similarity(C.Structure):
     """l3d_similarity (include/l3dpp_hip.h): y = scale * R(q) x + t, q = (w, x, y, z)"""
     _fields_ = [("scale", C.c_double), ("q", C.c_double * 4), ("t", C.c_double * 3)]
@@ -314,6 +336,7 @@ EXPORTS = [
     "l3d_align_segments", "l3d_align_lines", "l3d_transform_segments",
     "l3d_wireframe_segments", "l3d_wireframe_lines", "l3d_wireframe_counts", "l3d_wireframe_get", "l3d_wireframe_save_obj",
     "l3d_wireframe_close",
+    "l3d_plane_segments", "l3d_plane_lines", "l3d_planes_counts", "l3d_planes_get", "l3d_planes_save_obj", "l3d_planes_close",
 ]
 
 _lib = None
@@ -468,6 +491,12 @@ def load():
     L.l3d_wireframe_get.argtypes = [vp, vp, vp, vp, C.POINTER(WireframeSummary)]
     L.l3d_wireframe_save_obj.argtypes = [vp, C.c_char_p]
     L.l3d_wireframe_close.argtypes = [vp]; L.l3d_wireframe_close.restype = None
+    L.l3d_plane_segments.argtypes = [i32, u32, vp, vp, C.POINTER(PlanesParams), C.POINTER(vp)]
+    L.l3d_plane_lines.argtypes = [vp, C.POINTER(PlanesParams), C.POINTER(vp)]
+    L.l3d_planes_counts.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+    L.l3d_planes_get.argtypes = [vp, vp, vp, vp, vp, C.POINTER(PlanesSummary)]
+    L.l3d_planes_save_obj.argtypes = [vp, C.c_char_p]
+    L.l3d_planes_close.argtypes = [vp]; L.l3d_planes_close.restype = None
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("l3d_last_error", "l3d_build_info", "l3d_create", "l3d_destroy"):

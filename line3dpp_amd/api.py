@@ -521,6 +521,23 @@ class Line3D:
             return None
         return take_wireframe(h, obj_path)
 
+    # ---- the planes the lines lie in (no reference counterpart) ---------------------------------------------
+    def detectPlanes(self, max_distance, junction_distance=None, junction_extension=None, min_angle=10.0, min_length=0.0,
+                     min_segments=4, max_planes=64, max_tests=4096, slice_chunks=0, obj_path=None):
+        """the planes that the 3D lines of the last reconstruct3Dlines lie in -> the dict of detect_planes (its segments are
+        flatten_lines' of get3Dlines); None after an error.  The lines themselves are NOT modified."""
+        try:
+            par = planes_params(max_distance, junction_distance, junction_extension, min_angle, min_length, min_segments,
+                                max_planes, max_tests, slice_chunks)
+        except (ValueError, TypeError) as e:
+            print(f"{self.PREFIX}ERROR: detectPlanes: {e}")
+            self.last_status = -1
+            return None
+        h = C.c_void_p()
+        if not self._check(self.L.l3d_plane_lines(self.h, C.byref(par), C.byref(h)), "detectPlanes"):
+            return None
+        return take_planes(h, obj_path)
+
     # ---- this model aligned to another one (DESIGN §23; no reference counterpart) -------------------------------------
     def alignLines(self, other, max_distance, start_distance=0.0, initial=None, estimate_scale=True, max_angle=10.0,
                    min_overlap=0.5, step_tolerance=1e-9, max_iterations=50, min_matches=8, slice_chunks=0):
@@ -1018,6 +1035,70 @@ def write_wireframe_obj(wireframe, path):
             f.write("v %.17g %.17g %.17g\n" % (float(v["P"][0]), float(v["P"][1]), float(v["P"][2])))
         for e in wireframe["edges"]:
             f.write("l %d %d\n" % (int(e["v0"]) + 1, int(e["v1"]) + 1))
+
+
+def planes_params(max_distance, junction_distance=None, junction_extension=None, min_angle=10.0, min_length=0.0, min_segments=4,
+                  max_planes=64, max_tests=4096, slice_chunks=0):
+    """l3d_planes_params from the wrappers' arguments: junction_distance and junction_extension None = max_distance;
+    min_sin2 by wireframe_params' degree rule"""
+    w = wireframe_params(max_distance if junction_distance is None else junction_distance,
+                         max_distance if junction_extension is None else junction_extension, min_angle, slice_chunks)
+    return _lib.PlanesParams(float(max_distance), w.max_distance, w.max_extension, w.min_sin2, float(min_length), int(min_segments),
+                             int(max_planes), int(max_tests), w.slice_chunks, (0, 0))
+
+
+def planes_summary_dict(s):
+    return {f: getattr(s, f) for f, _ in _lib.PlanesSummary._fields_}
+
+
+def take_planes(handle, obj_path=None):
+    """the arrays and the summary out of an l3d_planes handle, which is closed -> dict(planes: PL_PLANE_DTYPE, members:
+    PL_MEMBER_DTYPE, seg_planes: uint32 per segment, scores: PL_SCORE_DTYPE per hypothesis, summary: dict).  obj_path:
+    l3d_planes_save_obj writes it first"""
+    L = _lib.load()
+    try:
+        if obj_path is not None and L.l3d_planes_save_obj(handle, str(obj_path).encode()) != 0:
+            raise RuntimeError(f"l3d_planes_save_obj failed: {_lib.last_error()}")
+        n_p = C.c_uint64(); n_m = C.c_uint64(); n_h = C.c_uint64(); s = _lib.PlanesSummary()
+        L.l3d_planes_counts(handle, C.byref(n_p), C.byref(n_m), C.byref(n_h))
+        L.l3d_planes_get(handle, None, None, None, None, C.byref(s))
+        planes = np.zeros(max(n_p.value, 1), _lib.PL_PLANE_DTYPE); members = np.zeros(max(n_m.value, 1), _lib.PL_MEMBER_DTYPE)
+        seg_planes = np.zeros(max(s.n_segments, 1), np.uint32); scores = np.zeros(max(n_h.value, 1), _lib.PL_SCORE_DTYPE)
+        L.l3d_planes_get(handle, ptr(planes), ptr(members), ptr(seg_planes), ptr(scores), None)
+    finally:
+        L.l3d_planes_close(handle)
+    return dict(planes=planes[:n_p.value], members=members[:n_m.value], seg_planes=seg_planes[:s.n_segments], scores=scores[:n_h.value],
+                summary=planes_summary_dict(s))
+
+
+def detect_planes(segs, line, max_distance, junction_distance=None, junction_extension=None, min_angle=10.0, min_length=0.0,
+                  min_segments=4, max_planes=64, max_tests=4096, slice_chunks=0, device=0, obj_path=None):
+    """l3d_plane_segments: one model of 3D segments, segs [n, 6] float64 (P1, P2) with a line index each ->
+    dict(planes, members, seg_planes, scores: arrays, summary: a dict): the planes that at least min_segments segments of
+    at least min_length in all lie in, both end points within max_distance, each spanned by two lines that meet (§24 with
+    junction_distance, junction_extension -- None: max_distance -- and min_angle in degrees [0, 90])."""
+    L = _lib.load()
+    s = np.ascontiguousarray(segs, np.float64).reshape(-1, 6)
+    ln = np.ascontiguousarray(line, np.uint32).reshape(-1)
+    if len(ln) != len(s):
+        raise ValueError("one line index per segment")
+    par = planes_params(max_distance, junction_distance, junction_extension, min_angle, min_length, min_segments, max_planes,
+                        max_tests, slice_chunks)
+    h = C.c_void_p()
+    rc = L.l3d_plane_segments(int(device), len(s), ptr(s), ptr(ln), C.byref(par), C.byref(h))
+    if rc != 0:
+        raise RuntimeError(f"l3d_plane_segments failed [{rc}]: {_lib.last_error()}")
+    return take_planes(h, obj_path)
+
+
+def write_planes_obj(planes, path):
+    """planes as detect_planes returns them -> an OBJ file, the bytes of l3d_planes_save_obj: per plane four "v x y z" at
+    %.17g, its corners, and one "f i j k l" (1-based)"""
+    with open(path, "w") as f:
+        for k, p in enumerate(planes["planes"]):
+            for c in p["corners"]:
+                f.write("v %.17g %.17g %.17g\n" % (float(c[0]), float(c[1]), float(c[2])))
+            f.write("f %d %d %d %d\n" % (4 * k + 1, 4 * k + 2, 4 * k + 3, 4 * k + 4))
 
 
 def align_params(max_distance, start_distance=0.0, max_angle=10.0, min_overlap=0.5, step_tolerance=1e-9, max_iterations=50,

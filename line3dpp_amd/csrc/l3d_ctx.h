@@ -148,6 +148,16 @@ void context_segments(const ::l3d_ctx* c, std::vector<double>& P6, std::vector<u
 // the context forms' opening (mutex held): "<busy> while a split call is open" (null: not checked), "no 3D lines to <verb>: ..."
 int lines_ready(const ::l3d_ctx* c, const char* busy, const char* verb);
 l3d_camera camera_of(const HostView& v);
+// l3d_wireframe.hip: stage 1 of §24, the junctions of a model (n > 0, arguments checked), for the wireframe and for the
+// planes of §25.  With `keep` the list is not downloaded: it stays in w.keys, the model in w.d, until w is used again.
+struct WfRecord;                             // l3d_wireframe.h
+struct WfOnDevice {
+    uint64_t max_junctions; const char* limit_message;   // in: L3D_ERR_LIMIT with this message beyond so many, before the list is allocated
+    const double* segs; const uint32_t* line;            // out: the model on the device,
+    const WfJunction* junctions; size_t n_junctions;     // the list (null where it is empty)
+};
+int wf_junctions(ProjWork& w, hipStream_t st, uint32_t n, const double* segs, const uint32_t* line, const l3d_wireframe_params& p,
+                 std::vector<WfRecord>& out, float* kernel_ms, WfOnDevice* keep = nullptr);
 // Optional kernel timing of a call.  Null `into` (a stateless form, a context below timing level 2): no event, nothing
 // recorded.  Else *into is zeroed, start / stop record around launches and add(), after a synchronise, adds their time.
 struct KernelTimer {

@@ -418,6 +418,28 @@ hipError_t launch_wf_check(const WfArgs& a, hipStream_t st);
 // l3d_wireframe.hip, test hooks read through l3d_debug_counter
 extern std::atomic<uint64_t> g_wf_count_launches, g_wf_write_launches, g_wf_slices, g_wf_junctions, g_wf_skipped_blocks, g_wf_kernel_ns, g_wf_count_ns;
 
+// ---- k_planes.hip: a plane per junction, and every plane scored against every segment (host side:
+// l3d_planes.hip, the selection: l3d_planes.h) ----
+struct PlHypothesis { double N[3], J[3]; uint32_t a, b, live, pad; };   // = PlHyp of l3d_planes.h
+struct PlCell { unsigned long long weight; uint32_t count, zero; };      // = l3d_pl_score
+static_assert(sizeof(PlHypothesis) == 64 && sizeof(PlCell) == 16, "plane record layout");
+constexpr unsigned long long kPlLiveBit = 1ull << 63;   // of a segment's weight word: E2 > 0.  The weight itself is below 2^53
+struct PlArgs {
+    const double* segs; uint32_t n;          // [n] x (P1, P2)
+    const unsigned long long* weight;        // [n] the integer weight, kPlLiveBit set for a live segment; 0: a point
+    const WfJunction* junctions; uint32_t n_h;   // the hypotheses' junctions
+    uint32_t slice_chunks, n_slices;
+    double max_distance;
+    PlHypothesis* hyp;                       // [n_h], written by k_pl_hypotheses
+    PlCell* cells;                           // [n_h * n_slices] at [h * n_slices + slice], written by k_pl_score
+    PlCell* scores;                          // [n_h], the cells of a hypothesis added, written by k_pl_merge
+};
+hipError_t launch_pl_hypotheses(const PlArgs& a, hipStream_t st);
+hipError_t launch_pl_score(const PlArgs& a, hipStream_t st);
+hipError_t launch_pl_merge(const PlArgs& a, hipStream_t st);
+// l3d_planes.hip, test hooks read through l3d_debug_counter
+extern std::atomic<uint64_t> g_pl_score_launches, g_pl_slices, g_pl_hypotheses, g_pl_kernel_ns, g_pl_junction_ns;
+
 // ---- k_align.hip: the similarity transform applied, and the normal equations of an alignment step (host
 // side: l3d_align.hip) ----
 constexpr uint32_t kAlnTerms = 37;       // H (28: the upper triangle of 7 x 7, row by row), b (7), cost, count

@@ -49,11 +49,17 @@ uint64_t skipped_blocks(uint32_t n, const SlicePlan& plan) {
     return skipped;
 }
 
+}  // namespace
+
+namespace l3d {
+
 // ---- stage 1: the junctions, ascending (a, b).  n > 0, arguments checked.  kernel_ms (may be null): [0] the time of the
 // count pass with its scan, [1] that of the write pass.  Slices by §18's rule, the counts within kWfCountBudget.
+// keep (null for the wireframe itself): the list stays on the device and `out` stays empty (l3d_ctx.h).
 int wf_junctions(ProjWork& w, hipStream_t st, uint32_t n, const double* segs, const uint32_t* line, const l3d_wireframe_params& p,
-                 std::vector<WfRecord>& out, float* kernel_ms) {
+                 std::vector<WfRecord>& out, float* kernel_ms, WfOnDevice* keep) {
     out.clear();
+    if (keep) { keep->segs = nullptr; keep->line = nullptr; keep->junctions = nullptr; keep->n_junctions = 0; }
     const SlicePlan plan = slice_plan(n, n, p.slice_chunks, sizeof(uint32_t), kWfCountBudget);
     const uint32_t n_slices = plan.n_slices;
     const size_t cells = (size_t)n * n_slices;
@@ -86,30 +92,34 @@ int wf_junctions(ProjWork& w, hipStream_t st, uint32_t n, const double* segs, co
         g_wf_count_launches.fetch_add(1, std::memory_order_relaxed);
         g_wf_slices.store(n_slices, std::memory_order_relaxed);
         g_wf_skipped_blocks.store(skipped_blocks(n, plan), std::memory_order_relaxed);
-        if (tail[1] || tail[0] > kWfMaxJunctions) rc = fail(L3D_ERR_LIMIT, "more than 2^28 junctions");
+        if (tail[1] || tail[0] > (keep ? keep->max_junctions : kWfMaxJunctions))
+            rc = fail(L3D_ERR_LIMIT, keep ? keep->limit_message : "more than 2^28 junctions");
     }
     const size_t n_out = tail[0];
     if (e == hipSuccess && rc == L3D_OK && n_out) {        // (no junction: no write pass)
-        if (w.keys.reserve(4 * n_out) != hipSuccess || w.h.reserve(32 * n_out) != hipSuccess) return fail(L3D_ERR_HIP, "wireframe: allocation failed");
+        if (w.keys.reserve(4 * n_out) != hipSuccess || (!keep && w.h.reserve(32 * n_out) != hipSuccess)) return fail(L3D_ERR_HIP, "wireframe: allocation failed");
         a.out = (WfJunction*)w.keys.p; a.n_out = (uint32_t)n_out;
         e = timer_w.start(st);
         if (e == hipSuccess) e = launch_wf_write(a, st);
         if (e == hipSuccess) e = timer_w.stop(st);
-        if (e == hipSuccess) e = hipMemcpyAsync(w.h.p, a.out, 32 * n_out, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && !keep) e = hipMemcpyAsync(w.h.p, a.out, 32 * n_out, hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
         if (e == hipSuccess) timer_w.add();
         if (e == hipSuccess) {
             g_wf_write_launches.fetch_add(1, std::memory_order_relaxed);
-            const WfRecord* got = (const WfRecord*)w.h.p;
-            out.assign(got, got + n_out);
+            if (!keep) {
+                const WfRecord* got = (const WfRecord*)w.h.p;
+                out.assign(got, got + n_out);
+            }
         }
     }
+    if (e == hipSuccess && rc == L3D_OK && keep) { keep->segs = a.segs; keep->line = a.line; keep->junctions = a.out; keep->n_junctions = n_out; }
     if (e != hipSuccess) return fail(L3D_ERR_HIP, std::string("wireframe: ") + hipGetErrorString(e));
     if (rc == L3D_OK) g_wf_junctions.store(n_out, std::memory_order_relaxed);
     return rc;
 }
 
-}  // namespace
+}  // namespace l3d
 
 extern "C" {
 
