@@ -1293,6 +1293,82 @@ int l3d_planes_get(const l3d_planes*, l3d_pl_plane* planes, l3d_pl_member* membe
 int l3d_planes_save_obj(const l3d_planes*, const char* path);
 void l3d_planes_close(l3d_planes*);
 
+/* ---- the directions the 3D lines run in (GPU: k_directions.hip, selection: l3d_directions.h) ------------------
+ * No reference counterpart.  One model as above.  The direction of every segment is a hypothesis; every hypothesis is scored
+ * on the device against every segment (a segment is an inlier iff the squared sine of its angle to the direction is at most
+ * max_sin2, either way round; the score is the number of inliers and their length as an integer weight), and a sequential
+ * selection on the host keeps the best-supported directions whose own segment is not yet a member of an accepted one and
+ * that do not share more than half their weight with one.  A segment may belong to several directions.  The frame is the
+ * rotation that turns the heaviest pairwise orthogonal directions into the coordinate axes.  The model itself is not
+ * modified.  fp64, the contract of DESIGN §26. */
+typedef struct l3d_directions_params {   /* 64 bytes */
+    double max_sin2;             /* in [0, 1], no default: largest squared sine between a member and the direction */
+    double min_length;           /* model units, finite, >= 0: least support (summed member length) of a direction */
+    double max_frame_cos2;       /* in [0, 1]: two directions are orthogonal iff the squared cosine of their angle is <= this */
+    uint32_t min_segments;       /* >= 1: least number of member segments */
+    uint32_t max_directions;     /* >= 1 */
+    uint32_t max_tests;          /* >= 1: candidates tested against the accepted directions before the selection gives up */
+    uint32_t slice_chunks;       /* 0: the library chooses; else chunks of 256 segments per slice.  No output depends on it */
+    uint32_t frame_search;       /* 1 .. 64: the frame is sought among so many of the first directions */
+    uint32_t reserved[5];        /* must be 0 */
+} l3d_directions_params;
+/* an accepted direction (136 bytes), in order of acceptance */
+typedef struct l3d_dir_direction {
+    uint32_t hypothesis;         /* the segment whose direction it is */
+    uint32_t n_segments;         /* members */
+    uint32_t n_lines;            /* distinct line indices among them */
+    uint32_t reserved;           /* 0 */
+    uint64_t weight;             /* the members' integer weights, summed: length * 2^scale_exponent, each floored */
+    double D[3];                 /* the unit direction of the hypothesis */
+    double length;               /* of the members, added sequentially */
+    double rms_sin;              /* root mean square of the members' sines against D */
+    double D_fit[3];             /* the largest eigenvector of the members' length-weighted scatter, D_fit.D >= 0 */
+    double rms_sin_fit;          /* ... against D_fit */
+    double centroid[3];          /* of the members' end points */
+    double t_min, t_max;         /* the extremes of (p - centroid).D_fit over them */
+} l3d_dir_direction;
+/* a membership (8 bytes), in (direction, segment) order */
+typedef struct l3d_dir_member { uint32_t direction, segment; } l3d_dir_member;
+/* the score of a hypothesis (16 bytes), as the device yields it */
+typedef struct l3d_dir_score { uint64_t weight; uint32_t count, reserved; } l3d_dir_score;
+/* (200 bytes) */
+typedef struct l3d_directions_summary {
+    uint64_t n_segments, n_point_segments;
+    uint64_t n_candidates;                  /* live hypotheses with min_segments and min_length */
+    uint64_t n_tested, n_dropped, n_rejected;
+    uint64_t n_directions, n_memberships;
+    uint64_t n_segments_in_directions, n_segments_in_several;
+    uint64_t truncated;                     /* 1: max_tests was reached before the candidates or max_directions ran out */
+    int64_t scale_exponent;                 /* weight = floor(length * 2^scale_exponent) */
+    double length_total;                    /* of the segments, added sequentially */
+    double length_in_directions;            /* of the segments in at least one direction, each once */
+    uint32_t frame_axes;                    /* 0 .. 3: directions the frame rests on */
+    uint32_t frame[3];                      /* their indices; an unused slot holds 0xFFFFFFFF */
+    double R[9];                            /* row-major, p' = R p: the rotation into the frame; the identity without a direction */
+} l3d_directions_summary;
+typedef struct l3d_directions l3d_directions;
+/* Stateless, host pointers.  segs6 [n x 6], line [n].  The result lives in a handle: *out, to be closed by
+ * l3d_directions_close.  Checked before any device work, *out untouched: L3D_ERR_LIMIT for 2^30 or more segments;
+ * L3D_ERR_ARG for a null pointer, a coordinate that is not finite or beyond 2^100 (the message names the segment), max_sin2
+ * or max_frame_cos2 outside [0, 1] or NaN, min_length negative or not finite, min_segments, max_directions or max_tests 0,
+ * frame_search outside 1 .. 64, reserved != 0.  n = 0: L3D_OK, no direction, a summary of zeros with the identity and an
+ * unused frame, no launch. */
+int l3d_direction_segments(int device, uint32_t n, const double* segs6, const uint32_t* line, const l3d_directions_params* params,
+                           l3d_directions** out);
+/* The same on the context's lines (flattened as for l3d_compare_lines), on the context's stream.  The context is NOT
+ * modified.  L3D_ERR_STATE without reconstructed lines or while a split call is open. */
+int l3d_direction_lines(l3d_ctx*, const l3d_directions_params* params, l3d_directions** out);
+/* the sizes of directions, members and scores (n_hypotheses = the segments); any pointer may be NULL */
+int l3d_directions_counts(const l3d_directions*, uint64_t* n_directions, uint64_t* n_memberships, uint64_t* n_hypotheses);
+/* directions [n_directions], members [n_memberships], seg_directions [n_segments]: the number of directions of every
+ * segment, scores [n_hypotheses]: the device's score of every hypothesis; the summary.  Any pointer may be NULL */
+int l3d_directions_get(const l3d_directions*, l3d_dir_direction* directions, l3d_dir_member* members, uint32_t* seg_directions,
+                       l3d_dir_score* scores, l3d_directions_summary* summary);
+/* two "v x y z" (%.17g), centroid + t_min D_fit and centroid + t_max D_fit, and one "l i j" (1-based) per direction, in
+ * direction order.  L3D_ERR_IO where the file cannot be written. */
+int l3d_directions_save_obj(const l3d_directions*, const char* path);
+void l3d_directions_close(l3d_directions*);
+
 #ifdef __cplusplus
 }
 #endif

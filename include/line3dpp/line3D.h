@@ -16,6 +16,7 @@
 //     alignLines(other, similarity, summary, max_distance, start_distance, ...)  (... and aligned to a model in another frame)
 //     wireframe(max_distance, max_extension, min_angle)                          (... and where they meet: junctions, vertices, edges)
 //     detectPlanes(max_distance, junction_distance, junction_extension, min_angle, ...)   (... and the planes they lie in)
+//     detectDirections(max_angle, min_length, min_segments, max_directions, max_tests, frame_angle)   (... the directions they run in)
 //
 // Same names, argument order, defaults (commons.h:40-70) and error behaviour as the reference: errors
 // are printed with the "[L3D++] ERROR:" prefix and the call returns (void), no exceptions
@@ -663,6 +664,47 @@ public:
         l3d_planes_close(h);
         p.ok = true;
         return p;
+    }
+
+    // The directions the lines of this model run in (no reference counterpart; DESIGN §26, k_directions.hip): the direction of
+    // every segment is a hypothesis; a segment belongs to it when the angle between them is at most max_angle, either way
+    // round; the best-supported directions with at least min_segments members of at least min_length in all are kept.  A
+    // segment may belong to several.  summary.R is the rotation (row-major, p' = R p) that turns the heaviest directions
+    // that are orthogonal within frame_angle into the coordinate axes.  Angles in degrees [0, 90].  The model itself is
+    // NOT changed.  Errors are printed and give an empty result with ok = false.
+    struct Directions {
+        bool ok = false;
+        std::vector<l3d_dir_direction> directions;
+        std::vector<l3d_dir_member> members;      // (direction, segment), in that order
+        std::vector<uint32_t> seg_directions;     // per segment: the number of its directions
+        std::vector<l3d_dir_score> scores;        // per hypothesis = per segment
+        l3d_directions_summary summary{};
+    };
+    Directions detectDirections(const double max_angle, const double min_length = 0.0, const unsigned int min_segments = 4,
+                                const unsigned int max_directions = 16, const unsigned int max_tests = 4096,
+                                const double frame_angle = 5.0) {
+        Directions d;
+        if (!(max_angle >= 0.0 && max_angle <= 90.0) || !(frame_angle >= 0.0 && frame_angle <= 90.0)) {
+            std::cout << prefix_err_ << "detectDirections: max_angle and frame_angle must lie in [0, 90] degrees" << std::endl;
+            return d;
+        }
+        const double sine = std::sin(max_angle * (3.14159265358979323846 / 180.0));
+        const double frame_sine = std::sin(frame_angle * (3.14159265358979323846 / 180.0));
+        const l3d_directions_params par{sine * sine, min_length, frame_sine * frame_sine, min_segments, max_directions, max_tests,
+                                        0u, 16u, {0u, 0u, 0u, 0u, 0u}};
+        l3d_directions* h = nullptr;
+        if (l3d_direction_lines(ctx_, &par, &h) != L3D_OK) {
+            std::cout << prefix_err_ << "detectDirections: " << l3d_last_error() << std::endl;
+            return d;
+        }
+        uint64_t nd = 0, nm = 0, nh = 0;
+        l3d_directions_counts(h, &nd, &nm, &nh);
+        l3d_directions_get(h, nullptr, nullptr, nullptr, nullptr, &d.summary);
+        d.directions.resize(nd); d.members.resize(nm); d.seg_directions.resize(d.summary.n_segments); d.scores.resize(nh);
+        l3d_directions_get(h, d.directions.data(), d.members.data(), d.seg_directions.data(), d.scores.data(), nullptr);
+        l3d_directions_close(h);
+        d.ok = true;
+        return d;
     }
 
     // The 3D lines drawn over inImg (cv::Mat, Image8U or ImageBuf8U, 8-bit with 1 or 3 channels, of the camera's size):

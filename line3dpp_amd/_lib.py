@@ -62,6 +62,13 @@ PL_PLANE_DTYPE = np.dtype([("hypothesis", "<u4"), ("a", "<u4"), ("b", "<u4"), ("
 PL_MEMBER_DTYPE = np.dtype([("plane", "<u4"), ("segment", "<u4")])
 PL_SCORE_DTYPE = np.dtype([("weight", "<u8"), ("count", "<u4"), ("reserved", "<u4")])
 assert PL_PLANE_DTYPE.itemsize == 264 and PL_MEMBER_DTYPE.itemsize == 8 and PL_SCORE_DTYPE.itemsize == 16
+# l3d_dir_direction, l3d_dir_member, l3d_dir_score: the directions of a model
+DIR_DIRECTION_DTYPE = np.dtype([("hypothesis", "<u4"), ("n_segments", "<u4"), ("n_lines", "<u4"), ("reserved", "<u4"), ("weight", "<u8"),
+                                ("D", "<f8", 3), ("length", "<f8"), ("rms_sin", "<f8"), ("D_fit", "<f8", 3), ("rms_sin_fit", "<f8"),
+                                ("centroid", "<f8", 3), ("t_min", "<f8"), ("t_max", "<f8")])
+DIR_MEMBER_DTYPE = np.dtype([("direction", "<u4"), ("segment", "<u4")])
+DIR_SCORE_DTYPE = np.dtype([("weight", "<u8"), ("count", "<u4"), ("reserved", "<u4")])
+assert DIR_DIRECTION_DTYPE.itemsize == 136 and DIR_MEMBER_DTYPE.itemsize == 8 and DIR_SCORE_DTYPE.itemsize == 16
 WF_L, WF_T, WF_X = 1, 2, 4                      # kind of a junction, the bits of a vertex's kinds
 WF_AT_P1, WF_AT_P2, WF_INTERIOR = 0, 1, 2       # class_a, class_b
 EMPTY = 0xFFFFFFFF
@@ -213,6 +220,22 @@ class PlanesSummary(C.Structure):
         [(n, C.c_double) for n in ("length_total", "length_in_planes", "max_rms")]
 
 
+class DirectionsParams(C.Structure):
+    """l3d_directions_params (include/l3dpp_hip.h)"""
+    _fields_ = [("max_sin2", C.c_double), ("min_length", C.c_double), ("max_frame_cos2", C.c_double), ("min_segments", C.c_uint32),
+                ("max_directions", C.c_uint32), ("max_tests", C.c_uint32), ("slice_chunks", C.c_uint32), ("frame_search", C.c_uint32),
+                ("reserved", C.c_uint32 * 5)]
+
+
+class DirectionsSummary(C.Structure):
+    """l3d_directions_summary (include/l3dpp_hip.h)"""
+    _fields_ = [(n, C.c_uint64) for n in ("n_segments", "n_point_segments", "n_candidates", "n_tested", "n_dropped", "n_rejected",
+                                          "n_directions", "n_memberships", "n_segments_in_directions", "n_segments_in_several",
+                                          "truncated")] + [("scale_exponent", C.c_int64)] + \
+        [(n, C.c_double) for n in ("length_total", "length_in_directions")] + \
+        [("frame_axes", C.c_uint32), ("frame", C.c_uint32 * 3), ("R", C.c_double * 9)]
+
+
 class Similarity(C.Structure):
     """l3d_similarity (include/l3dpp_hip.h): y = scale * R(q) x + t, q = (w, x, y, z)"""
     _fields_ = [("scale", C.c_double), ("q", C.c_double * 4), ("t", C.c_double * 3)]
@@ -337,6 +360,8 @@ EXPORTS = [
     "l3d_wireframe_segments", "l3d_wireframe_lines", "l3d_wireframe_counts", "l3d_wireframe_get", "l3d_wireframe_save_obj",
     "l3d_wireframe_close",
     "l3d_plane_segments", "l3d_plane_lines", "l3d_planes_counts", "l3d_planes_get", "l3d_planes_save_obj", "l3d_planes_close",
+    "l3d_direction_segments", "l3d_direction_lines", "l3d_directions_counts", "l3d_directions_get", "l3d_directions_save_obj",
+    "l3d_directions_close",
 ]
 
 _lib = None
@@ -497,6 +522,12 @@ def load():
     L.l3d_planes_get.argtypes = [vp, vp, vp, vp, vp, C.POINTER(PlanesSummary)]
     L.l3d_planes_save_obj.argtypes = [vp, C.c_char_p]
     L.l3d_planes_close.argtypes = [vp]; L.l3d_planes_close.restype = None
+    L.l3d_direction_segments.argtypes = [i32, u32, vp, vp, C.POINTER(DirectionsParams), C.POINTER(vp)]
+    L.l3d_direction_lines.argtypes = [vp, C.POINTER(DirectionsParams), C.POINTER(vp)]
+    L.l3d_directions_counts.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+    L.l3d_directions_get.argtypes = [vp, vp, vp, vp, vp, C.POINTER(DirectionsSummary)]
+    L.l3d_directions_save_obj.argtypes = [vp, C.c_char_p]
+    L.l3d_directions_close.argtypes = [vp]; L.l3d_directions_close.restype = None
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("l3d_last_error", "l3d_build_info", "l3d_create", "l3d_destroy"):

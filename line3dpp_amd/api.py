@@ -538,6 +538,24 @@ class Line3D:
             return None
         return take_planes(h, obj_path)
 
+    # ---- the directions the lines run in (no reference counterpart) -----------------------------------------
+    def detectDirections(self, max_angle, min_length=0.0, min_segments=4, max_directions=16, max_tests=4096, frame_angle=5.0,
+                         frame_search=16, slice_chunks=0, obj_path=None):
+        """the directions that the 3D lines of the last reconstruct3Dlines run in, and the frame that stands the model
+        upright -> the dict of detect_directions (its segments are flatten_lines' of get3Dlines); None after an error.  The
+        lines themselves are NOT modified."""
+        try:
+            par = directions_params(max_angle, min_length, min_segments, max_directions, max_tests, frame_angle, frame_search,
+                                    slice_chunks)
+        except (ValueError, TypeError) as e:
+            print(f"{self.PREFIX}ERROR: detectDirections: {e}")
+            self.last_status = -1
+            return None
+        h = C.c_void_p()
+        if not self._check(self.L.l3d_direction_lines(self.h, C.byref(par), C.byref(h)), "detectDirections"):
+            return None
+        return take_directions(h, obj_path)
+
     # ---- this model aligned to another one (DESIGN §23; no reference counterpart) -------------------------------------
     def alignLines(self, other, max_distance, start_distance=0.0, initial=None, estimate_scale=True, max_angle=10.0,
                    min_overlap=0.5, step_tolerance=1e-9, max_iterations=50, min_matches=8, slice_chunks=0):
@@ -1099,6 +1117,78 @@ def write_planes_obj(planes, path):
             for c in p["corners"]:
                 f.write("v %.17g %.17g %.17g\n" % (float(c[0]), float(c[1]), float(c[2])))
             f.write("f %d %d %d %d\n" % (4 * k + 1, 4 * k + 2, 4 * k + 3, 4 * k + 4))
+
+
+def _sin2_of_degrees(angle, name):
+    """sin(radians(angle))^2 for an angle in [0, 90] degrees (wireframe_params' degree rule)"""
+    if not 0.0 <= float(angle) <= 90.0:
+        raise ValueError(f"{name} must lie in [0, 90] degrees")
+    sin = float(np.sin(np.radians(np.float64(angle))))
+    return sin * sin
+
+
+def directions_params(max_angle, min_length=0.0, min_segments=4, max_directions=16, max_tests=4096, frame_angle=5.0, frame_search=16,
+                      slice_chunks=0):
+    """l3d_directions_params from the wrappers' arguments: max_sin2 = sin^2(max_angle), max_frame_cos2 = sin^2(frame_angle)
+    -- two directions are orthogonal when their angle is within frame_angle of 90 degrees --, both in degrees [0, 90]"""
+    return _lib.DirectionsParams(_sin2_of_degrees(max_angle, "max_angle"), float(min_length), _sin2_of_degrees(frame_angle, "frame_angle"),
+                                 int(min_segments), int(max_directions), int(max_tests), int(slice_chunks), int(frame_search), (0,) * 5)
+
+
+def directions_summary_dict(s):
+    """the summary as a dict; frame as a list of three, R as a list of nine (row-major)"""
+    return {f: (list(getattr(s, f)) if f in ("frame", "R") else getattr(s, f)) for f, _ in _lib.DirectionsSummary._fields_}
+
+
+def take_directions(handle, obj_path=None):
+    """the arrays and the summary out of an l3d_directions handle, which is closed -> dict(directions: DIR_DIRECTION_DTYPE,
+    members: DIR_MEMBER_DTYPE, seg_directions: uint32 per segment, scores: DIR_SCORE_DTYPE per hypothesis (= segment),
+    summary: dict, R: [3, 3] float64 with p' = R p).  obj_path: l3d_directions_save_obj writes it first"""
+    L = _lib.load()
+    try:
+        if obj_path is not None and L.l3d_directions_save_obj(handle, str(obj_path).encode()) != 0:
+            raise RuntimeError(f"l3d_directions_save_obj failed: {_lib.last_error()}")
+        n_d = C.c_uint64(); n_m = C.c_uint64(); n_h = C.c_uint64(); s = _lib.DirectionsSummary()
+        L.l3d_directions_counts(handle, C.byref(n_d), C.byref(n_m), C.byref(n_h))
+        L.l3d_directions_get(handle, None, None, None, None, C.byref(s))
+        directions = np.zeros(max(n_d.value, 1), _lib.DIR_DIRECTION_DTYPE); members = np.zeros(max(n_m.value, 1), _lib.DIR_MEMBER_DTYPE)
+        seg_directions = np.zeros(max(s.n_segments, 1), np.uint32); scores = np.zeros(max(n_h.value, 1), _lib.DIR_SCORE_DTYPE)
+        L.l3d_directions_get(handle, ptr(directions), ptr(members), ptr(seg_directions), ptr(scores), None)
+    finally:
+        L.l3d_directions_close(handle)
+    summary = directions_summary_dict(s)
+    return dict(directions=directions[:n_d.value], members=members[:n_m.value], seg_directions=seg_directions[:s.n_segments],
+                scores=scores[:n_h.value], summary=summary, R=np.array(summary["R"], np.float64).reshape(3, 3))
+
+
+def detect_directions(segs, line, max_angle, min_length=0.0, min_segments=4, max_directions=16, max_tests=4096, frame_angle=5.0,
+                      frame_search=16, slice_chunks=0, device=0, obj_path=None):
+    """l3d_direction_segments: one model of 3D segments, segs [n, 6] float64 (P1, P2) with a line index each ->
+    dict(directions, members, seg_directions, scores: arrays, summary: a dict, R: [3, 3]): the directions that at least
+    min_segments segments of at least min_length in all run in, each within max_angle degrees of it, best-supported first,
+    and the rotation R that turns the heaviest directions that are orthogonal within frame_angle degrees into the axes."""
+    L = _lib.load()
+    s = np.ascontiguousarray(segs, np.float64).reshape(-1, 6)
+    ln = np.ascontiguousarray(line, np.uint32).reshape(-1)
+    if len(ln) != len(s):
+        raise ValueError("one line index per segment")
+    par = directions_params(max_angle, min_length, min_segments, max_directions, max_tests, frame_angle, frame_search, slice_chunks)
+    h = C.c_void_p()
+    rc = L.l3d_direction_segments(int(device), len(s), ptr(s), ptr(ln), C.byref(par), C.byref(h))
+    if rc != 0:
+        raise RuntimeError(f"l3d_direction_segments failed [{rc}]: {_lib.last_error()}")
+    return take_directions(h, obj_path)
+
+
+def write_directions_obj(directions, path):
+    """directions as detect_directions returns them -> an OBJ file, the bytes of l3d_directions_save_obj: per direction two
+    "v x y z" at %.17g, centroid + t_min D_fit and centroid + t_max D_fit, and one "l i j" (1-based)"""
+    with open(path, "w") as f:
+        for k, p in enumerate(directions["directions"]):
+            c = [float(x) for x in p["centroid"]]; d = [float(x) for x in p["D_fit"]]
+            for t in (float(p["t_min"]), float(p["t_max"])):
+                f.write("v %.17g %.17g %.17g\n" % (c[0] + t * d[0], c[1] + t * d[1], c[2] + t * d[2]))
+            f.write("l %d %d\n" % (2 * k + 1, 2 * k + 2))
 
 
 def align_params(max_distance, start_distance=0.0, max_angle=10.0, min_overlap=0.5, step_tolerance=1e-9, max_iterations=50,

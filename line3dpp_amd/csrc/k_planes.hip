@@ -7,7 +7,7 @@
 //                    block = tile * n_slices + slice; the slice passes through LDS in chunks of kCmpChunk = 256 (48 bytes of
 //                    end points and the 8-byte weight word each), every lane walks the chunk with broadcast reads and adds
 //                    up its inliers: cells[h * n_slices + slice] = {weight, count, 0}.
-//   k_pl_merge       one lane per hypothesis adds its cells: scores[h].
+//   k_pl_merge       one lane per hypothesis adds its cells: scores[h]; §26's k_dir_score fills the same cells and shares it.
 // The weights are integers whose total stays below 2^53 (stage 0 on the host), so the sums are associative: no slicing
 // and no order of workgroups changes a bit.  No atomics, no cross-lane traffic; a lane beyond the last hypothesis takes
 // part in every barrier and writes nothing.
@@ -78,13 +78,14 @@ __global__ __launch_bounds__(kCmpTile) void k_pl_score(PlArgs a) {
     if (in_range) a.cells[(size_t)h * a.n_slices + slice] = PlCell{weight, count, 0u};
 }
 
-__global__ __launch_bounds__(256) void k_pl_merge(PlArgs a) {
+// (launched for the directions of §26 as well: their cells have this layout)
+__global__ __launch_bounds__(256) void k_pl_merge(const PlCell* cells, PlCell* scores, uint32_t n_h, uint32_t n_slices) {
     const uint32_t h = blockIdx.x * 256 + threadIdx.x;
-    if (h >= a.n_h) return;
-    const PlCell* c = a.cells + (size_t)h * a.n_slices;
+    if (h >= n_h) return;
+    const PlCell* c = cells + (size_t)h * n_slices;
     PlCell sum{0ull, 0u, 0u};
-    for (uint32_t s = 0; s < a.n_slices; ++s) { sum.weight += c[s].weight; sum.count += c[s].count; }
-    a.scores[h] = sum;
+    for (uint32_t s = 0; s < n_slices; ++s) { sum.weight += c[s].weight; sum.count += c[s].count; }
+    scores[h] = sum;
 }
 
 }  // namespace
@@ -101,9 +102,9 @@ hipError_t launch_pl_score(const PlArgs& a, hipStream_t st) {
     return hipGetLastError();
 }
 
-hipError_t launch_pl_merge(const PlArgs& a, hipStream_t st) {
-    if (!a.n_h || !a.n_slices) return hipSuccess;
-    hipLaunchKernelGGL(k_pl_merge, dim3((a.n_h + 255) / 256), dim3(256), 0, st, a);
+hipError_t launch_pl_merge(const PlCell* cells, PlCell* scores, uint32_t n_h, uint32_t n_slices, hipStream_t st) {
+    if (!n_h || !n_slices) return hipSuccess;
+    hipLaunchKernelGGL(k_pl_merge, dim3((n_h + 255) / 256), dim3(256), 0, st, cells, scores, n_h, n_slices);
     return hipGetLastError();
 }
 

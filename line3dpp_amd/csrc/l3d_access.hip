@@ -269,6 +269,10 @@ unsigned long long l3d_debug_counter(const char* name) {
     if (name && std::string(name) == "pl_hypotheses") return g_pl_hypotheses.load(std::memory_order_relaxed);
     if (name && std::string(name) == "pl_kernel_ns") return g_pl_kernel_ns.load(std::memory_order_relaxed);
     if (name && std::string(name) == "pl_junction_ns") return g_pl_junction_ns.load(std::memory_order_relaxed);
+    if (name && std::string(name) == "dir_score_launches") return g_dir_score_launches.load(std::memory_order_relaxed);
+    if (name && std::string(name) == "dir_slices") return g_dir_slices.load(std::memory_order_relaxed);
+    if (name && std::string(name) == "dir_hypotheses") return g_dir_hypotheses.load(std::memory_order_relaxed);
+    if (name && std::string(name) == "dir_kernel_ns") return g_dir_kernel_ns.load(std::memory_order_relaxed);
     if (name && std::string(name) == "live_device_blocks") return g_live_blocks[0].load(std::memory_order_relaxed);
     if (name && std::string(name) == "live_pinned_blocks") return g_live_blocks[1].load(std::memory_order_relaxed);
     static const char* const kSeamSupport[4] = {"seam_support_wave_lists", "seam_support_group_staged_lists",

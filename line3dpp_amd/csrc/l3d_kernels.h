@@ -436,9 +436,28 @@ struct PlArgs {
 };
 hipError_t launch_pl_hypotheses(const PlArgs& a, hipStream_t st);
 hipError_t launch_pl_score(const PlArgs& a, hipStream_t st);
-hipError_t launch_pl_merge(const PlArgs& a, hipStream_t st);
+// k_pl_merge, for the planes and for the directions of §26 alike: scores[h] = the sum of cells[h * n_slices + slice]
+hipError_t launch_pl_merge(const PlCell* cells, PlCell* scores, uint32_t n_h, uint32_t n_slices, hipStream_t st);
 // l3d_planes.hip, test hooks read through l3d_debug_counter
 extern std::atomic<uint64_t> g_pl_score_launches, g_pl_slices, g_pl_hypotheses, g_pl_kernel_ns, g_pl_junction_ns;
+
+// ---- k_directions.hip: a unit direction per segment, and every direction scored against every segment (DESIGN §26;
+// host side: l3d_directions.hip, the selection: l3d_directions.h).  The cells are §25's, added by k_pl_merge ----
+struct DirUnit { double D[3]; unsigned long long w; };   // e / sqrt(E2), 0 for a point; the weight word (kPlLiveBit)
+static_assert(sizeof(DirUnit) == 32, "direction record layout");
+struct DirArgs {
+    const double* segs; uint32_t n;          // [n] x (P1, P2): segments and hypotheses alike
+    const unsigned long long* weight;        // [n] the weight words of §25
+    uint32_t slice_chunks, n_slices;
+    double max_sin2;
+    DirUnit* units;                          // [n], written by k_dir_units
+    PlCell* cells;                           // [n * n_slices] at [h * n_slices + slice], written by k_dir_score
+    PlCell* scores;                          // [n], written by k_pl_merge
+};
+hipError_t launch_dir_units(const DirArgs& a, hipStream_t st);
+hipError_t launch_dir_score(const DirArgs& a, hipStream_t st);
+// l3d_directions.hip, test hooks read through l3d_debug_counter
+extern std::atomic<uint64_t> g_dir_score_launches, g_dir_slices, g_dir_hypotheses, g_dir_kernel_ns;
 
 // ---- k_align.hip: the similarity transform applied, and the normal equations of an alignment step (host
 // side: l3d_align.hip) ----

@@ -63,12 +63,13 @@ inline void pl_weights(uint32_t n, const double* segs, PlWeights& w) {
 
 inline double pl_dot(const double* x, const double* y) { return (x[0] * y[0] + x[1] * y[1]) + x[2] * y[2]; }
 
-// The eigenvector of the smallest eigenvalue of the symmetric 3 x 3 S = {xx, xy, xz, yy, yz, zz}: kPlJacobiSweeps cyclic
-// sweeps over (0,1), (0,2), (1,2), the rotation as DESIGN §25 writes it; the column of the smallest diagonal entry (the
-// first of equals), divided by its length.
-inline void pl_smallest_eigenvector(const double S[6], double out[3]) {
-    double A[3][3] = {{S[0], S[1], S[2]}, {S[1], S[3], S[4]}, {S[2], S[4], S[5]}};
-    double V[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
+// The Jacobi of DESIGN §25 on the symmetric 3 x 3 S = {xx, xy, xz, yy, yz, zz}: kPlJacobiSweeps cyclic sweeps over (0,1),
+// (0,2), (1,2), the rotation as §25 writes it.  -> A, whose diagonal holds the eigenvalues, and V, whose columns are the
+// eigenvectors.  Shared by the planes' refit (the smallest) and the directions' (the largest, l3d_directions.h).
+inline void pl_jacobi(const double S[6], double A[3][3], double V[3][3]) {
+    const double A0[3][3] = {{S[0], S[1], S[2]}, {S[1], S[3], S[4]}, {S[2], S[4], S[5]}};
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) { A[i][j] = A0[i][j]; V[i][j] = i == j ? 1.0 : 0.0; }
     static const int P[3] = {0, 0, 1}, Q[3] = {1, 2, 2}, R[3] = {2, 1, 0};
     for (int sweep = 0; sweep < kPlJacobiSweeps; ++sweep)
         for (int k = 0; k < 3; ++k) {
@@ -91,12 +92,22 @@ inline void pl_smallest_eigenvector(const double S[6], double out[3]) {
                 V[i][q] = s * vip + c * viq;
             }
         }
-    int m = 0;
-    if (A[1][1] < A[m][m]) m = 1;
-    if (A[2][2] < A[m][m]) m = 2;
+}
+// column m of V, divided by its length
+inline void pl_unit_column(const double V[3][3], int m, double out[3]) {
     const double v[3] = {V[0][m], V[1][m], V[2][m]};
     const double len = std::sqrt(pl_dot(v, v));
     out[0] = v[0] / len; out[1] = v[1] / len; out[2] = v[2] / len;
+}
+// The eigenvector of the smallest eigenvalue: the column of the smallest diagonal entry (the first of equals), divided by
+// its length.
+inline void pl_smallest_eigenvector(const double S[6], double out[3]) {
+    double A[3][3], V[3][3];
+    pl_jacobi(S, A, V);
+    int m = 0;
+    if (A[1][1] < A[m][m]) m = 1;
+    if (A[2][2] < A[m][m]) m = 2;
+    pl_unit_column(V, m, out);
 }
 
 // the inliers of a plane (N, J) among the live segments, ascending: stage 2's test

@@ -74,7 +74,7 @@ int detect(ProjWork& w, hipStream_t st, uint32_t n, const double* segs, const ui
         if (e == hipSuccess) e = timer.start(st);
         if (e == hipSuccess) e = launch_pl_hypotheses(a, st);
         if (e == hipSuccess) e = launch_pl_score(a, st);
-        if (e == hipSuccess) e = launch_pl_merge(a, st);
+        if (e == hipSuccess) e = launch_pl_merge(a.cells, a.scores, a.n_h, a.n_slices, st);
         if (e == hipSuccess) e = timer.stop(st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);     // (the weights have left h)
         if (e == hipSuccess) e = hipMemcpyAsync(h.p, d.p, down_bytes, hipMemcpyDeviceToHost, st);
