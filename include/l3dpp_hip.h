@@ -1143,6 +1143,70 @@ int l3d_align_lines(l3d_ctx*, uint32_t n_other, const double* other_segs6, const
  * of an alignment that returned this similarity.  L3D_ERR_ARG for a null pointer or a similarity as refused above. */
 int l3d_transform_segments(uint32_t n, const double* segs6, const l3d_similarity* similarity, double* out_segs6);
 
+/* ---- camera poses refined against the 3D line model (GPU: k_pose.hip) ------------------------------------
+ * No reference counterpart (its bundle adjustment holds every camera constant).  Given a model as above and, per camera,
+ * an approximate pose (l3d_camera: K stays fixed and must be upper triangular with K22 = 1) and the camera's 2D segments,
+ * every camera is refined on its own by iterated closest lines: per iteration the model is projected (stage 1 of the
+ * projection, unchanged), the segments are associated with the records (l3d_associate_segments' kernel, unchanged, within
+ * `gate` pixels), the 6x6 normal equations of the end points' distances from the image lines of their 3D segments are
+ * summed on the device and solved on the host, and the pose is updated.  The gate starts at max(max_distance,
+ * start_distance) and halves, down to max_distance, whenever the step falls to stall_tolerance.  fp64, the contract of
+ * DESIGN §27.  A start within reach is the caller's. */
+typedef struct l3d_pose_params {    /* 72 bytes */
+    double max_distance;         /* as in l3d_associate_params: the gate of the last iterations and of the delivery pass */
+    double min_cos2;
+    double min_overlap;
+    double start_distance;       /* 0: the gate is max_distance throughout; else finite and >= max_distance (pixels) */
+    double stall_tolerance;      /* finite, > 0: the gate halves after an iteration whose step is at most this */
+    double step_tolerance;       /* finite, > 0: converged when the gate is max_distance and the step is at most this */
+    double near_plane;           /* finite, > 0: of the projection */
+    uint32_t max_iterations;     /* 1 .. 256 */
+    uint32_t min_matches;        /* >= 6: fewer matched segments stop the camera (L3D_POSE_TOO_FEW) */
+    uint32_t reserved[2];        /* must be 0 */
+} l3d_pose_params;
+enum { L3D_POSE_CONVERGED = 0, L3D_POSE_MAX_ITERATIONS = 1, L3D_POSE_TOO_FEW = 2, L3D_POSE_DEGENERATE = 3 };
+typedef struct l3d_pose_summary {   /* 88 bytes */
+    uint32_t status;             /* L3D_POSE_* */
+    uint32_t iterations;         /* iterations run = trace entries written (one that stopped without an update included) */
+    uint64_t n_matched;          /* segments that entered the sums of the delivery pass: matched at max_distance under the final pose */
+    double rms;                  /* sqrt(cost / (2 n_matched)) of them, pixels: the end points' distance from the image lines */
+    double last_step;            /* the step of the last update (0: none was made) */
+    double q[4];                 /* the rotation of the delta on the input pose (w, x, y, z): R = R(q) R_in */
+    double t[3];                 /* its shift, in the frame about the model's centre: t' = R(q) t'_in + this */
+} l3d_pose_summary;
+/* one iteration of one camera (392 bytes).  sums: H (21, the upper triangle row by row), b (6), cost, count. */
+typedef struct l3d_pose_iteration {
+    double gate;
+    double sums[29];
+    double delta[6];             /* rotation (3), translation (3); all 0 where the iteration stopped without a solve */
+    double R[9], t[3];           /* the pose after the update (the camera as given where none has been made yet) */
+    uint64_t n_matched;
+} l3d_pose_iteration;
+/* Stateless, host pointers.  segs6 / line: the model, n_segments x (P1, P2) with a line index each.  cams [n_cams];
+ * n_segments_per_cam[c] 2D segments (x1, y1, x2, y2) of camera c in segs4, camera after camera.  out_cams [n_cams] and
+ * summaries [n_cams] are required; out_assoc (one l3d_association per 2D segment: what l3d_project_segments and
+ * l3d_associate_segments return for out_cams at max_distance) and trace [n_cams x max_iterations] (camera c's entries
+ * from c x max_iterations on) may be NULL.  Every camera is refined independently of the others in the call; a camera that
+ * is never updated comes back bit for bit.  Everything is written after all has run and stays untouched on any error.
+ * Checked before any device work: L3D_ERR_LIMIT for 2^30 or more model segments, 2^32 or more 2D segments or a camera side
+ * beyond 65535; L3D_ERR_ARG for a null pointer where one is needed, a coordinate not finite or beyond 2^100, a 2D segment
+ * or a camera with a non-finite entry or a side of zero pixels, a K that is not upper triangular with K22 = 1 and K00,
+ * K11 != 0, a threshold outside its range, start_distance below max_distance or not finite, stall_tolerance or
+ * step_tolerance not finite or not > 0, max_iterations outside 1..256, min_matches below 6, a near plane not finite or
+ * not > 0, reserved != 0, and the model's bounding box a point.  An empty model, zero cameras or a camera without
+ * segments: L3D_OK, status L3D_POSE_TOO_FEW, the camera returned as given, zero iterations. */
+int l3d_refine_cameras(int device, uint32_t n_segments, const double* segs6, const uint32_t* line, uint32_t n_cams,
+                       const l3d_camera* cams, const uint32_t* n_segments_per_cam, const float* segs4,
+                       const l3d_pose_params* params, l3d_camera* out_cams, l3d_pose_summary* summaries,
+                       l3d_association* out_assoc, l3d_pose_iteration* trace);
+/* The same for added views (camIDs, each once) against the context's lines, flattened as for l3d_compare_lines: each view's
+ * own camera (l3d_view_camera) and segments, on the context's stream.  offsets [n_views + 1] (required): where every view's
+ * associations begin in out_assoc.  The context is NOT modified.  L3D_ERR_STATE without reconstructed lines or while a
+ * split call is open; an unknown camID or one named twice: L3D_ERR_ARG. */
+int l3d_refine_view_cameras(l3d_ctx*, uint32_t n_views, const uint32_t* camIDs, const l3d_pose_params* params,
+                            l3d_camera* out_cams, l3d_pose_summary* summaries, uint64_t* offsets, l3d_association* out_assoc,
+                            l3d_pose_iteration* trace);
+
 /* ---- where 3D lines meet: junctions and the wireframe graph (GPU: k_wireframe.hip) ----------------------
  * No reference counterpart.  One model as above: a flat array of 3D segments with a line index per segment (any values).
  * Two segments a < b of different lines form a junction iff neither is a point, the angle between them is at least the

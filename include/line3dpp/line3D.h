@@ -14,6 +14,7 @@
 //     compareLines(other, mine, theirs, max_distance, max_angle, min_overlap)   (... and compared with another model)
 //     mergeLines(max_distance, max_angle, min_overlap)                           (... and their near-duplicates merged)
 //     alignLines(other, similarity, summary, max_distance, start_distance, ...)  (... and aligned to a model in another frame)
+//     refineCameras(cameras, summaries, max_distance, start_distance, ...)       (... and the views' poses refined against them)
 //     wireframe(max_distance, max_extension, min_angle)                          (... and where they meet: junctions, vertices, edges)
 //     detectPlanes(max_distance, junction_distance, junction_extension, min_angle, ...)   (... and the planes they lie in)
 //     detectDirections(max_angle, min_length, min_segments, max_directions, max_tests, frame_angle)   (... the directions they run in)
@@ -571,6 +572,53 @@ public:
         if (moved) moved->swap(m);
         if (mine) mine->swap(a);
         if (theirs) theirs->swap(b);
+    }
+
+    // The views' cameras refined against this model (no reference counterpart; DESIGN §27, k_pose.hip): the pose of every
+    // added view (or of the views camIDs) is refined against the lines of the last reconstruct3Dlines from the view's own
+    // segments, by iterated closest lines; the gate of a match halves from start_distance (0: none) down to max_distance,
+    // both in pixels, whenever the step stalls.  cameras[camID] receives the refined l3d_camera (K unchanged),
+    // summaries[camID] its l3d_pose_summary; associations (may be null): [camID][segID], what associateSegments would
+    // return for the refined camera.  Neither the views nor the model are changed.  Errors are printed and leave every
+    // output as it was.
+    void refineCameras(std::map<unsigned int, l3d_camera>& cameras, std::map<unsigned int, l3d_pose_summary>& summaries,
+                       const double max_distance = 2.5, const double start_distance = 0.0, const double max_angle = 10.0,
+                       const double min_overlap = 0.5, const std::vector<unsigned int>* camIDs = nullptr,
+                       std::map<unsigned int, std::vector<l3d_association>>* associations = nullptr, const double near_plane = 1e-6) {
+        if (!(max_angle >= 0.0 && max_angle <= 90.0)) {
+            std::cout << prefix_err_ << "refineCameras: max_angle must lie in [0, 90] degrees" << std::endl;
+            return;
+        }
+        const double cosine = std::cos(max_angle * (3.14159265358979323846 / 180.0));
+        const l3d_pose_params par{max_distance, cosine * cosine, min_overlap, start_distance, 1e-4, 1e-9, near_plane, 50u, 8u, {0u, 0u}};
+        std::vector<uint32_t> ids;
+        if (camIDs) ids.assign(camIDs->begin(), camIDs->end());
+        else {
+            std::lock_guard<std::mutex> lk(lines_mu_);
+            for (const auto& kv : num_lines_) ids.push_back(kv.first);
+        }
+        uint64_t room = 0;
+        {
+            std::lock_guard<std::mutex> lk(lines_mu_);
+            for (uint32_t id : ids) {
+                const auto f = num_lines_.find(id);
+                if (f != num_lines_.end()) room += f->second;
+            }
+        }
+        std::vector<l3d_camera> cams(ids.size() + 1);
+        std::vector<l3d_pose_summary> sums(ids.size() + 1);
+        std::vector<uint64_t> off(ids.size() + 1, 0);
+        std::vector<l3d_association> assoc((size_t)room + 1);
+        if (l3d_refine_view_cameras(ctx_, (uint32_t)ids.size(), ids.data(), &par, cams.data(), sums.data(), off.data(), assoc.data(),
+                                    nullptr) != L3D_OK) {
+            std::cout << prefix_err_ << "refineCameras: " << l3d_last_error() << std::endl;
+            return;
+        }
+        for (size_t k = 0; k < ids.size(); ++k) {
+            cameras[ids[k]] = cams[k];
+            summaries[ids[k]] = sums[k];
+            if (associations) (*associations)[ids[k]].assign(assoc.begin() + (size_t)off[k], assoc.begin() + (size_t)off[k + 1]);
+        }
     }
 
     // The near-duplicate lines of this model merged (no reference counterpart; DESIGN §19, k_merge.hip): lines joined by

@@ -45,6 +45,13 @@ ALIGN_ITERATION_DTYPE = np.dtype([("gate", "<f8"), ("sums", "<f8", 37), ("delta"
                                   ("n_matched", "<u8")])
 assert SIMILARITY_DTYPE.itemsize == 64 and ALIGN_ITERATION_DTYPE.itemsize == 432
 ALIGN_STATUS = ("CONVERGED", "MAX_ITERATIONS", "TOO_FEW", "DEGENERATE")
+# l3d_pose_summary and l3d_pose_iteration: a refined camera's summary, one entry of its trace
+POSE_SUMMARY_DTYPE = np.dtype([("status", "<u4"), ("iterations", "<u4"), ("n_matched", "<u8"), ("rms", "<f8"), ("last_step", "<f8"),
+                               ("q", "<f8", 4), ("t", "<f8", 3)])
+POSE_ITERATION_DTYPE = np.dtype([("gate", "<f8"), ("sums", "<f8", 29), ("delta", "<f8", 6), ("R", "<f8", 9), ("t", "<f8", 3),
+                                 ("n_matched", "<u8")])
+assert POSE_SUMMARY_DTYPE.itemsize == 88 and POSE_ITERATION_DTYPE.itemsize == 392
+POSE_STATUS = ALIGN_STATUS
 # l3d_merge_line_info: one line of a merged model
 MERGE_LINE_INFO_DTYPE = np.dtype([("n_members", "<u4"), ("label", "<u4"), ("max_offset", "<f8")])
 assert MERGE_LINE_INFO_DTYPE.itemsize == 16
@@ -249,6 +256,14 @@ class AlignParams(C.Structure):
                 ("reserved", C.c_uint32 * 2)]
 
 
+class PoseParams(C.Structure):
+    """l3d_pose_params (include/l3dpp_hip.h)"""
+    _fields_ = [("max_distance", C.c_double), ("min_cos2", C.c_double), ("min_overlap", C.c_double),
+                ("start_distance", C.c_double), ("stall_tolerance", C.c_double), ("step_tolerance", C.c_double),
+                ("near_plane", C.c_double), ("max_iterations", C.c_uint32), ("min_matches", C.c_uint32),
+                ("reserved", C.c_uint32 * 2)]
+
+
 class AlignSummary(C.Structure):
     """l3d_align_summary (include/l3dpp_hip.h)"""
     _fields_ = [("status", C.c_uint32), ("iterations", C.c_uint32), ("n_matched", C.c_uint64), ("rms", C.c_double),
@@ -357,6 +372,7 @@ EXPORTS = [
     "l3d_compare_segments", "l3d_compare_lines",
     "l3d_merge_segments", "l3d_merge_lines",
     "l3d_align_segments", "l3d_align_lines", "l3d_transform_segments",
+    "l3d_refine_cameras", "l3d_refine_view_cameras",
     "l3d_wireframe_segments", "l3d_wireframe_lines", "l3d_wireframe_counts", "l3d_wireframe_get", "l3d_wireframe_save_obj",
     "l3d_wireframe_close",
     "l3d_plane_segments", "l3d_plane_lines", "l3d_planes_counts", "l3d_planes_get", "l3d_planes_save_obj", "l3d_planes_close",
@@ -510,6 +526,8 @@ def load():
     L.l3d_align_lines.argtypes = [vp, u32, vp, vp, C.POINTER(AlignParams), C.POINTER(Similarity), C.POINTER(Similarity),
                                   C.POINTER(AlignSummary), vp, vp, vp, vp]
     L.l3d_transform_segments.argtypes = [u32, vp, C.POINTER(Similarity), vp]
+    L.l3d_refine_cameras.argtypes = [i32, u32, vp, vp, u32, vp, vp, vp, C.POINTER(PoseParams), vp, vp, vp, vp]
+    L.l3d_refine_view_cameras.argtypes = [vp, u32, vp, C.POINTER(PoseParams), vp, vp, vp, vp, vp]
     L.l3d_wireframe_segments.argtypes = [i32, u32, vp, vp, C.POINTER(WireframeParams), C.POINTER(vp)]
     L.l3d_wireframe_lines.argtypes = [vp, C.POINTER(WireframeParams), C.POINTER(vp)]
     L.l3d_wireframe_counts.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]

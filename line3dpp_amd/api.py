@@ -16,7 +16,7 @@ import numpy as np
 
 from . import _lib, lsd
 from ._lib import (ALIGN_ITERATION_DTYPE, ALIGN_STATUS, ASSOCIATION_DTYPE, CLEDGE_DTYPE, EMPTY, FLOAT4_DTYPE, LINE_MATCH_DTYPE, MATCH_DTYPE, MERGE_LINE_INFO_DTYPE,
-                   PROJECTED_SEGMENT_DTYPE, SEGMENT2D_DTYPE,
+                   POSE_ITERATION_DTYPE, POSE_STATUS, POSE_SUMMARY_DTYPE, PROJECTED_SEGMENT_DTYPE, SEGMENT2D_DTYPE,
                    SEGMENT3D_DTYPE, SLOT_DTYPE, MatchParams, Timings, ptr)
 
 # commons.h:40-70
@@ -582,6 +582,34 @@ class Line3D:
         if not self._check(self.L.l3d_align_lines(self.h, len(line), ptr(segs), ptr(line), C.byref(par), init, *out.pointers()), "alignLines"):
             return None
         return out.result()
+
+    # ---- the views' cameras refined against this model (no reference counterpart) -------------------------
+    def refineCameras(self, camIDs=None, max_distance=L3D_DEF_SCORING_POS_REGULARIZER, start_distance=0.0,
+                      max_angle=L3D_DEF_SCORING_ANG_REGULARIZER, min_overlap=0.5, stall_tolerance=1e-4, step_tolerance=1e-9,
+                      max_iterations=50, min_matches=8, near=1e-6):
+        """the poses of the views camIDs (None: all, ascending) refined against the 3D lines of the last
+        reconstruct3Dlines from each view's own segments -> the dict of refine_cameras, with `camIDs` beside it: cameras,
+        summaries, associations and trace hold one entry per view in that order; None after an error.  The context --
+        its views and its lines -- is NOT modified."""
+        ids = np.ascontiguousarray(sorted(self._M) if camIDs is None else list(camIDs), np.uint32).reshape(-1)
+        try:
+            par = pose_params(max_distance, start_distance, max_angle, min_overlap, stall_tolerance, step_tolerance, max_iterations,
+                              min_matches, near)
+        except ValueError as e:
+            print(f"{self.PREFIX}ERROR: refineCameras: {e}")
+            self.last_status = -1
+            return None
+        # room for the segments the views were given (the context keeps at most that many; an unknown ID is the library's
+        # to refuse); the offsets that come back say where each view's associations lie
+        out = _PoseOutputs(len(ids), [self._M.get(int(c), 0) for c in ids], par.max_iterations)
+        off = np.zeros(len(ids) + 1, np.uint64)
+        if not self._check(self.L.l3d_refine_view_cameras(self.h, len(ids), ptr(ids), C.byref(par), out.cams, ptr(out.summaries),
+                                                          ptr(off), ptr(out.assoc), ptr(out.trace)), "refineCameras"):
+            return None
+        out.n_seg = [int(off[k + 1] - off[k]) for k in range(len(ids))]
+        res = out.result()
+        res["camIDs"] = [int(c) for c in ids]
+        return res
 
     def set_projection_budget(self, n_bytes):
         """test hook: device-memory budget of a group of cameras in the four calls above (0: the default)"""
@@ -1334,6 +1362,62 @@ def align_segments(q_segs, q_line, r_segs, r_line, max_distance, start_distance=
                               *out.pointers())
     if rc != 0:
         raise RuntimeError(f"l3d_align_segments failed [{rc}]: {_lib.last_error()}")
+    return out.result()
+
+
+def pose_params(max_distance=L3D_DEF_SCORING_POS_REGULARIZER, start_distance=0.0, max_angle=L3D_DEF_SCORING_ANG_REGULARIZER,
+                min_overlap=0.5, stall_tolerance=1e-4, step_tolerance=1e-9, max_iterations=50, min_matches=8, near=1e-6):
+    """l3d_pose_params from the wrappers' arguments, by associate_params' degree rule; the distances in pixels"""
+    p = associate_params(max_distance, max_angle, min_overlap)
+    return _lib.PoseParams(p.max_distance, p.min_cos2, p.min_overlap, float(start_distance), float(stall_tolerance),
+                           float(step_tolerance), float(near), int(max_iterations), int(min_matches), (0, 0))
+
+
+class _PoseOutputs:
+    """the output arguments of l3d_refine_cameras / l3d_refine_view_cameras, and the dict the wrappers return from them"""
+
+    def __init__(self, n_cams, n_seg_per_cam, max_iterations):
+        self.n, self.n_seg, self.max_it = n_cams, [int(v) for v in n_seg_per_cam], int(max_iterations)
+        self.cams = (_lib.Camera * max(n_cams, 1))()
+        self.summaries = np.zeros(max(n_cams, 1), POSE_SUMMARY_DTYPE)
+        self.assoc = np.zeros(max(sum(self.n_seg), 1), ASSOCIATION_DTYPE)
+        self.trace = np.zeros(max(n_cams * self.max_it, 1), POSE_ITERATION_DTYPE)
+
+    def result(self):
+        s = self.summaries[:self.n]
+        summaries = [dict(status=POSE_STATUS[int(v["status"])], iterations=int(v["iterations"]), n_matched=int(v["n_matched"]),
+                          rms=float(v["rms"]), last_step=float(v["last_step"]), q=v["q"].copy(), t=v["t"].copy()) for v in s]
+        trace = [self.trace[k * self.max_it:k * self.max_it + int(s["iterations"][k])].copy() for k in range(self.n)]
+        return dict(cameras=[camera_dict(self.cams[k]) for k in range(self.n)], summaries=summaries,
+                    associations=split_records(self.assoc, self.n_seg), trace=trace)
+
+
+def refine_cameras(segs, line, cams, segs_per_cam, max_distance=L3D_DEF_SCORING_POS_REGULARIZER, start_distance=0.0,
+                   max_angle=L3D_DEF_SCORING_ANG_REGULARIZER, min_overlap=0.5, stall_tolerance=1e-4, step_tolerance=1e-9,
+                   max_iterations=50, min_matches=8, near=1e-6, device=0):
+    """l3d_refine_cameras: the poses of `cams` (dicts K, R, t, width, height; K stays fixed) refined against
+    the model (segs [n, 6] float64 with a line index each) from each camera's 2D segments (segs_per_cam: one float32
+    [M, 4] array per camera), by iterated closest lines with the gate halving from start_distance down to max_distance
+    (pixels) whenever the step stalls -> a dict: cameras (the refined dicts), summaries (status as a name, iterations,
+    n_matched, rms in pixels, last_step, the delta q and t), associations (one ASSOCIATION_DTYPE array per camera, of the
+    refined camera at max_distance) and trace (one POSE_ITERATION_DTYPE array per camera)"""
+    L = _lib.load()
+    s = np.ascontiguousarray(segs, np.float64).reshape(-1, 6); ln = np.ascontiguousarray(line, np.uint32).reshape(-1)
+    if len(ln) != len(s):
+        raise ValueError("one line index per segment")
+    if len(cams) != len(segs_per_cam):
+        raise ValueError("one array of segments per camera")
+    seg = [np.ascontiguousarray(v, np.float32).reshape(-1, 4) for v in segs_per_cam]
+    n_seg = np.array([len(v) for v in seg] + [0], np.uint32)
+    seg4 = np.concatenate(seg + [np.zeros((1, 4), np.float32)])
+    par = pose_params(max_distance, start_distance, max_angle, min_overlap, stall_tolerance, step_tolerance, max_iterations,
+                      min_matches, near)
+    arr = camera_array(list(cams))
+    out = _PoseOutputs(len(cams), n_seg[:len(cams)], par.max_iterations)
+    rc = L.l3d_refine_cameras(int(device), len(s), ptr(s), ptr(ln), len(cams), arr, ptr(n_seg), ptr(seg4), C.byref(par), out.cams,
+                              ptr(out.summaries), ptr(out.assoc), ptr(out.trace))
+    if rc != 0:
+        raise RuntimeError(f"l3d_refine_cameras failed [{rc}]: {_lib.last_error()}")
     return out.result()
 
 

@@ -257,6 +257,9 @@ unsigned long long l3d_debug_counter(const char* name) {
     if (name && std::string(name) == "align_iterations") return g_aln_iterations.load(std::memory_order_relaxed);
     if (name && std::string(name) == "align_normal_launches") return g_aln_normal_launches.load(std::memory_order_relaxed);
     if (name && std::string(name) == "align_kernel_ns") return g_aln_kernel_ns.load(std::memory_order_relaxed);
+    if (name && std::string(name) == "pose_iterations") return g_pose_iterations.load(std::memory_order_relaxed);
+    if (name && std::string(name) == "pose_normal_launches") return g_pose_normal_launches.load(std::memory_order_relaxed);
+    if (name && std::string(name) == "pose_kernel_ns") return g_pose_kernel_ns.load(std::memory_order_relaxed);
     if (name && std::string(name) == "wf_count_launches") return g_wf_count_launches.load(std::memory_order_relaxed);
     if (name && std::string(name) == "wf_write_launches") return g_wf_write_launches.load(std::memory_order_relaxed);
     if (name && std::string(name) == "wf_slices") return g_wf_slices.load(std::memory_order_relaxed);

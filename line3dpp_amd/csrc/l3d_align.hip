@@ -90,36 +90,20 @@ void bounding_box(size_t n, const double* segs, double c[3], double& diag) {
     diag = std::sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
 }
 
-// H delta = -b by a plain Cholesky factorisation H = L L^T, column by column (DESIGN §23 writes the loops out); without
-// the scale, row and column 3 are left out and delta[3] = 0.  false: a pivot that is not finite and > 0.
+// H delta = -b by a plain Cholesky factorisation H = L L^T, column by column (DESIGN §23 writes the loops out; they are
+// cholesky_solve of l3d_model.h); without the scale, row and column 3 are left out and delta[3] = 0.  false: a pivot that
+// is not finite and > 0.
 bool solve_normal(const double* s, bool with_scale, double delta[7]) {
     static const int kRow[7] = {0, 7, 13, 18, 22, 25, 27};   // where row i of the upper triangle begins
     int idx[7], n = 0;
     for (int i = 0; i < 7; ++i)
         if (with_scale || i != 3) idx[n++] = i;
-    auto H = [&](int i, int j) { return s[kRow[idx[i]] + (idx[j] - idx[i])]; };   // i <= j
-    double L[7][7] = {}, y[7], x[7];
-    for (int j = 0; j < n; ++j) {
-        double p = H(j, j);
-        for (int k = 0; k < j; ++k) p = p - L[j][k] * L[j][k];
-        if (!(p > 0.0) || !std::isfinite(p)) return false;
-        L[j][j] = std::sqrt(p);
-        for (int i = j + 1; i < n; ++i) {
-            double v = H(j, i);
-            for (int k = 0; k < j; ++k) v = v - L[i][k] * L[j][k];
-            L[i][j] = v / L[j][j];
-        }
-    }
+    double H[7 * 7] = {}, rhs[7], x[7];
     for (int i = 0; i < n; ++i) {
-        double v = -s[28 + idx[i]];
-        for (int k = 0; k < i; ++k) v = v - L[i][k] * y[k];
-        y[i] = v / L[i][i];
+        for (int j = i; j < n; ++j) H[i * n + j] = s[kRow[idx[i]] + (idx[j] - idx[i])];
+        rhs[i] = -s[28 + idx[i]];
     }
-    for (int i = n - 1; i >= 0; --i) {
-        double v = y[i];
-        for (int k = i + 1; k < n; ++k) v = v - L[k][i] * x[k];
-        x[i] = v / L[i][i];
-    }
+    if (!cholesky_solve(n, H, rhs, x)) return false;
     for (int i = 0; i < 7; ++i) delta[i] = 0.0;
     for (int i = 0; i < n; ++i) delta[idx[i]] = x[i];
     return true;

@@ -135,6 +135,11 @@ struct ProjWork {
     size_t budget = 0;                       // device-memory budget of a group of cameras; 0: l3d_project.hip's kProjBudget
 };
 size_t projection_budget(const ProjWork& w);   // l3d_project.hip: the budget in force
+// l3d_project.hip: the checks of stage 1's entries on the near plane and the cameras (sides, finite entries)
+int check_projection_cameras(uint32_t n_cams, const l3d_camera* cams, double near_plane);
+// l3d_project.hip: the launches of stage 1 on device buffers -- k_project_lines, the scan of a.vis in place, the
+// compaction into a.out / a.bounds.  w.scan_ws holds scan_ws_words(n_cams x n_seg, 4) zeroed words.
+hipError_t launch_project_stage1(ProjWork& w, const ProjArgs& a, hipStream_t st);
 // l3d_project.hip: stage 1 on the context's lines into c->proj_records, camera after camera (the caller holds the mutex)
 int project_context_lines(::l3d_ctx* c, uint32_t n_cams, const l3d_camera* cams, double near_plane, std::vector<uint32_t>& counts);
 

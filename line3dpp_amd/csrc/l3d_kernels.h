@@ -478,4 +478,23 @@ hipError_t launch_align_normal(const AlnNormalArgs& a, hipStream_t st);
 // l3d_align.hip, test hooks read through l3d_debug_counter
 extern std::atomic<uint64_t> g_aln_iterations, g_aln_normal_launches, g_aln_kernel_ns;
 
+// ---- k_pose.hip: the normal equations of a camera's pose against the 3D line model (host side:
+// l3d_pose.hip).  The tiles are k_associate's: AssocCam, kAssocTile segments of one camera per workgroup. ----
+constexpr uint32_t kPoseTerms = 29;      // H (21: the upper triangle of 6 x 6, row by row), b (6), cost, count
+// a camera of a pass: the entries m00, m10, m11, m20, m21 of K^-T (the others are 0, 0, 0 and 1) and the pose in force
+struct PoseCam { double M[5], R[9], t[3]; };
+struct PoseNormalArgs {
+    const AssocCam* cams; uint32_t n_cams;   // the table launch_associate was given
+    const PoseCam* pose;                     // [n_cams]
+    const float4* segs;                      // [segments of the group] (x1, y1, x2, y2)
+    const AssocOut* assoc;                   // [segments of the group] the association's records
+    const double* model; uint32_t n_model;   // the 3D segments (P1, P2) in the frame of `pose`
+    double* tiles;                           // [tiles of the launch x kPoseTerms]
+};
+hipError_t launch_pose_normal(const PoseNormalArgs& a, uint32_t n_tiles, hipStream_t st);
+// cams[c].rec0 / n_rec from the compaction's bounds[n_cams + 1], one lane per camera
+hipError_t launch_pose_bounds(AssocCam* cams, uint32_t n_cams, const uint32_t* bounds, hipStream_t st);
+// l3d_pose.hip, test hooks read through l3d_debug_counter
+extern std::atomic<uint64_t> g_pose_iterations, g_pose_normal_launches, g_pose_kernel_ns;
+
 }  // namespace l3d

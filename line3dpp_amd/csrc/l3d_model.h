@@ -5,6 +5,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <cmath>
+
 namespace l3d {
 
 inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }   // device tables start at multiples of 256 bytes
@@ -34,6 +36,38 @@ inline SlicePlan slice_plan(uint32_t n_queries, uint32_t n_refs, uint32_t asked_
     p.slice_chunks = (n_chunks + cap - 1) / cap;
     p.n_slices = (n_chunks + p.slice_chunks - 1) / p.slice_chunks;
     return p;
+}
+
+// H x = rhs for a symmetric H of n <= kCholeskyMax rows, of which the upper triangle H[i * n + j], i <= j, is read, by a
+// plain Cholesky factorisation H = L L^T, column by column, then the forward and the backward substitution: the loops
+// DESIGN §23 writes out, which the alignment (n = 6 or 7) and the pose refinement of §27 (n = 6) share.  false: a pivot
+// that is not finite and > 0, x untouched.
+constexpr int kCholeskyMax = 7;
+inline bool cholesky_solve(int n, const double* H, const double* rhs, double* x) {
+    double L[kCholeskyMax][kCholeskyMax] = {}, y[kCholeskyMax], z[kCholeskyMax];
+    for (int j = 0; j < n; ++j) {
+        double p = H[j * n + j];
+        for (int k = 0; k < j; ++k) p = p - L[j][k] * L[j][k];
+        if (!(p > 0.0) || !std::isfinite(p)) return false;
+        L[j][j] = std::sqrt(p);
+        for (int i = j + 1; i < n; ++i) {
+            double v = H[j * n + i];
+            for (int k = 0; k < j; ++k) v = v - L[i][k] * L[j][k];
+            L[i][j] = v / L[j][j];
+        }
+    }
+    for (int i = 0; i < n; ++i) {
+        double v = rhs[i];
+        for (int k = 0; k < i; ++k) v = v - L[i][k] * y[k];
+        y[i] = v / L[i][i];
+    }
+    for (int i = n - 1; i >= 0; --i) {
+        double v = y[i];
+        for (int k = i + 1; k < n; ++k) v = v - L[k][i] * z[k];
+        z[i] = v / L[i][i];
+    }
+    for (int i = 0; i < n; ++i) x[i] = z[i];
+    return true;
 }
 
 }  // namespace l3d

@@ -104,9 +104,7 @@ int project_core(ProjWork& w, hipStream_t st, uint32_t n_cams, const l3d_camera*
         ProjArgs a{(const ProjCam*)(d + o_cam), g, n_seg, (const double*)(d + o_P), (const uint32_t*)(d + o_line), near_plane,
                    (ProjRecord*)(d + o_rec), (uint32_t*)(d + o_vis), (ProjRecord*)(d + o_out), (uint32_t*)(d + o_bounds)};
         hipError_t e = hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = launch_project_lines(a, st);
-        if (e == hipSuccess) e = launch_scan(a.vis, (uint32_t)n, a.vis, w.scan_ws.p, nullptr, st);
-        if (e == hipSuccess) e = launch_project_compact(a, st);
+        if (e == hipSuccess) e = launch_project_stage1(w, a, st);
         if (e == hipSuccess) e = hipMemcpyAsync(h_bounds, a.bounds, 4 * ((size_t)g + 1), hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
         if (e != hipSuccess) return hip_fail("projection", e);
@@ -264,6 +262,17 @@ std::vector<std::pair<uint32_t, uint32_t>> camera_sizes(uint32_t n_cams, const l
 // shared with l3d_associate.hip: the budget of a group of cameras, and stage 1 on the context's lines (mutex held)
 namespace l3d {
 size_t projection_budget(const ProjWork& w) { return w.budget ? w.budget : kProjBudget; }
+int check_projection_cameras(uint32_t n_cams, const l3d_camera* cams, double near_plane) {
+    if (int rc = check_near(near_plane)) return rc;
+    return check_cameras(n_cams, cams);
+}
+hipError_t launch_project_stage1(ProjWork& w, const ProjArgs& a, hipStream_t st) {
+    const size_t n = (size_t)a.n_cams * a.n_seg;
+    hipError_t e = launch_project_lines(a, st);
+    if (e == hipSuccess) e = launch_scan(a.vis, (uint32_t)n, a.vis, w.scan_ws.p, nullptr, st);
+    if (e == hipSuccess) e = launch_project_compact(a, st);
+    return e;
+}
 int project_context_lines(l3d_ctx* c, uint32_t n_cams, const l3d_camera* cams, double near_plane, std::vector<uint32_t>& counts) {
     if (int rc = lines_ready(c, nullptr, "project")) return rc;
     if (int rc = set_device(c->device)) return rc;
