@@ -1433,6 +1433,100 @@ int l3d_directions_get(const l3d_directions*, l3d_dir_direction* directions, l3d
 int l3d_directions_save_obj(const l3d_directions*, const char* path);
 void l3d_directions_close(l3d_directions*);
 
+/* ---- the 3D lines refit against cameras and their 2D segments (GPU: k_refit.hip, and unchanged k_project.hip's
+ * stage 1, k_scan.hip, k_associate.hip, k_lineopt.hip) ---------------------------------------------------------------------
+ * No reference counterpart as a stage; it restates the reference's project2DsegmentOnto3Dline and the sweep of its final
+ * segments.  Given a model as above, cameras (l3d_camera: K upper triangular with K22 = 1, K00, K11 != 0 and K01 = 0) and each
+ * camera's 2D segments, every line of the model -- the segments that share a line index -- is re-estimated from the 2D
+ * segments associated with it (l3d_project_segments + l3d_associate_segments' kernels at max_distance, on the device) by the
+ * solver of the line bundling from the line's own carrier, and its segments are cut anew: the stretches of the new carrier
+ * that at least `visibility` cameras see.  fp64, the contract of DESIGN §28. */
+typedef struct l3d_refit_params {   /* 64 bytes */
+    double max_distance;         /* as in l3d_associate_params */
+    double min_cos2;
+    double min_overlap;
+    double near_plane;           /* finite, > 0: of the projection */
+    double min_length;           /* finite, >= 0, world units: a shorter piece is not kept */
+    uint32_t visibility;         /* >= 1: cameras that must see a piece; a line needs max(2, visibility) cameras to be refit */
+    uint32_t max_iterations;     /* 0 .. 1000 of the solver; 0 cuts the extents anew about the unchanged carrier */
+    uint32_t use_ambiguous;      /* 0: a 2D segment that accepted more than one record is left out; 1: it is used */
+    uint32_t reserved[3];        /* must be 0 */
+} l3d_refit_params;
+enum { L3D_REFIT_REFIT = 0, L3D_REFIT_TOO_FEW_VIEWS = 1, L3D_REFIT_CONSTANT = 2, L3D_REFIT_FAILED = 3, L3D_REFIT_NO_EXTENT = 4,
+       L3D_REFIT_EMPTY = 5 };
+/* one per line index 0 .. max(line) (152 bytes) */
+typedef struct l3d_refit_line {
+    uint32_t status;             /* L3D_REFIT_* */
+    uint32_t n_observations;     /* 2D segments that observe the line */
+    uint32_t n_views;            /* distinct cameras among them */
+    uint32_t solver_status;      /* the stopping rule of the line bundling's solver (1 gradient, 2 function, 3 parameter, 4
+                                  * iterations, 5 other); 0 where the line was not solved */
+    uint32_t iterations;
+    uint32_t n_pieces;           /* segments of the line in the output model */
+    double cost0, cost1;         /* the robust cost before and after the solve */
+    double x0[4], x[4];          /* the Cayley parameters of the carrier about the model's centre: the start, the result */
+    double P1[3], P2[3];         /* the carrier in the model's frame: written back where the line was solved, else as given */
+} l3d_refit_line;
+/* one per observation (32 bytes), line after line in ascending line index, a line's in ascending (camera, segment) order */
+typedef struct l3d_refit_observation {
+    uint32_t camera, segment;    /* the camera's index in the call, the 2D segment's index in its camera */
+    uint32_t line;
+    uint32_t valid;              /* 1: the span below entered the sweep */
+    double s_lo, s_hi;           /* the span of the 2D segment along the new carrier, M + s u (0 where the line was not solved) */
+} l3d_refit_observation;
+/* (104 bytes) */
+typedef struct l3d_refit_summary {
+    uint64_t n_lines;
+    uint64_t n_status[6];        /* lines per L3D_REFIT_* */
+    uint64_t n_observations;
+    uint64_t n_ambiguous_left_out;   /* associated 2D segments with n_accepted > 1 that use_ambiguous = 0 left out */
+    uint64_t n_segments_before, n_segments_after;
+    double cost0, cost1;         /* of the REFIT lines, added in ascending line index */
+} l3d_refit_summary;
+typedef struct l3d_refit l3d_refit;
+/* Stateless, host pointers.  segs6 / line: the model, n x (P1, P2) with a line index each (a line's segments need not be
+ * neighbours); cams [n_cams]; n_segments_per_cam[c] 2D segments (x1, y1, x2, y2) of camera c in segs4, camera after camera.
+ * The result lives in a handle: *out, to be closed by l3d_refit_close.  Every line that is not REFIT keeps its segments bit
+ * for bit in input order; the output model is grouped by ascending line index, a REFIT line's pieces in ascending s.
+ * Checked before any device work, *out untouched: L3D_ERR_LIMIT for 2^30 or more model segments, a line index of 2^31 or
+ * more, 2^32 or more 2D segments or a camera side beyond 65535; L3D_ERR_ARG for a null pointer where one is needed, a
+ * coordinate not finite or beyond 2^100, a 2D segment or a camera with a non-finite entry or a side of zero pixels, a K that
+ * is not upper triangular with K22 = 1, K00, K11 != 0 and K01 = 0, a threshold outside its range, a near plane not finite
+ * or not > 0, min_length negative or not finite, visibility 0, max_iterations above 1000, use_ambiguous above 1,
+ * reserved != 0, and the model's bounding box a point.  An empty model, zero cameras or no 2D segment at all: L3D_OK, every
+ * line as given (TOO_FEW_VIEWS or EMPTY), no launch. */
+int l3d_refit_segments(int device, uint32_t n_segments, const double* segs6, const uint32_t* line, uint32_t n_cams,
+                       const l3d_camera* cams, const uint32_t* n_segments_per_cam, const float* segs4,
+                       const l3d_refit_params* params, l3d_refit** out);
+/* The same on the context's lines (flattened as for l3d_compare_lines) with the added views camIDs (each once) and their own
+ * segments, on the context's stream; cams [n_views] or NULL: the views' own (l3d_view_camera).  The refit model TAKES THE
+ * PLACE of the context's lines, as l3d_merge_lines' does: a REFIT line's segments are the new pieces, its cluster segment the
+ * written-back carrier, its residuals its observations as (camID, segID); its reference view is kept, every other line is
+ * untouched, the records of l3d_project_lines are cleared and l3d_output_filename carries "REFIT_<max_distance>__" until the
+ * next reconstruct3Dlines; a call in which no line becomes REFIT leaves the records and the name alone, as it leaves the
+ * model.  summary and out may be NULL.  L3D_ERR_STATE without reconstructed lines or while a split call is
+ * open; an unknown camID or one named twice: L3D_ERR_ARG. */
+int l3d_refit_view_lines(l3d_ctx*, uint32_t n_views, const uint32_t* camIDs, const l3d_camera* cams,
+                         const l3d_refit_params* params, l3d_refit_summary* summary, l3d_refit** out);
+/* the sizes of the output model, the lines, the observations and the associations (= the 2D segments); any may be NULL */
+int l3d_refit_counts(const l3d_refit*, uint64_t* n_segments, uint64_t* n_lines, uint64_t* n_observations, uint64_t* n_associations);
+/* segs6 [n_segments x 6] and seg_line [n_segments]: the output model; lines [n_lines]; observations [n_observations];
+ * associations [n_associations]: what l3d_project_segments + l3d_associate_segments return for the call's inputs, camera
+ * after camera; the summary.  Any pointer may be NULL */
+int l3d_refit_get(const l3d_refit*, double* segs6, uint32_t* seg_line, l3d_refit_line* lines, l3d_refit_observation* observations,
+                  l3d_association* associations, l3d_refit_summary* summary);
+void l3d_refit_close(l3d_refit*);
+/* Host only: the span stage's arithmetic for one camera (K, R are read) and one 2D segment (x1, y1, x2, y2), by the function
+ * the device runs: the parameters s of the segment's two end points along M + s u as seen from the centre Q (all three about
+ * the model's centre), ordered.  Returns 1: valid, 0: not (s_lo = s_hi = 0), -1: a null pointer. */
+int l3d_refit_span(const l3d_camera* cam, const float seg4[4], const double M[3], const double u[3], const double Q[3],
+                   double* s_lo, double* s_hi);
+/* Host only: the sweep of stage 9 over n spans [s_lo, s_hi] with their cameras: pieces [2 x n at most] receives (s_start,
+ * s_end) of the kept pieces in ascending s, *n_pieces their number; u_norm = |u| turns parameters into lengths.
+ * L3D_ERR_ARG for a null pointer, visibility 0, or min_length / u_norm negative or not finite. */
+int l3d_refit_sweep(uint32_t n, const double* s_lo, const double* s_hi, const uint32_t* camera, uint32_t visibility,
+                    double min_length, double u_norm, double* pieces, uint32_t* n_pieces);
+
 #ifdef __cplusplus
 }
 #endif

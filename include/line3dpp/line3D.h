@@ -15,6 +15,7 @@
 //     mergeLines(max_distance, max_angle, min_overlap)                           (... and their near-duplicates merged)
 //     alignLines(other, similarity, summary, max_distance, start_distance, ...)  (... and aligned to a model in another frame)
 //     refineCameras(cameras, summaries, max_distance, start_distance, ...)       (... and the views' poses refined against them)
+//     refitLines(cameras, max_distance, max_angle, min_overlap, visibility, ...) (... and the lines refit against the views' segments)
 //     wireframe(max_distance, max_extension, min_angle)                          (... and where they meet: junctions, vertices, edges)
 //     detectPlanes(max_distance, junction_distance, junction_extension, min_angle, ...)   (... and the planes they lie in)
 //     detectDirections(max_angle, min_length, min_segments, max_directions, max_tests, frame_angle)   (... the directions they run in)
@@ -619,6 +620,46 @@ public:
             summaries[ids[k]] = sums[k];
             if (associations) (*associations)[ids[k]].assign(assoc.begin() + (size_t)off[k], assoc.begin() + (size_t)off[k + 1]);
         }
+    }
+
+    // This model refit against the views (no reference counterpart; DESIGN §28, k_refit.hip): every line of the last
+    // reconstruct3Dlines is re-estimated from the 2D segments of the added views (or of the views camIDs) that observe it
+    // within max_distance pixels -- in `cameras` (by camID; null or a missing camID: the view's own, e.g. what
+    // refineCameras returned) -- by the solver of the line bundling, and cut anew where at least `visibility` views see
+    // it.  The refit model takes the place of lines3D_, as mergeLines' does; a line that cannot be refit stays as it is.
+    // Saved files carry REFIT_<max_distance>__ in their name until the next reconstruct3Dlines.  summary (may be null):
+    // the counts of the refit.  Errors are printed and leave the model as it was.
+    void refitLines(const std::map<unsigned int, l3d_camera>* cameras = nullptr, const double max_distance = 2.5,
+                    const double max_angle = 10.0, const double min_overlap = 0.5, const unsigned int visibility = 3,
+                    const unsigned int max_iterations = 50, const bool use_ambiguous = false, const double min_length = 0.0,
+                    const std::vector<unsigned int>* camIDs = nullptr, l3d_refit_summary* summary = nullptr,
+                    const double near_plane = 1e-6) {
+        if (!(max_angle >= 0.0 && max_angle <= 90.0)) {
+            std::cout << prefix_err_ << "refitLines: max_angle must lie in [0, 90] degrees" << std::endl;
+            return;
+        }
+        const double cosine = std::cos(max_angle * (3.14159265358979323846 / 180.0));
+        const l3d_refit_params par{max_distance, cosine * cosine, min_overlap, near_plane, min_length, visibility, max_iterations,
+                                   use_ambiguous ? 1u : 0u, {0u, 0u, 0u}};
+        std::vector<uint32_t> ids;
+        if (camIDs) ids.assign(camIDs->begin(), camIDs->end());
+        else {
+            std::lock_guard<std::mutex> lk(lines_mu_);
+            for (const auto& kv : num_lines_) ids.push_back(kv.first);
+        }
+        std::vector<l3d_camera> cams(ids.size() + 1);
+        for (size_t k = 0; k < ids.size(); ++k) {
+            if (cameras) {
+                const auto f = cameras->find(ids[k]);
+                if (f != cameras->end()) { cams[k] = f->second; continue; }
+            }
+            if (l3d_view_camera(ctx_, ids[k], &cams[k]) != L3D_OK) {
+                std::cout << prefix_err_ << "refitLines: " << l3d_last_error() << std::endl;
+                return;
+            }
+        }
+        if (l3d_refit_view_lines(ctx_, (uint32_t)ids.size(), ids.data(), cams.data(), &par, summary, nullptr) != L3D_OK)
+            std::cout << prefix_err_ << "refitLines: " << l3d_last_error() << std::endl;
     }
 
     // The near-duplicate lines of this model merged (no reference counterpart; DESIGN §19, k_merge.hip): lines joined by

@@ -52,6 +52,14 @@ POSE_ITERATION_DTYPE = np.dtype([("gate", "<f8"), ("sums", "<f8", 29), ("delta",
                                  ("n_matched", "<u8")])
 assert POSE_SUMMARY_DTYPE.itemsize == 88 and POSE_ITERATION_DTYPE.itemsize == 392
 POSE_STATUS = ALIGN_STATUS
+# l3d_refit_line, l3d_refit_observation: a line of a refit model, a 2D segment that observes one
+REFIT_LINE_DTYPE = np.dtype([("status", "<u4"), ("n_observations", "<u4"), ("n_views", "<u4"), ("solver_status", "<u4"),
+                             ("iterations", "<u4"), ("n_pieces", "<u4"), ("cost0", "<f8"), ("cost1", "<f8"), ("x0", "<f8", 4),
+                             ("x", "<f8", 4), ("P1", "<f8", 3), ("P2", "<f8", 3)])
+REFIT_OBSERVATION_DTYPE = np.dtype([("camera", "<u4"), ("segment", "<u4"), ("line", "<u4"), ("valid", "<u4"), ("s_lo", "<f8"),
+                                    ("s_hi", "<f8")])
+assert REFIT_LINE_DTYPE.itemsize == 152 and REFIT_OBSERVATION_DTYPE.itemsize == 32
+REFIT_STATUS = ("REFIT", "TOO_FEW_VIEWS", "CONSTANT", "FAILED", "NO_EXTENT", "EMPTY")
 # l3d_merge_line_info: one line of a merged model
 MERGE_LINE_INFO_DTYPE = np.dtype([("n_members", "<u4"), ("label", "<u4"), ("max_offset", "<f8")])
 assert MERGE_LINE_INFO_DTYPE.itemsize == 16
@@ -264,6 +272,20 @@ class PoseParams(C.Structure):
                 ("reserved", C.c_uint32 * 2)]
 
 
+class RefitParams(C.Structure):
+    """l3d_refit_params (include/l3dpp_hip.h)"""
+    _fields_ = [("max_distance", C.c_double), ("min_cos2", C.c_double), ("min_overlap", C.c_double), ("near_plane", C.c_double),
+                ("min_length", C.c_double), ("visibility", C.c_uint32), ("max_iterations", C.c_uint32),
+                ("use_ambiguous", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class RefitSummary(C.Structure):
+    """l3d_refit_summary (include/l3dpp_hip.h)"""
+    _fields_ = [("n_lines", C.c_uint64), ("n_status", C.c_uint64 * 6), ("n_observations", C.c_uint64),
+                ("n_ambiguous_left_out", C.c_uint64), ("n_segments_before", C.c_uint64), ("n_segments_after", C.c_uint64),
+                ("cost0", C.c_double), ("cost1", C.c_double)]
+
+
 class AlignSummary(C.Structure):
     """l3d_align_summary (include/l3dpp_hip.h)"""
     _fields_ = [("status", C.c_uint32), ("iterations", C.c_uint32), ("n_matched", C.c_uint64), ("rms", C.c_double),
@@ -378,6 +400,8 @@ EXPORTS = [
     "l3d_plane_segments", "l3d_plane_lines", "l3d_planes_counts", "l3d_planes_get", "l3d_planes_save_obj", "l3d_planes_close",
     "l3d_direction_segments", "l3d_direction_lines", "l3d_directions_counts", "l3d_directions_get", "l3d_directions_save_obj",
     "l3d_directions_close",
+    "l3d_refit_segments", "l3d_refit_view_lines", "l3d_refit_counts", "l3d_refit_get", "l3d_refit_close", "l3d_refit_span",
+    "l3d_refit_sweep",
 ]
 
 _lib = None
@@ -546,6 +570,13 @@ def load():
     L.l3d_directions_get.argtypes = [vp, vp, vp, vp, vp, C.POINTER(DirectionsSummary)]
     L.l3d_directions_save_obj.argtypes = [vp, C.c_char_p]
     L.l3d_directions_close.argtypes = [vp]; L.l3d_directions_close.restype = None
+    L.l3d_refit_segments.argtypes = [i32, u32, vp, vp, u32, vp, vp, vp, C.POINTER(RefitParams), C.POINTER(vp)]
+    L.l3d_refit_view_lines.argtypes = [vp, u32, vp, vp, C.POINTER(RefitParams), C.POINTER(RefitSummary), C.POINTER(vp)]
+    L.l3d_refit_counts.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+    L.l3d_refit_get.argtypes = [vp, vp, vp, vp, vp, vp, C.POINTER(RefitSummary)]
+    L.l3d_refit_close.argtypes = [vp]; L.l3d_refit_close.restype = None
+    L.l3d_refit_span.argtypes = [vp, vp, vp, vp, vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.l3d_refit_sweep.argtypes = [u32, vp, vp, vp, u32, C.c_double, C.c_double, vp, C.POINTER(u32)]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("l3d_last_error", "l3d_build_info", "l3d_create", "l3d_destroy"):

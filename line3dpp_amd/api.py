@@ -16,7 +16,8 @@ import numpy as np
 
 from . import _lib, lsd
 from ._lib import (ALIGN_ITERATION_DTYPE, ALIGN_STATUS, ASSOCIATION_DTYPE, CLEDGE_DTYPE, EMPTY, FLOAT4_DTYPE, LINE_MATCH_DTYPE, MATCH_DTYPE, MERGE_LINE_INFO_DTYPE,
-                   POSE_ITERATION_DTYPE, POSE_STATUS, POSE_SUMMARY_DTYPE, PROJECTED_SEGMENT_DTYPE, SEGMENT2D_DTYPE,
+                   POSE_ITERATION_DTYPE, POSE_STATUS, POSE_SUMMARY_DTYPE, PROJECTED_SEGMENT_DTYPE, REFIT_LINE_DTYPE,
+                   REFIT_OBSERVATION_DTYPE, REFIT_STATUS, SEGMENT2D_DTYPE,
                    SEGMENT3D_DTYPE, SLOT_DTYPE, MatchParams, Timings, ptr)
 
 # commons.h:40-70
@@ -47,6 +48,7 @@ class Line3D:
         self.verbose = verbose
         self.last_status = 0
         self._M = {}
+        self.device = int(device)
         self.stream = int(stream)          # the hipStream_t every launch of this context goes to (dist.py: ordering of collectives)
         self.h = self.L.l3d_create(int(device), C.c_void_p(stream))
         if not self.h:
@@ -610,6 +612,67 @@ class Line3D:
         res = out.result()
         res["camIDs"] = [int(c) for c in ids]
         return res
+
+    # ---- this model refit against the views (no reference counterpart) --------------------------------------
+    def refitLines(self, camIDs=None, cameras=None, max_distance=L3D_DEF_SCORING_POS_REGULARIZER,
+                   max_angle=L3D_DEF_SCORING_ANG_REGULARIZER, min_overlap=0.5, near=1e-6, min_length=0.0,
+                   visibility=L3D_DEF_MIN_VISIBILITY_T, max_iterations=50, use_ambiguous=False):
+        """the 3D lines of the last reconstruct3Dlines re-estimated from the segments of the views camIDs (None: all,
+        ascending) that observe them, in `cameras` (camera dicts in that order; None: the views' own), and cut anew ->
+        the dict of refit_segments with `camIDs` beside it; None after an error.  The refit model TAKES THE PLACE of the
+        context's lines, as mergeLines' does; outputFilename carries REFIT_<max_distance>__ until the next
+        reconstruct3Dlines."""
+        ids = np.ascontiguousarray(sorted(self._M) if camIDs is None else list(camIDs), np.uint32).reshape(-1)
+        try:
+            par = refit_params(max_distance, max_angle, min_overlap, near, min_length, visibility, max_iterations, use_ambiguous)
+            if cameras is not None and len(cameras) != len(ids):
+                raise ValueError("one camera per view")
+            arr = camera_array(list(cameras)) if cameras is not None else None
+        except (ValueError, KeyError, TypeError) as e:
+            print(f"{self.PREFIX}ERROR: refitLines: {e}")
+            self.last_status = -1
+            return None
+        h = C.c_void_p(); s = _lib.RefitSummary()
+        if not self._check(self.L.l3d_refit_view_lines(self.h, len(ids), ptr(ids), arr, C.byref(par), C.byref(s), C.byref(h)), "refitLines"):
+            return None
+        res = take_refit(h, None)
+        res["camIDs"] = [int(c) for c in ids]
+        return res
+
+    def refineModel(self, rounds=3, camIDs=None, max_distance=L3D_DEF_SCORING_POS_REGULARIZER, start_distance=0.0, **kw):
+        """refine_model on the 3D lines of the last reconstruct3Dlines and the views camIDs (None: all, ascending) with
+        their own cameras and segments (kw: refine_model's) -> its dict, with `camIDs` beside it; None after an error.
+        Every round refines the cameras against the context's lines as they stand and then refits those lines in the
+        cameras just returned (refitLines), so the context holds the model of the last round that ran; the views keep
+        their cameras.  After an error in round k (None is returned) the context is left with the model of round k - 1,
+        its file names tagged REFIT_ if a round before refit a line; an error in round 0 leaves it as it was."""
+        ids = [int(c) for c in (sorted(self._M) if camIDs is None else camIDs)]
+        pose_kw = {k: kw[k] for k in ("max_angle", "min_overlap", "stall_tolerance", "step_tolerance", "min_matches", "near") if k in kw}
+        refit_kw = {k: kw[k] for k in ("max_angle", "min_overlap", "near", "min_length", "visibility", "use_ambiguous") if k in kw}
+        try:
+            unknown = set(kw) - set(pose_kw) - set(refit_kw) - {"pose_iterations", "refit_iterations"}
+            if unknown:
+                raise TypeError(f"unknown arguments {sorted(unknown)}")
+            cams = [self.viewCamera(c) for c in ids]
+            if any(c is None for c in cams):
+                raise ValueError("unknown camera ID")
+            obs = [np.array([self.getSegmentCoords2D(c, s) for s in range(self._M[c])], np.float32).reshape(-1, 4) for c in ids]
+            per_round, fit = [], None
+            for r in range(int(rounds)):
+                segs, line = flatten_lines(self.get3Dlines())
+                pose = refine_cameras(segs, line, cams, obs, max_distance=max_distance, start_distance=start_distance if r == 0 else 0.0,
+                                      max_iterations=kw.get("pose_iterations", 50), device=self.device, **pose_kw)
+                cams = pose["cameras"]
+                fit = self.refitLines(ids, cams, max_distance=max_distance, max_iterations=kw.get("refit_iterations", 50), **refit_kw)
+                if fit is None:
+                    return None
+                per_round.append((pose["summaries"], fit["summary"]))
+        except (ValueError, KeyError, TypeError, RuntimeError) as e:
+            print(f"{self.PREFIX}ERROR: refineModel: {e}")
+            self.last_status = -1
+            return None
+        segs, line = flatten_lines(self.get3Dlines())
+        return dict(cameras=cams, segments=segs, line=line, rounds=per_round, refit=fit, camIDs=ids)
 
     def set_projection_budget(self, n_bytes):
         """test hook: device-memory budget of a group of cameras in the four calls above (0: the default)"""
@@ -1419,6 +1482,91 @@ def refine_cameras(segs, line, cams, segs_per_cam, max_distance=L3D_DEF_SCORING_
     if rc != 0:
         raise RuntimeError(f"l3d_refine_cameras failed [{rc}]: {_lib.last_error()}")
     return out.result()
+
+
+def refit_params(max_distance=L3D_DEF_SCORING_POS_REGULARIZER, max_angle=L3D_DEF_SCORING_ANG_REGULARIZER, min_overlap=0.5,
+                 near=1e-6, min_length=0.0, visibility=L3D_DEF_MIN_VISIBILITY_T, max_iterations=50, use_ambiguous=False):
+    """l3d_refit_params from the wrappers' arguments, by associate_params' degree rule; max_distance in pixels, min_length
+    in world units"""
+    p = associate_params(max_distance, max_angle, min_overlap)
+    return _lib.RefitParams(p.max_distance, p.min_cos2, p.min_overlap, float(near), float(min_length), int(visibility),
+                            int(max_iterations), int(bool(use_ambiguous)), (0, 0, 0))
+
+
+def refit_summary_dict(s):
+    return dict(n_lines=int(s.n_lines), status={name: int(s.n_status[k]) for k, name in enumerate(REFIT_STATUS)},
+                n_observations=int(s.n_observations), n_ambiguous_left_out=int(s.n_ambiguous_left_out),
+                n_segments_before=int(s.n_segments_before), n_segments_after=int(s.n_segments_after), cost0=float(s.cost0),
+                cost1=float(s.cost1))
+
+
+def take_refit(h, n_seg_per_cam):
+    """the contents of an l3d_refit handle as a dict, and the handle closed: segments [n, 6] and line [n] (the output
+    model), lines (REFIT_LINE_DTYPE, one per line index; `status` an index into REFIT_STATUS), observations
+    (REFIT_OBSERVATION_DTYPE, line after line), associations (ASSOCIATION_DTYPE; one array per camera where the counts are
+    known) and the summary"""
+    L = _lib.load()
+    try:
+        n = [C.c_uint64() for _ in range(4)]
+        L.l3d_refit_counts(h, *[C.byref(v) for v in n])
+        ns, nl, no, na = (int(v.value) for v in n)
+        segs = np.zeros((max(ns, 1), 6), np.float64); line = np.zeros(max(ns, 1), np.uint32)
+        lines = np.zeros(max(nl, 1), REFIT_LINE_DTYPE); obs = np.zeros(max(no, 1), REFIT_OBSERVATION_DTYPE)
+        assoc = np.zeros(max(na, 1), ASSOCIATION_DTYPE)
+        s = _lib.RefitSummary()
+        L.l3d_refit_get(h, ptr(segs), ptr(line), ptr(lines), ptr(obs), ptr(assoc), C.byref(s))
+    finally:
+        L.l3d_refit_close(h)
+    assoc = assoc[:na]
+    return dict(segments=segs[:ns], line=line[:ns], lines=lines[:nl], observations=obs[:no],
+                associations=split_records(assoc, n_seg_per_cam) if n_seg_per_cam is not None else assoc,
+                summary=refit_summary_dict(s))
+
+
+def refit_segments(segs, line, cams, segs_per_cam, max_distance=L3D_DEF_SCORING_POS_REGULARIZER,
+                   max_angle=L3D_DEF_SCORING_ANG_REGULARIZER, min_overlap=0.5, near=1e-6, min_length=0.0,
+                   visibility=L3D_DEF_MIN_VISIBILITY_T, max_iterations=50, use_ambiguous=False, device=0):
+    """l3d_refit_segments: every line of the model (segs [n, 6] float64 with a line index each) re-estimated
+    from the 2D segments that observe it in `cams` (dicts K, R, t, width, height; segs_per_cam: one float32 [M, 4] array
+    per camera) and cut anew -> the dict of take_refit.  A line that is not REFIT keeps its segments bit for bit."""
+    L = _lib.load()
+    s = np.ascontiguousarray(segs, np.float64).reshape(-1, 6); ln = np.ascontiguousarray(line, np.uint32).reshape(-1)
+    if len(ln) != len(s):
+        raise ValueError("one line index per segment")
+    if len(cams) != len(segs_per_cam):
+        raise ValueError("one array of segments per camera")
+    seg = [np.ascontiguousarray(v, np.float32).reshape(-1, 4) for v in segs_per_cam]
+    n_seg = np.array([len(v) for v in seg] + [0], np.uint32)
+    seg4 = np.concatenate(seg + [np.zeros((1, 4), np.float32)])
+    par = refit_params(max_distance, max_angle, min_overlap, near, min_length, visibility, max_iterations, use_ambiguous)
+    arr = camera_array(list(cams))
+    h = C.c_void_p()
+    rc = L.l3d_refit_segments(int(device), len(s), ptr(s), ptr(ln), len(cams), arr, ptr(n_seg), ptr(seg4), C.byref(par), C.byref(h))
+    if rc != 0:
+        raise RuntimeError(f"l3d_refit_segments failed [{rc}]: {_lib.last_error()}")
+    return take_refit(h, [int(v) for v in n_seg[:len(cams)]])
+
+
+def refine_model(segs, line, cams, segs_per_cam, rounds=3, max_distance=L3D_DEF_SCORING_POS_REGULARIZER, start_distance=0.0,
+                 max_angle=L3D_DEF_SCORING_ANG_REGULARIZER, min_overlap=0.5, near=1e-6, min_length=0.0,
+                 visibility=L3D_DEF_MIN_VISIBILITY_T, pose_iterations=50, refit_iterations=50, min_matches=8,
+                 stall_tolerance=1e-4, step_tolerance=1e-9, use_ambiguous=False, device=0):
+    """cameras and lines refined in turn, K fixed (bundle adjustment over lines): every round is refine_cameras against the
+    model as it stands, then refit_segments in the cameras just returned; start_distance applies in the first round only
+    -> a dict: cameras, segments and line (the model after the last round), rounds (one (pose summaries, refit summary)
+    pair per round) and the last round's refit dict as `refit`"""
+    model, ml = np.ascontiguousarray(segs, np.float64).reshape(-1, 6), np.ascontiguousarray(line, np.uint32).reshape(-1)
+    cams = list(cams)
+    per_round, fit = [], None
+    for r in range(int(rounds)):
+        pose = refine_cameras(model, ml, cams, segs_per_cam, max_distance, start_distance if r == 0 else 0.0, max_angle, min_overlap,
+                              stall_tolerance, step_tolerance, pose_iterations, min_matches, near, device)
+        cams = pose["cameras"]
+        fit = refit_segments(model, ml, cams, segs_per_cam, max_distance, max_angle, min_overlap, near, min_length, visibility,
+                             refit_iterations, use_ambiguous, device)
+        model, ml = fit["segments"], fit["line"]
+        per_round.append((pose["summaries"], fit["summary"]))
+    return dict(cameras=cams, segments=model, line=ml, rounds=per_round, refit=fit)
 
 
 def transform_segments(segs, similarity):

@@ -260,6 +260,15 @@ unsigned long long l3d_debug_counter(const char* name) {
     if (name && std::string(name) == "pose_iterations") return g_pose_iterations.load(std::memory_order_relaxed);
     if (name && std::string(name) == "pose_normal_launches") return g_pose_normal_launches.load(std::memory_order_relaxed);
     if (name && std::string(name) == "pose_kernel_ns") return g_pose_kernel_ns.load(std::memory_order_relaxed);
+    if (name && std::string(name) == "refit_observations") return g_refit_observations.load(std::memory_order_relaxed);
+    if (name && std::string(name) == "refit_lines_solved") return g_refit_lines_solved.load(std::memory_order_relaxed);
+    if (name && std::string(name) == "refit_kernel_ns") return g_refit_kernel_ns.load(std::memory_order_relaxed);
+    {
+        // the parts of refit_kernel_ns: projection + association, observation list, k_refit_obs, k_lineopt, k_refit_spans
+        static const char* const kParts[5] = {"refit_associate_ns", "refit_list_ns", "refit_obs_ns", "refit_lineopt_ns", "refit_spans_ns"};
+        for (int k = 0; k < 5; ++k)
+            if (name && std::string(name) == kParts[k]) return g_refit_part_ns[k].load(std::memory_order_relaxed);
+    }
     if (name && std::string(name) == "wf_count_launches") return g_wf_count_launches.load(std::memory_order_relaxed);
     if (name && std::string(name) == "wf_write_launches") return g_wf_write_launches.load(std::memory_order_relaxed);
     if (name && std::string(name) == "wf_slices") return g_wf_slices.load(std::memory_order_relaxed);

@@ -124,6 +124,7 @@ int ensure_affinity_host(::l3d_ctx* c);    // l3d_affinity_host.hip
 std::string output_filename(::l3d_ctx* c, int max_image_width);   // l3d_output.hip
 // l3d_lineopt.hip: LineOptimizer::optimize on clusters3D_ (translated frame), and its parametrisation / write-back
 int line_opt(::l3d_ctx* c, const std::map<uint32_t, const HostView*>& views, std::vector<ReconCluster>& clusters, uint32_t max_iter);
+uint32_t lo_work_order(const uint32_t* res_off, std::vector<uint32_t>& order, uint32_t narrow_max);   // k_lineopt's work order; returns n_wide
 bool line_to_cayley(const d3& P1, const d3& P2, double x[4]);
 bool cayley_to_segment(const double x[4], const d3& P1_old, const d3& P2_old, d3& P1, d3& P2);
 
@@ -357,6 +358,8 @@ struct l3d_ctx {
     bool lines_done = false;
     bool lines_merged = false;                      // l3d_merge_lines has replaced lines3D since the last reconstruct3Dlines
     double merged_distance = 0.0;                   // ... with this max_distance (l3d_output_filename)
+    bool lines_refit = false;                       // l3d_refit_view_lines has replaced lines3D since the last reconstruct3Dlines
+    double refit_distance = 0.0;                    // ... with this max_distance (l3d_output_filename)
     // line bundling (use_CERES_ of the last reconstruct3Dlines; l3d_lineopt.hip)
     bool use_ceres = false;
     l3d_line_opt_summary lo_stats{};

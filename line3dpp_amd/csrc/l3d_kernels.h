@@ -497,4 +497,8 @@ hipError_t launch_pose_bounds(AssocCam* cams, uint32_t n_cams, const uint32_t* b
 // l3d_pose.hip, test hooks read through l3d_debug_counter
 extern std::atomic<uint64_t> g_pose_iterations, g_pose_normal_launches, g_pose_kernel_ns;
 
+// ---- k_refit.hip: the 3D lines refit against cameras and their 2D segments (host side: l3d_refit.hip; the
+// kernels' arguments: l3d_refit.h).  l3d_refit.hip, test hooks read through l3d_debug_counter ----
+extern std::atomic<uint64_t> g_refit_observations, g_refit_lines_solved, g_refit_kernel_ns, g_refit_part_ns[5];
+
 }  // namespace l3d

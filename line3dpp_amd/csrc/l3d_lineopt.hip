@@ -89,20 +89,27 @@ namespace {
 size_t up64(size_t b) { return (b + 63) & ~(size_t)63; }
 }
 
-// The per-line solves of `order` (indices into x0 / res_off, in the caller's order): the work order -- a stable sort by
-// residual count, longest first, so lines of equal count keep the caller's order; the first n_wide, with more than
-// narrow_max (<= 16) residuals, take a wave each, the others a 16-lane group -- then one packed upload, one launch of
-// k_lineopt and one download through the caller's buffers.  `order` comes back sorted, *out points at the results by
-// line index (inside hb; only the lines of `order` are written).  ev: an event pair recorded around the launch, or null.
-int lo_solve_lines(PinnedBuf<char>& hb, DevBuf<char>& db, hipStream_t stream, hipEvent_t* ev, const std::vector<LoCam>& cams,
-                   const std::vector<LoObs>& obs, const std::vector<double>& x0, const std::vector<uint32_t>& res_off,
-                   std::vector<uint32_t>& order, uint32_t narrow_max, uint32_t max_iter, uint32_t* n_wide_out, const LoOut** out) {
-    const size_t nl = x0.size() / 4;
-    // work order: one-wave lines (more than narrow_max residuals) first, both classes longest first
+// The work order of a launch of k_lineopt over the lines of `order` (indices into res_off, in the caller's order): a
+// stable sort by residual count, longest first, so lines of equal count keep the caller's order; the first n_wide (the
+// value returned), with more than narrow_max (<= kLoNarrow) residuals, take a wave each, the others a 16-lane group.
+// Shared by the line bundling and the refit of §28 (l3d_refit.hip).
+uint32_t lo_work_order(const uint32_t* res_off, std::vector<uint32_t>& order, uint32_t narrow_max) {
     auto cnt = [&](uint32_t i) { return res_off[i + 1] - res_off[i]; };
     std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return cnt(a) > cnt(b); });
     uint32_t n_wide = 0;
     while (n_wide < order.size() && cnt(order[n_wide]) > narrow_max) ++n_wide;
+    return n_wide;
+}
+
+// The per-line solves of `order` (indices into x0 / res_off, in the caller's order): the work order (lo_work_order), then
+// one packed upload, one launch of k_lineopt and one download through the caller's buffers.  `order` comes back sorted,
+// *out points at the results by line index (inside hb; only the lines of `order` are written).  ev: an event pair
+// recorded around the launch, or null.
+int lo_solve_lines(PinnedBuf<char>& hb, DevBuf<char>& db, hipStream_t stream, hipEvent_t* ev, const std::vector<LoCam>& cams,
+                   const std::vector<LoObs>& obs, const std::vector<double>& x0, const std::vector<uint32_t>& res_off,
+                   std::vector<uint32_t>& order, uint32_t narrow_max, uint32_t max_iter, uint32_t* n_wide_out, const LoOut** out) {
+    const size_t nl = x0.size() / 4;
+    const uint32_t n_wide = lo_work_order(res_off.data(), order, narrow_max);
     *n_wide_out = n_wide;
     // one packed upload: cameras | observations | start parameters | CSR | order; then the results
     const size_t o_cam = 0, o_obs = up64(o_cam + cams.size() * sizeof(LoCam)), o_x = up64(o_obs + obs.size() * sizeof(LoObs));
