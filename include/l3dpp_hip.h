@@ -1527,6 +1527,99 @@ int l3d_refit_span(const l3d_camera* cam, const float seg4[4], const double M[3]
 int l3d_refit_sweep(uint32_t n, const double* s_lo, const double* s_hi, const uint32_t* camera, uint32_t visibility,
                     double min_length, double u_norm, double* pieces, uint32_t* n_pieces);
 
+/* ---- cameras and 3D lines bundled jointly (GPU: k_bundle.hip, and unchanged k_project.hip's stage 1, k_scan.hip,
+ * k_associate.hip, k_refit.hip) --------------------------------------------------------------------------------------------
+ * No reference counterpart.  Given a model, cameras and each camera's 2D segments as l3d_refit_segments takes them, ONE
+ * association at max_distance, then Levenberg-Marquardt jointly over 6 pose parameters of every free camera and 4
+ * parameters of every eligible line on that fixed observation set, Huber(2) on every observation: the lines are eliminated
+ * by a Schur complement on the device, the reduced camera system is solved on the host (dense: at most 512 free cameras).
+ * Then the lines' segments are cut anew as l3d_refit_segments cuts them.  A line is ELIGIBLE iff it has a segment, its
+ * carrier is not a point and at least max(2, visibility) cameras observe it; every other observed line is HELD: constant, but
+ * its observations constrain their cameras.  A camera is FREE iff its byte of `fixed` is 0 and it observes a line.  fp64,
+ * the contract of DESIGN §29.  Re-association between calls is the caller's (the Python driver bundle_model). */
+typedef struct l3d_bundle_params {   /* 104 bytes */
+    double max_distance;         /* as in l3d_associate_params */
+    double min_cos2;
+    double min_overlap;
+    double near_plane;           /* finite, > 0: of the projection */
+    double min_length;           /* finite, >= 0, world units: a shorter piece is not kept */
+    double initial_damping;      /* mu of the first iteration, in [min_damping, max_damping]; 1e-4 */
+    double min_damping;          /* finite, > 0: the floor of mu; 1e-9 */
+    double max_damping;          /* finite, >= min_damping: a rejected step that takes mu past it ends the call STALLED; 1e8 */
+    double function_tolerance;   /* finite, >= 0: an accepted step that gains no more than this share of the cost: CONVERGED; 1e-6 */
+    uint32_t visibility;         /* >= 1: cameras that must see a piece; a line needs max(2, visibility) cameras to be eligible */
+    uint32_t max_iterations;     /* 0 .. 256; 0 cuts the extents anew about the unchanged carriers */
+    uint32_t use_ambiguous;      /* 0: a 2D segment that accepted more than one record is left out; 1: it is used */
+    uint32_t capture_iteration;  /* test item: 0 none, k: the handle keeps the reduced system of the k-th iteration */
+    uint32_t reserved[4];        /* must be 0 */
+} l3d_bundle_params;
+enum { L3D_BUNDLE_BUNDLED = 0, L3D_BUNDLE_HELD = 1, L3D_BUNDLE_NO_EXTENT = 2, L3D_BUNDLE_EMPTY = 3 };
+enum { L3D_BUNDLE_CONVERGED = 0, L3D_BUNDLE_MAX_ITERATIONS = 1, L3D_BUNDLE_STALLED = 2, L3D_BUNDLE_NO_VARIABLES = 3 };
+/* one per line index 0 .. max(line) (64 bytes) */
+typedef struct l3d_bundle_line {
+    uint32_t status;             /* L3D_BUNDLE_*: HELD too few views, a point for a carrier; NO_EXTENT took part, but the sweep
+                                  * kept no piece; EMPTY no segment */
+    uint32_t n_observations;     /* 2D segments that observe the line */
+    uint32_t n_views;            /* its cells: distinct cameras among them */
+    uint32_t n_pieces;           /* segments of the line in the output model */
+    double P1[3], P2[3];         /* the carrier in the model's frame: as given, or, for an eligible line of a call that
+                                  * accepted a step, the new one */
+} l3d_bundle_line;
+/* one per iteration run (56 bytes) */
+typedef struct l3d_bundle_iteration {
+    double damping;              /* mu of the iteration */
+    double cost, cost_trial;     /* the robust cost in force and at the trial step (0 where the system was not solved) */
+    double step_cameras;         /* |delta_c|inf over the free cameras */
+    double step_lines;           /* |delta_l|inf over the eligible lines */
+    uint32_t solved;             /* 0: a pivot of the reduced system failed (a rejected step) */
+    uint32_t accepted;
+    uint32_t n_held_for_step;    /* eligible lines whose own 4 x 4 pivot failed at this mu */
+    uint32_t pad;
+} l3d_bundle_iteration;
+/* (144 bytes) */
+typedef struct l3d_bundle_summary {
+    uint32_t status;             /* L3D_BUNDLE_CONVERGED .. ; NO_VARIABLES: no eligible line and no free camera */
+    uint32_t iterations, accepted_steps, rejected_steps;
+    double cost0, cost1;         /* sum of rho over the observations before and after */
+    double damping;              /* mu as the call left it */
+    uint64_t n_observations, n_cells, n_eligible_lines, n_free_cameras, n_lines;
+    uint64_t n_status[4];        /* lines per L3D_BUNDLE_* line status */
+    uint64_t n_ambiguous_left_out, n_segments_before, n_segments_after;
+    uint32_t captured;           /* 1: the system of capture_iteration is in the handle */
+    uint32_t reserved;
+} l3d_bundle_summary;
+typedef struct l3d_bundle l3d_bundle;
+/* Stateless, host pointers; the model, the cameras and the 2D segments as for l3d_refit_segments (K01 = 0 as there: the
+ * spans are §28's); fixed [n_cams] bytes 0 / 1 or NULL: none is fixed.  The result lives in a handle: *out, to be closed by
+ * l3d_bundle_close.  Every line that is not BUNDLED keeps its segments bit for bit; a camera that no accepted step moved
+ * comes back bit for bit.  Checked before any device work, *out untouched: what l3d_refit_segments checks, with
+ * max_iterations above 256, a damping or a tolerance outside its range, capture_iteration above 256 and a byte of `fixed`
+ * above 1 as L3D_ERR_ARG; more than 512 cameras that are not fixed, or lines x cameras of 2^28 or more, as L3D_ERR_LIMIT.
+ * An empty model, zero cameras or no 2D segment at all: L3D_OK, everything as given, no launch. */
+int l3d_bundle_segments(int device, uint32_t n_segments, const double* segs6, const uint32_t* line, uint32_t n_cams,
+                        const l3d_camera* cams, const uint8_t* fixed, const uint32_t* n_segments_per_cam, const float* segs4,
+                        const l3d_bundle_params* params, l3d_bundle** out);
+/* The same on the context's lines with the added views camIDs (each once) and their own segments, on the context's stream;
+ * cams [n_views] or NULL: the views' own.  The bundled model TAKES THE PLACE of the context's lines as l3d_refit_view_lines'
+ * does (l3d_output_filename carries "BUNDLE_<max_distance>__"); the cameras come back through the handle and the views'
+ * cameras are NOT changed.  summary and out may be NULL.  L3D_ERR_STATE / L3D_ERR_ARG as l3d_refit_view_lines. */
+int l3d_bundle_view_lines(l3d_ctx*, uint32_t n_views, const uint32_t* camIDs, const l3d_camera* cams, const uint8_t* fixed,
+                          const l3d_bundle_params* params, l3d_bundle_summary* summary, l3d_bundle** out);
+/* the sizes of the output model, the lines, the observations, the associations (= the 2D segments), the cameras, the trace
+ * and the captured system's side n (0: none); any may be NULL */
+int l3d_bundle_counts(const l3d_bundle*, uint64_t* n_segments, uint64_t* n_lines, uint64_t* n_observations, uint64_t* n_associations,
+                      uint64_t* n_cameras, uint64_t* n_iterations, uint64_t* n_system);
+/* segs6 / seg_line: the output model; lines; observations (l3d_refit_observation: the spans along the new carriers);
+ * associations; cams [n_cameras]; trace [n_iterations]; system [n x n] (the upper triangle is set, the free cameras in
+ * ascending index, 6 rows each) and rhs [n] (g: the step solves S delta = -g).  Any pointer may be NULL */
+int l3d_bundle_get(const l3d_bundle*, double* segs6, uint32_t* seg_line, l3d_bundle_line* lines, l3d_refit_observation* observations,
+                   l3d_association* associations, l3d_camera* cams, l3d_bundle_iteration* trace, double* system, double* rhs,
+                   l3d_bundle_summary* summary);
+void l3d_bundle_close(l3d_bundle*);
+/* Host only: the stage's dense Cholesky solve of S delta = -g, S [n x n] symmetric of which the upper triangle is read.
+ * Returns 1: solved, 0: a pivot that is not finite and > 0 (delta untouched), -1: a null pointer or no memory. */
+int l3d_bundle_solve(uint32_t n, const double* S, const double* g, double* delta);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,7 @@
 //     alignLines(other, similarity, summary, max_distance, start_distance, ...)  (... and aligned to a model in another frame)
 //     refineCameras(cameras, summaries, max_distance, start_distance, ...)       (... and the views' poses refined against them)
 //     refitLines(cameras, max_distance, max_angle, min_overlap, visibility, ...) (... and the lines refit against the views' segments)
+//     bundleModel(cameras, max_distance, max_angle, min_overlap, visibility, ...) (cameras and lines bundled jointly)
 //     wireframe(max_distance, max_extension, min_angle)                          (... and where they meet: junctions, vertices, edges)
 //     detectPlanes(max_distance, junction_distance, junction_extension, min_angle, ...)   (... and the planes they lie in)
 //     detectDirections(max_angle, min_length, min_segments, max_directions, max_tests, frame_angle)   (... the directions they run in)
@@ -660,6 +661,59 @@ public:
         }
         if (l3d_refit_view_lines(ctx_, (uint32_t)ids.size(), ids.data(), cams.data(), &par, summary, nullptr) != L3D_OK)
             std::cout << prefix_err_ << "refitLines: " << l3d_last_error() << std::endl;
+    }
+
+    // This model and the views' cameras bundled jointly (no reference counterpart; DESIGN §29, k_bundle.hip): one
+    // association of the lines of the last reconstruct3Dlines with the 2D segments of the added views (or of the views
+    // camIDs) within max_distance pixels, in `cameras` (by camID; null or a missing camID: the view's own), then
+    // Levenberg-Marquardt jointly over the poses of the cameras that are not in `fixed` and the lines that at least
+    // max(2, visibility) views see, and the lines cut anew.  The bundled model takes the place of lines3D_, as refitLines'
+    // does; saved files carry BUNDLE_<max_distance>__ in their name until the next reconstruct3Dlines.  The new cameras are
+    // written into `cameras` where it is given (every camID of the call); the views keep theirs.  summary (may be null): the
+    // counts of the call.  Errors are printed and leave the model and `cameras` as they were.
+    void bundleModel(std::map<unsigned int, l3d_camera>* cameras = nullptr, const double max_distance = 2.5,
+                     const double max_angle = 10.0, const double min_overlap = 0.5, const unsigned int visibility = 3,
+                     const unsigned int max_iterations = 10, const bool use_ambiguous = false, const double min_length = 0.0,
+                     const std::vector<unsigned int>* camIDs = nullptr, const std::vector<unsigned int>* fixed = nullptr,
+                     l3d_bundle_summary* summary = nullptr, const double near_plane = 1e-6) {
+        if (!(max_angle >= 0.0 && max_angle <= 90.0)) {
+            std::cout << prefix_err_ << "bundleModel: max_angle must lie in [0, 90] degrees" << std::endl;
+            return;
+        }
+        const double cosine = std::cos(max_angle * (3.14159265358979323846 / 180.0));
+        const l3d_bundle_params par{max_distance, cosine * cosine, min_overlap, near_plane, min_length, 1e-4, 1e-9, 1e8, 1e-6,
+                                    visibility, max_iterations, use_ambiguous ? 1u : 0u, 0u, {0u, 0u, 0u, 0u}};
+        std::vector<uint32_t> ids;
+        if (camIDs) ids.assign(camIDs->begin(), camIDs->end());
+        else {
+            std::lock_guard<std::mutex> lk(lines_mu_);
+            for (const auto& kv : num_lines_) ids.push_back(kv.first);
+        }
+        std::vector<l3d_camera> cams(ids.size() + 1);
+        std::vector<uint8_t> fix(ids.size() + 1, 0);
+        for (size_t k = 0; k < ids.size(); ++k) {
+            if (fixed)
+                for (const unsigned int id : *fixed)
+                    if (id == ids[k]) fix[k] = 1;
+            if (cameras) {
+                const auto f = cameras->find(ids[k]);
+                if (f != cameras->end()) { cams[k] = f->second; continue; }
+            }
+            if (l3d_view_camera(ctx_, ids[k], &cams[k]) != L3D_OK) {
+                std::cout << prefix_err_ << "bundleModel: " << l3d_last_error() << std::endl;
+                return;
+            }
+        }
+        l3d_bundle* h = nullptr;
+        if (l3d_bundle_view_lines(ctx_, (uint32_t)ids.size(), ids.data(), cams.data(), fix.data(), &par, summary, &h) != L3D_OK) {
+            std::cout << prefix_err_ << "bundleModel: " << l3d_last_error() << std::endl;
+            return;
+        }
+        if (cameras) {
+            l3d_bundle_get(h, nullptr, nullptr, nullptr, nullptr, nullptr, cams.data(), nullptr, nullptr, nullptr, nullptr);
+            for (size_t k = 0; k < ids.size(); ++k) (*cameras)[ids[k]] = cams[k];
+        }
+        l3d_bundle_close(h);
     }
 
     // The near-duplicate lines of this model merged (no reference counterpart; DESIGN §19, k_merge.hip): lines joined by

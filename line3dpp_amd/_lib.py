@@ -60,6 +60,15 @@ REFIT_OBSERVATION_DTYPE = np.dtype([("camera", "<u4"), ("segment", "<u4"), ("lin
                                     ("s_hi", "<f8")])
 assert REFIT_LINE_DTYPE.itemsize == 152 and REFIT_OBSERVATION_DTYPE.itemsize == 32
 REFIT_STATUS = ("REFIT", "TOO_FEW_VIEWS", "CONSTANT", "FAILED", "NO_EXTENT", "EMPTY")
+# l3d_bundle_line, l3d_bundle_iteration: a line of a bundled model, one iteration of a call's trace
+BUNDLE_LINE_DTYPE = np.dtype([("status", "<u4"), ("n_observations", "<u4"), ("n_views", "<u4"), ("n_pieces", "<u4"),
+                              ("P1", "<f8", 3), ("P2", "<f8", 3)])
+BUNDLE_ITERATION_DTYPE = np.dtype([("damping", "<f8"), ("cost", "<f8"), ("cost_trial", "<f8"), ("step_cameras", "<f8"),
+                                   ("step_lines", "<f8"), ("solved", "<u4"), ("accepted", "<u4"), ("n_held_for_step", "<u4"),
+                                   ("pad", "<u4")])
+assert BUNDLE_LINE_DTYPE.itemsize == 64 and BUNDLE_ITERATION_DTYPE.itemsize == 56
+BUNDLE_LINE_STATUS = ("BUNDLED", "HELD", "NO_EXTENT", "EMPTY")
+BUNDLE_STATUS = ("CONVERGED", "MAX_ITERATIONS", "STALLED", "NO_VARIABLES")
 # l3d_merge_line_info: one line of a merged model
 MERGE_LINE_INFO_DTYPE = np.dtype([("n_members", "<u4"), ("label", "<u4"), ("max_offset", "<f8")])
 assert MERGE_LINE_INFO_DTYPE.itemsize == 16
@@ -286,6 +295,24 @@ class RefitSummary(C.Structure):
                 ("cost0", C.c_double), ("cost1", C.c_double)]
 
 
+class BundleParams(C.Structure):
+    """l3d_bundle_params (include/l3dpp_hip.h)"""
+    _fields_ = [("max_distance", C.c_double), ("min_cos2", C.c_double), ("min_overlap", C.c_double), ("near_plane", C.c_double),
+                ("min_length", C.c_double), ("initial_damping", C.c_double), ("min_damping", C.c_double),
+                ("max_damping", C.c_double), ("function_tolerance", C.c_double), ("visibility", C.c_uint32),
+                ("max_iterations", C.c_uint32), ("use_ambiguous", C.c_uint32), ("capture_iteration", C.c_uint32),
+                ("reserved", C.c_uint32 * 4)]
+
+
+class BundleSummary(C.Structure):
+    """l3d_bundle_summary (include/l3dpp_hip.h)"""
+    _fields_ = [("status", C.c_uint32), ("iterations", C.c_uint32), ("accepted_steps", C.c_uint32), ("rejected_steps", C.c_uint32),
+                ("cost0", C.c_double), ("cost1", C.c_double), ("damping", C.c_double), ("n_observations", C.c_uint64),
+                ("n_cells", C.c_uint64), ("n_eligible_lines", C.c_uint64), ("n_free_cameras", C.c_uint64), ("n_lines", C.c_uint64),
+                ("n_status", C.c_uint64 * 4), ("n_ambiguous_left_out", C.c_uint64), ("n_segments_before", C.c_uint64),
+                ("n_segments_after", C.c_uint64), ("captured", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class AlignSummary(C.Structure):
     """l3d_align_summary (include/l3dpp_hip.h)"""
     _fields_ = [("status", C.c_uint32), ("iterations", C.c_uint32), ("n_matched", C.c_uint64), ("rms", C.c_double),
@@ -402,6 +429,7 @@ EXPORTS = [
     "l3d_directions_close",
     "l3d_refit_segments", "l3d_refit_view_lines", "l3d_refit_counts", "l3d_refit_get", "l3d_refit_close", "l3d_refit_span",
     "l3d_refit_sweep",
+    "l3d_bundle_segments", "l3d_bundle_view_lines", "l3d_bundle_counts", "l3d_bundle_get", "l3d_bundle_close", "l3d_bundle_solve",
 ]
 
 _lib = None
@@ -577,6 +605,12 @@ def load():
     L.l3d_refit_close.argtypes = [vp]; L.l3d_refit_close.restype = None
     L.l3d_refit_span.argtypes = [vp, vp, vp, vp, vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.l3d_refit_sweep.argtypes = [u32, vp, vp, vp, u32, C.c_double, C.c_double, vp, C.POINTER(u32)]
+    L.l3d_bundle_segments.argtypes = [i32, u32, vp, vp, u32, vp, vp, vp, vp, C.POINTER(BundleParams), C.POINTER(vp)]
+    L.l3d_bundle_view_lines.argtypes = [vp, u32, vp, vp, vp, C.POINTER(BundleParams), C.POINTER(BundleSummary), C.POINTER(vp)]
+    L.l3d_bundle_counts.argtypes = [vp] + [C.POINTER(u64)] * 7
+    L.l3d_bundle_get.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(BundleSummary)]
+    L.l3d_bundle_close.argtypes = [vp]; L.l3d_bundle_close.restype = None
+    L.l3d_bundle_solve.argtypes = [u32, vp, vp, vp]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("l3d_last_error", "l3d_build_info", "l3d_create", "l3d_destroy"):

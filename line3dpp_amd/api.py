@@ -10,12 +10,14 @@ bench and torch.distributed plumbing -- the C++ facade over the same C-ABI is
 include/line3dpp/line3D.h.
 """
 import ctypes as C
+import math
 import threading
 
 import numpy as np
 
 from . import _lib, lsd
 from ._lib import (ALIGN_ITERATION_DTYPE, ALIGN_STATUS, ASSOCIATION_DTYPE, CLEDGE_DTYPE, EMPTY, FLOAT4_DTYPE, LINE_MATCH_DTYPE, MATCH_DTYPE, MERGE_LINE_INFO_DTYPE,
+                   BUNDLE_ITERATION_DTYPE, BUNDLE_LINE_DTYPE, BUNDLE_LINE_STATUS, BUNDLE_STATUS,
                    POSE_ITERATION_DTYPE, POSE_STATUS, POSE_SUMMARY_DTYPE, PROJECTED_SEGMENT_DTYPE, REFIT_LINE_DTYPE,
                    REFIT_OBSERVATION_DTYPE, REFIT_STATUS, SEGMENT2D_DTYPE,
                    SEGMENT3D_DTYPE, SLOT_DTYPE, MatchParams, Timings, ptr)
@@ -673,6 +675,39 @@ class Line3D:
             return None
         segs, line = flatten_lines(self.get3Dlines())
         return dict(cameras=cams, segments=segs, line=line, rounds=per_round, refit=fit, camIDs=ids)
+
+    # ---- this model and the views' cameras bundled jointly (no reference counterpart) ------------------------
+    def bundleModel(self, camIDs=None, cameras=None, fixed=None, rounds=1, max_distance=L3D_DEF_SCORING_POS_REGULARIZER, **kw):
+        """the 3D lines of the last reconstruct3Dlines and the cameras of the views camIDs (None: all, ascending; `cameras`:
+        camera dicts in that order, None: the views' own) bundled jointly from the views' segments, `rounds` times, each
+        round on the cameras the round before returned (kw: bundle_params') -> the dict of bundle_segments of the last
+        round with `camIDs` and `rounds` (one summary per round) beside it; None after an error.  The bundled model TAKES
+        THE PLACE of the context's lines; outputFilename carries BUNDLE_<max_distance>__ until the next
+        reconstruct3Dlines.  The cameras come back in the dict: the views keep theirs."""
+        ids = np.ascontiguousarray(sorted(self._M) if camIDs is None else list(camIDs), np.uint32).reshape(-1)
+        res, per_round = None, []
+        for _ in range(int(rounds)):
+            try:
+                par = bundle_params(max_distance, **kw)
+                if cameras is not None and len(cameras) != len(ids):
+                    raise ValueError("one camera per view")
+                arr = camera_array(list(cameras)) if cameras is not None else None
+                fx = _fixed_bytes(fixed, len(ids))
+            except (ValueError, KeyError, TypeError) as e:
+                print(f"{self.PREFIX}ERROR: bundleModel: {e}")
+                self.last_status = -1
+                return None
+            h = C.c_void_p(); s = _lib.BundleSummary()
+            if not self._check(self.L.l3d_bundle_view_lines(self.h, len(ids), ptr(ids), arr, ptr(fx) if fx is not None else None,
+                                                            C.byref(par), C.byref(s), C.byref(h)), "bundleModel"):
+                return None
+            res = take_bundle(h, None)
+            cameras = res["cameras"]
+            per_round.append(res["summary"])
+        if res is not None:
+            res["camIDs"] = [int(c) for c in ids]
+            res["rounds"] = per_round
+        return res
 
     def set_projection_budget(self, n_bytes):
         """test hook: device-memory budget of a group of cameras in the four calls above (0: the default)"""
@@ -1567,6 +1602,160 @@ def refine_model(segs, line, cams, segs_per_cam, rounds=3, max_distance=L3D_DEF_
         model, ml = fit["segments"], fit["line"]
         per_round.append((pose["summaries"], fit["summary"]))
     return dict(cameras=cams, segments=model, line=ml, rounds=per_round, refit=fit)
+
+
+def bundle_params(max_distance=L3D_DEF_SCORING_POS_REGULARIZER, max_angle=L3D_DEF_SCORING_ANG_REGULARIZER, min_overlap=0.5,
+                  near=1e-6, min_length=0.0, visibility=L3D_DEF_MIN_VISIBILITY_T, max_iterations=10, use_ambiguous=False,
+                  initial_damping=1e-4, min_damping=1e-9, max_damping=1e8, function_tolerance=1e-6, capture_iteration=0):
+    """l3d_bundle_params from the wrappers' arguments, by associate_params' degree rule; max_distance in pixels, min_length
+    in world units"""
+    p = associate_params(max_distance, max_angle, min_overlap)
+    return _lib.BundleParams(p.max_distance, p.min_cos2, p.min_overlap, float(near), float(min_length), float(initial_damping),
+                             float(min_damping), float(max_damping), float(function_tolerance), int(visibility),
+                             int(max_iterations), int(bool(use_ambiguous)), int(capture_iteration), (0, 0, 0, 0))
+
+
+def bundle_summary_dict(s):
+    return dict(status=BUNDLE_STATUS[s.status], iterations=int(s.iterations), accepted_steps=int(s.accepted_steps),
+                rejected_steps=int(s.rejected_steps), cost0=float(s.cost0), cost1=float(s.cost1), damping=float(s.damping),
+                n_observations=int(s.n_observations), n_cells=int(s.n_cells), n_eligible_lines=int(s.n_eligible_lines),
+                n_free_cameras=int(s.n_free_cameras), n_lines=int(s.n_lines),
+                lines={name: int(s.n_status[k]) for k, name in enumerate(BUNDLE_LINE_STATUS)},
+                n_ambiguous_left_out=int(s.n_ambiguous_left_out), n_segments_before=int(s.n_segments_before),
+                n_segments_after=int(s.n_segments_after), captured=bool(s.captured))
+
+
+def take_bundle(h, n_seg_per_cam):
+    """the contents of an l3d_bundle handle as a dict, and the handle closed: segments [n, 6] and line [n] (the output
+    model), lines (BUNDLE_LINE_DTYPE; `status` an index into BUNDLE_LINE_STATUS), observations (REFIT_OBSERVATION_DTYPE),
+    associations, cameras (dicts), trace (BUNDLE_ITERATION_DTYPE), system [n, n] and rhs [n] of the captured iteration
+    (None where none was kept) and the summary"""
+    L = _lib.load()
+    try:
+        n = [C.c_uint64() for _ in range(7)]
+        L.l3d_bundle_counts(h, *[C.byref(v) for v in n])
+        ns, nl, no, na, nc, ni, nsys = (int(v.value) for v in n)
+        segs = np.zeros((max(ns, 1), 6), np.float64); line = np.zeros(max(ns, 1), np.uint32)
+        lines = np.zeros(max(nl, 1), BUNDLE_LINE_DTYPE); obs = np.zeros(max(no, 1), REFIT_OBSERVATION_DTYPE)
+        assoc = np.zeros(max(na, 1), ASSOCIATION_DTYPE); cams = (_lib.Camera * max(nc, 1))()
+        trace = np.zeros(max(ni, 1), BUNDLE_ITERATION_DTYPE)
+        system = np.zeros((max(nsys, 1), max(nsys, 1)), np.float64); rhs = np.zeros(max(nsys, 1), np.float64)
+        s = _lib.BundleSummary()
+        L.l3d_bundle_get(h, ptr(segs), ptr(line), ptr(lines), ptr(obs), ptr(assoc), cams, ptr(trace), ptr(system), ptr(rhs), C.byref(s))
+    finally:
+        L.l3d_bundle_close(h)
+    assoc = assoc[:na]
+    return dict(segments=segs[:ns], line=line[:ns], lines=lines[:nl], observations=obs[:no],
+                associations=split_records(assoc, n_seg_per_cam) if n_seg_per_cam is not None else assoc,
+                cameras=[camera_dict(cams[k]) for k in range(nc)], trace=trace[:ni],
+                system=system[:nsys, :nsys] if s.captured else None, rhs=rhs[:nsys] if s.captured else None,
+                summary=bundle_summary_dict(s))
+
+
+def _fixed_bytes(fixed, n):
+    if fixed is None:
+        return None
+    f = np.ascontiguousarray(fixed, np.uint8).reshape(-1)
+    if len(f) != n:
+        raise ValueError("one byte of `fixed` per camera")
+    return np.concatenate([f, np.zeros(1, np.uint8)])
+
+
+def bundle_segments(segs, line, cams, segs_per_cam, fixed=None, max_distance=L3D_DEF_SCORING_POS_REGULARIZER,
+                    max_angle=L3D_DEF_SCORING_ANG_REGULARIZER, min_overlap=0.5, near=1e-6, min_length=0.0,
+                    visibility=L3D_DEF_MIN_VISIBILITY_T, max_iterations=10, use_ambiguous=False, initial_damping=1e-4,
+                    min_damping=1e-9, max_damping=1e8, function_tolerance=1e-6, capture_iteration=0, device=0):
+    """l3d_bundle_segments: one association of the model (segs [n, 6] float64 with a line index each) with the
+    2D segments of `cams` (dicts K, R, t, width, height; segs_per_cam: one float32 [M, 4] array per camera), then
+    Levenberg-Marquardt jointly over the poses of the cameras that are not `fixed` (one 0 / 1 per camera; None: none) and
+    the lines that enough cameras see, and the lines' segments cut anew -> the dict of take_bundle"""
+    L = _lib.load()
+    s = np.ascontiguousarray(segs, np.float64).reshape(-1, 6); ln = np.ascontiguousarray(line, np.uint32).reshape(-1)
+    if len(ln) != len(s):
+        raise ValueError("one line index per segment")
+    if len(cams) != len(segs_per_cam):
+        raise ValueError("one array of segments per camera")
+    seg = [np.ascontiguousarray(v, np.float32).reshape(-1, 4) for v in segs_per_cam]
+    n_seg = np.array([len(v) for v in seg] + [0], np.uint32)
+    seg4 = np.concatenate(seg + [np.zeros((1, 4), np.float32)])
+    par = bundle_params(max_distance, max_angle, min_overlap, near, min_length, visibility, max_iterations, use_ambiguous,
+                        initial_damping, min_damping, max_damping, function_tolerance, capture_iteration)
+    fx = _fixed_bytes(fixed, len(cams))
+    arr = camera_array(list(cams))
+    h = C.c_void_p()
+    rc = L.l3d_bundle_segments(int(device), len(s), ptr(s), ptr(ln), len(cams), arr, ptr(fx) if fx is not None else None, ptr(n_seg),
+                               ptr(seg4), C.byref(par), C.byref(h))
+    if rc != 0:
+        raise RuntimeError(f"l3d_bundle_segments failed [{rc}]: {_lib.last_error()}")
+    return take_bundle(h, [int(v) for v in n_seg[:len(cams)]])
+
+
+def _rotation_of(q):
+    """R(q) of a quaternion (w, x, y, z), normalised first"""
+    w, x, y, z = (float(v) for v in np.asarray(q, np.float64) / np.linalg.norm(q))
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                     [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                     [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+
+
+def transform_cameras(cams, similarity):
+    """the cameras (dicts) that see a model moved by x' = s R_s x + t_s as they saw it before: R' = R R_s^T,
+    t' = s t - R' t_s (K, width, height unchanged); numpy on the host -> a list of camera dicts"""
+    if not isinstance(similarity, dict):
+        similarity = similarity_from_matrix(similarity)
+    Rs = _rotation_of(similarity["q"])
+    ts = np.asarray(similarity["t"], np.float64).reshape(3); scale = float(similarity["scale"])
+    out = []
+    for c in cams:
+        R = np.asarray(c["R"], np.float64).reshape(3, 3) @ Rs.T
+        t = scale * np.asarray(c["t"], np.float64).reshape(3) - R @ ts
+        out.append(dict(K=np.array(c["K"], np.float64).reshape(3, 3), R=R, t=t, width=int(c["width"]), height=int(c["height"])))
+    return out
+
+
+def camera_centres(cams):
+    """[n, 3]: -R^T t of every camera dict"""
+    return np.array([-(np.asarray(c["R"], np.float64).reshape(3, 3).T @ np.asarray(c["t"], np.float64).reshape(3)) for c in cams]).reshape(-1, 3)
+
+
+def bundle_model(segs, line, cams, segs_per_cam, rounds=3, keep_gauge=True, fixed=None, **kw):
+    """cameras and lines bundled jointly over `rounds` rounds: each round is one bundle_segments -- one
+    association, then the joint solve on it -- on the previous round's cameras and model (kw: bundle_segments').  Nothing
+    but the damping holds the 7-parameter gauge, so with keep_gauge and no fixed camera the driver finishes with the
+    similarity that takes the new camera centres back onto the input's -- similarity_from_points' rotation, the scale and
+    the translation that restore the centres' scatter and mean exactly --, applied to the model (transform_segments) and to
+    the cameras (transform_cameras); with fewer than three cameras it skips that and says so
+    -> a dict: cameras, segments, line, rounds (one summary per round), bundle (the last round's dict), gauge (the
+    similarity applied, or None) and gauge_skipped (why not, or None)"""
+    model, ml = np.ascontiguousarray(segs, np.float64).reshape(-1, 6), np.ascontiguousarray(line, np.uint32).reshape(-1)
+    cams = list(cams)
+    cams0 = cams
+    per_round, fit = [], None
+    for _ in range(int(rounds)):
+        fit = bundle_segments(model, ml, cams, segs_per_cam, fixed, **kw)
+        cams, model, ml = fit["cameras"], fit["segments"], fit["line"]
+        per_round.append(fit["summary"])
+    gauge, skipped = None, None
+    if keep_gauge and fit is not None:
+        if fixed is not None and np.any(np.asarray(fixed)):
+            skipped = "a camera is fixed"
+        elif len(cams) < 3:
+            skipped = "fewer than three cameras"
+        else:
+            try:
+                src, dst = camera_centres(cams), camera_centres(cams0)
+                gauge = similarity_from_points(src, dst)
+                # the rotation is the least-squares one; scale and translation are set so that the scatter and the mean of
+                # the centres come back exactly (the least-squares scale falls short by the misfit)
+                ms, md = src.mean(0), dst.mean(0)
+                gauge["scale"] = math.sqrt(float(((dst - md) ** 2).sum()) / float(((src - ms) ** 2).sum()))
+                gauge["t"] = md - gauge["scale"] * (_rotation_of(gauge["q"]) @ ms)
+            except (ValueError, ZeroDivisionError, np.linalg.LinAlgError) as e:
+                gauge, skipped = None, str(e)
+        if gauge is not None:
+            model = transform_segments(model, gauge)
+            cams = transform_cameras(cams, gauge)
+    return dict(cameras=cams, segments=model, line=ml, rounds=per_round, bundle=fit, gauge=gauge, gauge_skipped=skipped)
 
 
 def transform_segments(segs, similarity):

@@ -269,6 +269,9 @@ unsigned long long l3d_debug_counter(const char* name) {
         for (int k = 0; k < 5; ++k)
             if (name && std::string(name) == kParts[k]) return g_refit_part_ns[k].load(std::memory_order_relaxed);
     }
+    if (name && std::string(name) == "bundle_iterations") return g_bundle_iterations.load(std::memory_order_relaxed);
+    if (name && std::string(name) == "bundle_rejected_steps") return g_bundle_rejected_steps.load(std::memory_order_relaxed);
+    if (name && std::string(name) == "bundle_kernel_ns") return g_bundle_kernel_ns.load(std::memory_order_relaxed);
     if (name && std::string(name) == "wf_count_launches") return g_wf_count_launches.load(std::memory_order_relaxed);
     if (name && std::string(name) == "wf_write_launches") return g_wf_write_launches.load(std::memory_order_relaxed);
     if (name && std::string(name) == "wf_slices") return g_wf_slices.load(std::memory_order_relaxed);

@@ -390,7 +390,7 @@ int l3d_reconstruct_3d_lines(l3d_ctx* c, uint32_t visibility_t, int perform_diff
     const unsigned vis = std::max<unsigned>(visibility_t, 3);
     c->visibility_t = vis; c->perform_rdd = perform_diffusion != 0;
     c->lines3D.clear();
-    c->lines_merged = false; c->lines_refit = false;
+    c->lines_merged = false; c->lines_refit = false; c->lines_bundled = false;
     const Translated frame(*c);
     int rc = affinity_core(c);
     // matrix diffusion (performRDD, line3D.cc:1787-1791) on the device-resident A_

@@ -492,7 +492,7 @@ int l3d_match_begin(l3d_ctx* c, const l3d_match_params* p) {
     else { c->fixed3Dregularizer = false; c->sigma_p = std::fmax(0.1f, c->sigma_p); }
     c->affinity_done = false; c->aff_rec_mode = -1;
     c->lines_done = false;
-    c->lines_merged = false; c->lines_refit = false;
+    c->lines_merged = false; c->lines_refit = false; c->lines_bundled = false;
     c->n_hyps = 0;
     // line3D.cc:426-433
     c->med_scene_depth = c->const_regularization_depth;

@@ -360,6 +360,8 @@ struct l3d_ctx {
     double merged_distance = 0.0;                   // ... with this max_distance (l3d_output_filename)
     bool lines_refit = false;                       // l3d_refit_view_lines has replaced lines3D since the last reconstruct3Dlines
     double refit_distance = 0.0;                    // ... with this max_distance (l3d_output_filename)
+    bool lines_bundled = false;                     // l3d_bundle_view_lines has replaced lines3D since the last reconstruct3Dlines
+    double bundle_distance = 0.0;                   // ... with this max_distance (l3d_output_filename)
     // line bundling (use_CERES_ of the last reconstruct3Dlines; l3d_lineopt.hip)
     bool use_ceres = false;
     l3d_line_opt_summary lo_stats{};

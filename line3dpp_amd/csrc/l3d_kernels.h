@@ -501,4 +501,8 @@ extern std::atomic<uint64_t> g_pose_iterations, g_pose_normal_launches, g_pose_k
 // kernels' arguments: l3d_refit.h).  l3d_refit.hip, test hooks read through l3d_debug_counter ----
 extern std::atomic<uint64_t> g_refit_observations, g_refit_lines_solved, g_refit_kernel_ns, g_refit_part_ns[5];
 
+// ---- k_bundle.hip: cameras and 3D lines bundled jointly (host side: l3d_bundle.hip; the kernels' arguments:
+// l3d_bundle.h).  l3d_bundle.hip, test hooks read through l3d_debug_counter ----
+extern std::atomic<uint64_t> g_bundle_iterations, g_bundle_rejected_steps, g_bundle_kernel_ns;
+
 }  // namespace l3d

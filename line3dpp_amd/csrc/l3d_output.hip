@@ -25,6 +25,7 @@ std::string output_filename(l3d_ctx* c, int max_image_width) {
     if (c->use_ceres) str << "OPTIMIZED__";   // the lines were bundled (l3d_lineopt.hip)
     if (c->lines_merged) str << "MERGED_" << c->merged_distance << "__";   // near-duplicate lines merged (l3d_merge.hip)
     if (c->lines_refit) str << "REFIT_" << c->refit_distance << "__";      // lines refit against the views (l3d_refit.hip)
+    if (c->lines_bundled) str << "BUNDLE_" << c->bundle_distance << "__";  // lines bundled with the cameras (l3d_bundle.hip)
     str << "vis_" << c->visibility_t;
     return str.str();
 }

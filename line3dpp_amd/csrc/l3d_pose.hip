@@ -15,6 +15,7 @@
 #include <atomic>
 
 #include "l3d_ctx.h"
+#include "l3d_pose.h"
 
 namespace l3d {
 // test hooks (l3d_debug_counter): iterations run (summed over the cameras) and launches of k_pose_normal so far, and the
@@ -54,11 +55,6 @@ int check_pose_cameras(uint32_t n_cams, const l3d_camera* cams, double near_plan
     return L3D_OK;
 }
 
-void normalise(double q[4]) {
-    const double n = std::sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
-    for (int i = 0; i < 4; ++i) q[i] = q[i] / n;
-}
-
 // midpoint c and diagonal of the bounding box of the n > 0 segments' end points (§23's)
 void bounding_box(size_t n, const double* segs, double c[3], double& diag) {
     double lo[3] = {segs[0], segs[1], segs[2]}, hi[3] = {segs[0], segs[1], segs[2]};
@@ -73,53 +69,13 @@ void bounding_box(size_t n, const double* segs, double c[3], double& diag) {
     diag = std::sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
 }
 
-// one camera's state: the delta (q, tau) on the input pose, t'_in = t_in + R_in c, the gate and how far it has come
-struct CamState {
-    double q[4] = {1.0, 0.0, 0.0, 0.0}, tau[3] = {0.0, 0.0, 0.0}, tin[3] = {0.0, 0.0, 0.0};
+// one camera's state: the delta (q, tau) on the input pose and t'_in = t_in + R_in c (l3d_pose.h), the gate and how far
+// it has come
+struct CamState : PoseDelta {
     double gate = 0.0, last_step = 0.0;
     uint32_t status = L3D_POSE_TOO_FEW, iterations = 0;
-    bool done = true, updated = false;
+    bool done = true;
 };
-
-// R = R(q^) R_in and t' = R(q^) t'_in + tau: the pose in the frame about c
-void pose_about_centre(const l3d_camera& in, const CamState& s, double R[9], double tc[3]) {
-    double qh[4] = {s.q[0], s.q[1], s.q[2], s.q[3]}, Rd[9];
-    normalise(qh);
-    sim_rotation(qh, Rd);
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) R[3 * i + j] = (Rd[3 * i] * in.R[j] + Rd[3 * i + 1] * in.R[3 + j]) + Rd[3 * i + 2] * in.R[6 + j];
-    const d3 u = mul33(Rd, d3{s.tin[0], s.tin[1], s.tin[2]});
-    tc[0] = u.x + s.tau[0]; tc[1] = u.y + s.tau[1]; tc[2] = u.z + s.tau[2];
-}
-
-// the camera as it is handed out: the input, bit for bit, while no update has been made; else K, R and t = t' - R c
-l3d_camera camera_now(const l3d_camera& in, const CamState& s, const double c[3]) {
-    if (!s.updated) return in;
-    l3d_camera out = in;
-    double tc[3];
-    pose_about_centre(in, s, out.R, tc);
-    const d3 rc = mul33(out.R, d3{c[0], c[1], c[2]});
-    out.t[0] = tc[0] - rc.x; out.t[1] = tc[1] - rc.y; out.t[2] = tc[2] - rc.z;
-    return out;
-}
-
-// step 5's update of the delta: q <- dq (x) q, normalised; tau <- dR tau + delta_3..5
-void update(CamState& s, const double delta[6]) {
-    double dq[4] = {1.0, delta[0] * 0.5, delta[1] * 0.5, delta[2] * 0.5};
-    normalise(dq);
-    double dR[9];
-    sim_rotation(dq, dR);
-    const double* q = s.q;
-    double qn[4] = {((dq[0] * q[0] - dq[1] * q[1]) - dq[2] * q[2]) - dq[3] * q[3],
-                    ((dq[0] * q[1] + dq[1] * q[0]) + dq[2] * q[3]) - dq[3] * q[2],
-                    ((dq[0] * q[2] - dq[1] * q[3]) + dq[2] * q[0]) + dq[3] * q[1],
-                    ((dq[0] * q[3] + dq[1] * q[2]) - dq[2] * q[1]) + dq[3] * q[0]};
-    normalise(qn);
-    const d3 u = mul33(dR, d3{s.tau[0], s.tau[1], s.tau[2]});
-    for (int i = 0; i < 4; ++i) s.q[i] = qn[i];
-    s.tau[0] = u.x + delta[3]; s.tau[1] = u.y + delta[4]; s.tau[2] = u.z + delta[5];
-    s.updated = true;
-}
 
 // H delta = -b from the 29 sums (n = 6), by the alignment's Cholesky.  false: a pivot that is not finite and > 0
 bool solve_normal(const double* s, double delta[6]) {
@@ -139,15 +95,6 @@ double step_of(const double delta[6], double diag) {
         s = std::max(s, std::fabs(delta[3 + i]) / diag);
     }
     return s;
-}
-
-// the entries m00, m10, m11, m20, m21 of K^-T for an upper-triangular K with K22 = 1
-void inverse_transpose(const double* K, double M[5]) {
-    M[0] = 1.0 / K[0];
-    M[2] = 1.0 / K[4];
-    M[1] = -((K[1] * M[0]) * M[2]);
-    M[3] = -(K[2] * M[0]) - K[5] * M[1];
-    M[4] = -(K[5] * M[2]);
 }
 
 struct Job {
@@ -269,7 +216,7 @@ int refine_core(ProjWork& w, hipStream_t st, const Job& J, const l3d_pose_params
                 ProjCam pc;
                 std::memcpy(pc.K, in.K, 72);
                 if (final) {
-                    const l3d_camera now = camera_now(in, s, c);
+                    const l3d_camera now = pose_camera_now(in, s, c);
                     std::memcpy(pc.R, now.R, 72); std::memcpy(pc.t, now.t, 24);
                 } else {
                     pose_about_centre(in, s, pc.R, pc.t);
@@ -277,7 +224,7 @@ int refine_core(ProjWork& w, hipStream_t st, const Job& J, const l3d_pose_params
                 pc.xmax = (double)(in.width - 1); pc.ymax = (double)(in.height - 1);
                 pcam[i] = pc;
                 PoseCam po;
-                inverse_transpose(in.K, po.M);
+                pose_inverse_transpose(in.K, po.M);
                 std::memcpy(po.R, pc.R, 72); std::memcpy(po.t, pc.t, 24);
                 pose[i] = po;
                 const double gate = final ? p.max_distance : s.gate;
@@ -348,7 +295,7 @@ int refine_core(ProjWork& w, hipStream_t st, const Job& J, const l3d_pose_params
                 else if (!solve_normal(sm, delta)) { s.status = L3D_POSE_DEGENERATE; s.done = true; }
                 else solved = true;
                 if (solved) {
-                    update(s, delta);
+                    pose_update(s, delta);
                     s.last_step = step_of(delta, diag);
                     std::memcpy(tr.delta, delta, sizeof(delta));
                     if (s.gate == p.max_distance && s.last_step <= p.step_tolerance) { s.status = L3D_POSE_CONVERGED; s.done = true; }
@@ -359,7 +306,7 @@ int refine_core(ProjWork& w, hipStream_t st, const Job& J, const l3d_pose_params
                     }
                 }
                 if (o.trace) {
-                    const l3d_camera now = camera_now(J.cams[k], s, c);
+                    const l3d_camera now = pose_camera_now(J.cams[k], s, c);
                     std::memcpy(tr.R, now.R, 72); std::memcpy(tr.t, now.t, 24);
                     trace[(size_t)k * p.max_iterations + it] = tr;
                 }
@@ -372,7 +319,7 @@ int refine_core(ProjWork& w, hipStream_t st, const Job& J, const l3d_pose_params
             if (J.n_seg[k]) act.push_back(k);
         if (!act.empty() && (e = pass(true)) != hipSuccess) break;
         for (uint32_t k = G.c0; k < G.c1; ++k) {
-            out_cams[k] = camera_now(J.cams[k], state[k], c);
+            out_cams[k] = pose_camera_now(J.cams[k], state[k], c);
             l3d_pose_summary sm{};
             sm.status = state[k].status; sm.iterations = state[k].iterations; sm.last_step = state[k].last_step;
             for (int i = 0; i < 4; ++i) sm.q[i] = state[k].q[i];

@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "../../include/l3dpp_hip.h"
 #include "l3d_kernels.h"
 #include "l3d_lineopt.h"
 
@@ -104,5 +105,53 @@ struct RefitObsArgs {
 };
 hipError_t launch_refit_obs(const RefitObsArgs& a, hipStream_t st);
 hipError_t launch_refit_spans(const RefitObsArgs& a, hipStream_t st);
+
+// ---- host (l3d_refit.hip): stages 1 to 3, shared with the joint bundle of DESIGN §29 (l3d_bundle.hip) ----
+struct ProjWork;               // l3d_ctx.h
+struct RefitJob {
+    uint32_t n_model; const double* segs; const uint32_t* line;
+    uint32_t n_cams; const l3d_camera* cams; const uint32_t* n_seg; const float* const* seg;
+};
+// What the stages leave behind.  On the device (offsets into w.d, kept until the caller overwrites them): the model as
+// given at o_P, its line indices at o_line, every camera's float4 segments at o_segs, their first indices [n_cams + 1]
+// at o_begin, the flat 2D segment of every observation at o_oseg; the caller's own tables go at keep_end and behind, up
+// to `bound` = up256(keep_end) + tail_bytes, which w.h and w.d hold.
+struct RefitObserved {
+    std::vector<uint32_t> seg_begin;             // [n_cams + 1]
+    uint32_t S = 0, n_obs = 0;                   // 2D segments, observations
+    size_t o_P = 0, o_line = 0, o_segs = 0, o_begin = 0, o_oseg = 0, keep_end = 0, bound = 0;
+    std::vector<l3d_association> assoc;          // [S] as they are handed out
+    uint64_t n_ambiguous_left_out = 0;
+    std::vector<uint32_t> oseg, oline;           // [n_obs] in flat order: the flat 2D segment, the line
+    std::vector<uint32_t> obs_off, csr;          // [n_lines + 1]; [n_obs] the observation at a CSR position
+};
+// Arguments already checked; model, cameras and 2D segments non-empty.  `who` opens the messages ("refit", "bundle");
+// ms_assoc / ms_list (may be null): the time of the launches of stage 2 and of stage 3.
+int refit_observe(ProjWork& w, hipStream_t st, const RefitJob& J, double max_distance, double min_cos2, double min_overlap, double near_plane,
+                  uint32_t use_ambiguous, uint32_t n_lines, size_t tail_bytes, const char* who, float* ms_assoc, float* ms_list,
+                  RefitObserved& O);
+
+// the near plane, the cameras' sides and entries as stage 1 checks them, and the form of K that LoCam can hold
+int check_refit_cameras(uint32_t n_cams, const l3d_camera* cams, double near_plane);
+// midpoint c and diagonal of the bounding box of the n > 0 segments' end points (§23's)
+void refit_bounding_box(size_t n, const double* segs, double c[3], double& diag);
+// LoCam of a camera about the centre c
+LoCam refit_lo_camera(const l3d_camera& cam, const double c[3]);
+// The model's side of a call: the lines' segments in input order (a stable counting sort by line index)
+struct ModelLines {
+    uint32_t n_lines = 0;
+    std::vector<uint32_t> off, seg;              // [n_lines + 1], [n_model]: line l's segments are seg[off[l] .. off[l + 1])
+    void build(uint32_t n, const uint32_t* line) {
+        for (uint32_t i = 0; i < n; ++i) n_lines = std::max(n_lines, line[i] + 1);
+        off.assign((size_t)n_lines + 1, 0); seg.resize(n);
+        for (uint32_t i = 0; i < n; ++i) ++off[line[i] + 1];
+        for (uint32_t l = 0; l < n_lines; ++l) off[l + 1] += off[l];
+        std::vector<uint32_t> at(off.begin(), off.end() - 1);
+        for (uint32_t i = 0; i < n; ++i) seg[at[line[i]]++] = i;
+    }
+};
+
+// the checks of the entries of §28 and §29 behind their parameters (messages and order as §28 lists them)
+int refit_check_job(const RefitJob& J, double near_plane, double c[3], ModelLines& ml, uint64_t& n_seg);
 
 }  // namespace l3d

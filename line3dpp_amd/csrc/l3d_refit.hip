@@ -65,6 +65,14 @@ int check_params(const l3d_refit_params* p) {
     return L3D_OK;
 }
 
+using Job = RefitJob;
+
+l3d_association no_association() { return l3d_association{-1, 0xFFFFFFFFu, 0xFFFFFFFFu, 0.0f, 0.0f, 0u}; }
+
+}  // namespace
+
+namespace l3d {
+
 // the near plane, the cameras' sides and entries as stage 1 checks them, and the form of K that LoCam can hold
 int check_refit_cameras(uint32_t n_cams, const l3d_camera* cams, double near_plane) {
     if (int rc = check_projection_cameras(n_cams, cams, near_plane)) return rc;
@@ -78,7 +86,7 @@ int check_refit_cameras(uint32_t n_cams, const l3d_camera* cams, double near_pla
 }
 
 // midpoint c and diagonal of the bounding box of the n > 0 segments' end points (§23's)
-void bounding_box(size_t n, const double* segs, double c[3], double& diag) {
+void refit_bounding_box(size_t n, const double* segs, double c[3], double& diag) {
     double lo[3] = {segs[0], segs[1], segs[2]}, hi[3] = {segs[0], segs[1], segs[2]};
     for (size_t i = 0; i < 2 * n; ++i)
         for (int k = 0; k < 3; ++k) {
@@ -91,15 +99,8 @@ void bounding_box(size_t n, const double* segs, double c[3], double& diag) {
     diag = std::sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
 }
 
-struct Job {
-    uint32_t n_model; const double* segs; const uint32_t* line;
-    uint32_t n_cams; const l3d_camera* cams; const uint32_t* n_seg; const float* const* seg;
-};
-
-l3d_association no_association() { return l3d_association{-1, 0xFFFFFFFFu, 0xFFFFFFFFu, 0.0f, 0.0f, 0u}; }
-
 // LoCam of a camera about the centre c: R, C = Q - c with Q_i = -((R_0i t0 + R_1i t1) + R_2i t2), and K's four entries
-LoCam lo_camera(const l3d_camera& cam, const double c[3]) {
+LoCam refit_lo_camera(const l3d_camera& cam, const double c[3]) {
     LoCam lc;
     for (int k = 0; k < 9; ++k) lc.R[k] = cam.R[k];
     for (int i = 0; i < 3; ++i) lc.C[i] = -((cam.R[i] * cam.t[0] + cam.R[3 + i] * cam.t[1]) + cam.R[6 + i] * cam.t[2]) - c[i];
@@ -107,19 +108,182 @@ LoCam lo_camera(const l3d_camera& cam, const double c[3]) {
     return lc;
 }
 
-// The model's side of a call: the lines' segments in input order (a stable counting sort by line index)
-struct ModelLines {
-    uint32_t n_lines = 0;
-    std::vector<uint32_t> off, seg;              // [n_lines + 1], [n_model]: line l's segments are seg[off[l] .. off[l + 1])
-    void build(uint32_t n, const uint32_t* line) {
-        for (uint32_t i = 0; i < n; ++i) n_lines = std::max(n_lines, line[i] + 1);
-        off.assign((size_t)n_lines + 1, 0); seg.resize(n);
-        for (uint32_t i = 0; i < n; ++i) ++off[line[i] + 1];
-        for (uint32_t l = 0; l < n_lines; ++l) off[l + 1] += off[l];
-        std::vector<uint32_t> at(off.begin(), off.end() - 1);
-        for (uint32_t i = 0; i < n; ++i) seg[at[line[i]]++] = i;
+// What the entries of §28 and §29 check once the parameters, the model's arrays and the cameras' pointers are known to be
+// sound; c: the centre of the model's box (0 for an empty model), ml: its lines, n_seg: the 2D segments in all
+int refit_check_job(const RefitJob& J, double near_plane, double c[3], ModelLines& ml, uint64_t& n_seg) {
+    for (uint32_t i = 0; i < J.n_model; ++i)
+        if (J.line[i] >= 0x80000000u) return fail(L3D_ERR_LIMIT, "segment " + std::to_string(i) + " has a line index of 2^31 or more");
+    if (int rc = check_refit_cameras(J.n_cams, J.cams, near_plane)) return rc;
+    n_seg = 0;
+    for (uint32_t k = 0; k < J.n_cams; ++k) n_seg += J.n_seg[k];
+    if (n_seg >= ((uint64_t)1 << 32)) return fail(L3D_ERR_LIMIT, "2^32 or more segments in total");
+    for (uint32_t k = 0; k < J.n_cams; ++k) {
+        if (J.n_seg[k] && !J.seg[k]) return fail(L3D_ERR_ARG, "null argument");
+        for (size_t i = 0; i < 4 * (size_t)J.n_seg[k]; ++i)
+            if (!std::isfinite(J.seg[k][i]))
+                return fail(L3D_ERR_ARG, "camera " + std::to_string(k) + ": segment " + std::to_string(i / 4) + " has a non-finite entry");
     }
-};
+    c[0] = c[1] = c[2] = 0.0;
+    if (J.n_model) {
+        double diag;
+        refit_bounding_box(J.n_model, J.segs, c, diag);
+        if (!(diag > 0.0)) return fail(L3D_ERR_ARG, "the model's bounding box is a point");
+    }
+    ml.build(J.n_model, J.line);
+    return L3D_OK;
+}
+
+// Stages 1 to 3 of §28, which the joint bundle of §29 runs on the same function: the upload, projection and association
+// group by group, the observation list and its CSR per line.  See l3d_refit.h.
+int refit_observe(ProjWork& w, hipStream_t st, const RefitJob& J, double max_distance, double min_cos2, double min_overlap, double near_plane,
+                  uint32_t use_ambiguous, uint32_t n_lines, size_t tail_bytes, const char* who, float* ms_assoc, float* ms_list,
+                  RefitObserved& O) {
+    const std::string tag = std::string(who) + ": ";
+    const uint32_t n_model = J.n_model, n_cams = J.n_cams;
+    std::vector<uint32_t>& seg_begin = O.seg_begin;
+    seg_begin.assign((size_t)n_cams + 1, 0);
+    for (uint32_t k = 0; k < n_cams; ++k) seg_begin[k + 1] = seg_begin[k] + J.n_seg[k];
+    const uint32_t S = seg_begin[n_cams];
+    O.S = S;
+    // the groups: cameras with segments while their records fit the budget (one at least)
+    struct Group { uint32_t c0, c1, g; uint64_t n_tiles; };
+    std::vector<Group> groups;
+    for (uint32_t c0 = 0; c0 < n_cams;) {
+        Group G{c0, c0, 0, 0};
+        uint64_t bytes = 0;
+        while (G.c1 < n_cams && G.g < kRefitMaxGroup) {
+            const bool has = J.n_seg[G.c1] != 0;
+            const uint64_t tiles = ((uint64_t)J.n_seg[G.c1] + kAssocTile - 1) / kAssocTile;
+            const uint64_t b = has ? 68 * (uint64_t)n_model + 40 * (uint64_t)J.n_seg[G.c1] : 0;
+            if (G.g && has && (bytes + b > projection_budget(w) || (uint64_t)(G.g + 1) * n_model >= ((uint64_t)1 << 31) ||
+                               G.n_tiles + tiles >= ((uint64_t)1 << 31)))
+                break;
+            bytes += b; G.n_tiles += tiles; G.g += has ? 1 : 0;
+            ++G.c1;
+        }
+        groups.push_back(G);
+        c0 = G.c1;
+    }
+    uint32_t g_max = 0;
+    for (const Group& G : groups) g_max = std::max(g_max, G.g);
+    // what stays for the whole call; behind it a group's tables and records, and later, in their place, the caller's
+    Layout lay;
+    const size_t o_P = lay.take(48 * (size_t)n_model), o_line = lay.take(4 * (size_t)n_model), o_segs = lay.take(16 * (size_t)S);
+    const size_t o_begin = lay.take(4 * ((size_t)n_cams + 1)), up_end = lay.at;
+    const size_t o_assoc = lay.take(24 * (size_t)S), o_oseg = lay.take(4 * (size_t)S), o_oline = lay.take(4 * (size_t)S);
+    const size_t o_flag = lay.take(4 * ((size_t)S + 1)), keep_end = lay.at;
+    const size_t n_rec = (size_t)g_max * n_model;
+    const size_t o_pcam = lay.take(sizeof(ProjCam) * g_max), o_acam = lay.take(sizeof(AssocCam) * g_max), grp_up_end = lay.at;
+    const size_t o_bounds = lay.take(4 * ((size_t)g_max + 1)), o_vis = lay.take(4 * (n_rec + 1)), o_rec = lay.take(32 * n_rec),
+                 o_out = lay.take(32 * n_rec);
+    const size_t grp_end = lay.at;
+    const size_t sol_bound = up256(keep_end) + tail_bytes;
+    O.o_P = o_P; O.o_line = o_line; O.o_segs = o_segs; O.o_begin = o_begin; O.o_oseg = o_oseg; O.keep_end = keep_end; O.bound = sol_bound;
+    if (w.h.reserve(std::max(std::max(grp_up_end, keep_end), sol_bound)) != hipSuccess || w.d.reserve(std::max(grp_end, sol_bound)) != hipSuccess ||
+        w.scan_ws.reserve_zeroed(std::max(scan_ws_words(n_rec, 4), scan_ws_words(S, 4)), st) != hipSuccess)
+        return fail(L3D_ERR_HIP, tag + "allocation failed");
+    char* h = w.h.p; char* d = w.d.p;
+    KernelTimer t_assoc(ms_assoc), t_list(ms_list);
+    if (!t_assoc.ok() || !t_list.ok()) return fail(L3D_ERR_HIP, tag + "no event");
+    auto hip_fail = [&tag](hipError_t e) { return fail(L3D_ERR_HIP, tag + hipGetErrorString(e)); };
+
+    // the model as given, its line indices, every camera's segments and where they begin: one upload
+    std::memcpy(h + o_P, J.segs, 48 * (size_t)n_model);
+    std::memcpy(h + o_line, J.line, 4 * (size_t)n_model);
+    for (uint32_t k = 0; k < n_cams; ++k)
+        if (J.n_seg[k]) std::memcpy(h + o_segs + 16 * (size_t)seg_begin[k], J.seg[k], 16 * (size_t)J.n_seg[k]);
+    std::memcpy(h + o_begin, seg_begin.data(), 4 * ((size_t)n_cams + 1));
+    hipError_t e = hipMemcpyAsync(d, h, up_end, hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return hip_fail(e);
+
+    // stage 2: projection and association, group by group, in the frame of the model as given
+    for (const Group& G : groups) {
+        if (!G.g) continue;
+        ProjCam* pcam = (ProjCam*)(h + o_pcam); AssocCam* acam = (AssocCam*)(h + o_acam);
+        uint32_t i = 0, n_tiles = 0;
+        for (uint32_t k = G.c0; k < G.c1; ++k) {
+            if (!J.n_seg[k]) continue;
+            const l3d_camera& in = J.cams[k];
+            ProjCam pc;
+            std::memcpy(pc.K, in.K, 72); std::memcpy(pc.R, in.R, 72); std::memcpy(pc.t, in.t, 24);
+            pc.xmax = (double)(in.width - 1); pc.ymax = (double)(in.height - 1);
+            pcam[i] = pc;
+            acam[i] = AssocCam{n_tiles, seg_begin[k], J.n_seg[k], 0u, 0u};
+            n_tiles += (J.n_seg[k] + kAssocTile - 1) / kAssocTile;
+            ++i;
+        }
+        ProjArgs pa{(const ProjCam*)(d + o_pcam), G.g, n_model, (const double*)(d + o_P), (const uint32_t*)(d + o_line), near_plane,
+                    (ProjRecord*)(d + o_rec), (uint32_t*)(d + o_vis), (ProjRecord*)(d + o_out), (uint32_t*)(d + o_bounds)};
+        AssocArgs aa{(const AssocCam*)(d + o_acam), G.g, (const float4*)(d + o_segs), (const ProjRecord*)(d + o_out), (AssocOut*)(d + o_assoc),
+                     max_distance * max_distance, min_cos2, min_overlap};
+        e = hipMemcpyAsync(d + o_pcam, h + o_pcam, grp_up_end - o_pcam, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = t_assoc.start(st);
+        if (e == hipSuccess) e = launch_project_stage1(w, pa, st);
+        if (e == hipSuccess) e = launch_pose_bounds((AssocCam*)(d + o_acam), G.g, pa.bounds, st);
+        if (e == hipSuccess) e = launch_associate(aa, n_tiles, st);
+        if (e == hipSuccess) e = t_assoc.stop(st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);       // (the next group reuses the tables)
+        if (e != hipSuccess) return hip_fail(e);
+        t_assoc.add();
+    }
+    // stage 3: the observation list
+    const RefitCompactArgs ca{(const AssocOut*)(d + o_assoc), S, use_ambiguous, (uint32_t*)(d + o_flag), (uint32_t*)(d + o_oseg),
+                              (uint32_t*)(d + o_oline)};
+    uint32_t n_obs = 0;
+    e = t_list.start(st);
+    if (e == hipSuccess) e = launch_refit_flag(ca, st);
+    if (e == hipSuccess) e = launch_scan(ca.flag, S, ca.flag, w.scan_ws.p, nullptr, st);
+    if (e == hipSuccess) e = launch_refit_compact(ca, st);
+    if (e == hipSuccess) e = t_list.stop(st);
+    if (e == hipSuccess) e = hipMemcpyAsync(h + o_flag, d + o_flag + 4 * (size_t)S, 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(h + o_assoc, d + o_assoc, 24 * (size_t)S, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return hip_fail(e);
+    t_list.add();
+    std::memcpy(&n_obs, h + o_flag, 4);
+    if (n_obs > S) return fail(L3D_ERR_HIP, tag + "the observation count is out of range");
+    if (n_obs) {
+        e = hipMemcpyAsync(h + o_oline, d + o_oline, 4 * (size_t)n_obs, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) return hip_fail(e);
+    }
+    O.n_obs = n_obs;
+    O.assoc.resize(S);
+    // the associations as they are handed out; from them the flat 2D segment of every observation, which the device keeps
+    // to itself: the list is in flat order, so its j-th entry is the j-th segment that the rule of stage 3 accepts
+    std::vector<uint32_t>& oseg = O.oseg;
+    oseg.clear(); oseg.reserve(n_obs);
+    O.n_ambiguous_left_out = 0;
+    {
+        const AssocOut* res = (const AssocOut*)(h + o_assoc);
+        for (uint32_t i = 0; i < S; ++i) {
+            const AssocOut& r = res[i];
+            O.assoc[i] = l3d_association{r.record, r.line, r.segment, std::sqrt(r.d2), r.overlap, r.n_accepted};
+            if (r.record >= 0 && r.n_accepted > 1 && !use_ambiguous) ++O.n_ambiguous_left_out;
+            if (r.record >= 0 && (r.n_accepted == 1 || use_ambiguous)) oseg.push_back(i);
+        }
+    }
+    // the CSR per line (stable counting sort: a line's observations in ascending flat 2D segment)
+    O.oline.assign((const uint32_t*)(h + o_oline), (const uint32_t*)(h + o_oline) + n_obs);
+    const std::vector<uint32_t>& oline = O.oline;
+    if (oseg.size() != n_obs) return fail(L3D_ERR_HIP, tag + "the observation list does not match the associations");
+    for (uint32_t j = 0; j < n_obs; ++j)
+        if (oline[j] >= n_lines || oline[j] != O.assoc[oseg[j]].line) return fail(L3D_ERR_HIP, tag + "an observation is out of range");
+    std::vector<uint32_t>& obs_off = O.obs_off;
+    obs_off.assign((size_t)n_lines + 1, 0);
+    for (uint32_t j = 0; j < n_obs; ++j) ++obs_off[oline[j] + 1];
+    for (uint32_t l = 0; l < n_lines; ++l) obs_off[l + 1] += obs_off[l];
+    O.csr.resize(n_obs);                         // the observation (its rank in the compaction) at a CSR position
+    {
+        std::vector<uint32_t> at(obs_off.begin(), obs_off.end() - 1);
+        for (uint32_t j = 0; j < n_obs; ++j) O.csr[at[oline[j]]++] = j;
+    }
+    return L3D_OK;
+}
+
+}  // namespace l3d
+
+namespace {
 
 // Stage 10: the output model and the summary from the lines' statuses and the REFIT lines' pieces (piece_off [n_lines + 1]
 // into pieces, 6 doubles each)
@@ -167,146 +331,34 @@ bool finite4(const double* x) { return std::isfinite(x[0]) && std::isfinite(x[1]
 // L3D_OK.  kernel_ms (may be null): [5] the time of the launches, by part.
 int refit_core(ProjWork& w, hipStream_t st, const Job& J, const l3d_refit_params& p, const double c[3], const ModelLines& ml, RefitResult& R,
                float* kernel_ms) {
-    const uint32_t n_model = J.n_model, n_cams = J.n_cams, n_lines = ml.n_lines;
-    std::vector<uint32_t> seg_begin((size_t)n_cams + 1, 0);
-    for (uint32_t k = 0; k < n_cams; ++k) seg_begin[k + 1] = seg_begin[k] + J.n_seg[k];
-    const uint32_t S = seg_begin[n_cams];
-    // the groups: cameras with segments while their records fit the budget (one at least)
-    struct Group { uint32_t c0, c1, g; uint64_t n_tiles; };
-    std::vector<Group> groups;
-    for (uint32_t c0 = 0; c0 < n_cams;) {
-        Group G{c0, c0, 0, 0};
-        uint64_t bytes = 0;
-        while (G.c1 < n_cams && G.g < kRefitMaxGroup) {
-            const bool has = J.n_seg[G.c1] != 0;
-            const uint64_t tiles = ((uint64_t)J.n_seg[G.c1] + kAssocTile - 1) / kAssocTile;
-            const uint64_t b = has ? 68 * (uint64_t)n_model + 40 * (uint64_t)J.n_seg[G.c1] : 0;
-            if (G.g && has && (bytes + b > projection_budget(w) || (uint64_t)(G.g + 1) * n_model >= ((uint64_t)1 << 31) ||
-                               G.n_tiles + tiles >= ((uint64_t)1 << 31)))
-                break;
-            bytes += b; G.n_tiles += tiles; G.g += has ? 1 : 0;
-            ++G.c1;
-        }
-        groups.push_back(G);
-        c0 = G.c1;
-    }
-    uint32_t g_max = 0;
-    for (const Group& G : groups) g_max = std::max(g_max, G.g);
-    // what stays for the whole call; behind it a group's tables and records, and later, in their place, the solve's
-    Layout lay;
-    const size_t o_P = lay.take(48 * (size_t)n_model), o_line = lay.take(4 * (size_t)n_model), o_segs = lay.take(16 * (size_t)S);
-    const size_t o_begin = lay.take(4 * ((size_t)n_cams + 1)), up_end = lay.at;
-    const size_t o_assoc = lay.take(24 * (size_t)S), o_oseg = lay.take(4 * (size_t)S), o_oline = lay.take(4 * (size_t)S);
-    const size_t o_flag = lay.take(4 * ((size_t)S + 1)), keep_end = lay.at;
-    const size_t n_rec = (size_t)g_max * n_model;
-    const size_t o_pcam = lay.take(sizeof(ProjCam) * g_max), o_acam = lay.take(sizeof(AssocCam) * g_max), grp_up_end = lay.at;
-    const size_t o_bounds = lay.take(4 * ((size_t)g_max + 1)), o_vis = lay.take(4 * (n_rec + 1)), o_rec = lay.take(32 * n_rec),
-                 o_out = lay.take(32 * n_rec);
-    const size_t grp_end = lay.at;
+    const uint32_t n_cams = J.n_cams, n_lines = ml.n_lines;
+    uint64_t S64 = 0;
+    for (uint32_t k = 0; k < n_cams; ++k) S64 += J.n_seg[k];
     // the solve's tables at their largest: every line that has a segment solved, every 2D segment an observation
-    const size_t nl_max = std::min<size_t>(n_lines, n_model);
-    const size_t sol_bound = up256(keep_end) + sizeof(LoCam) * n_cams + (32 + 4 + 4 + 48 + sizeof(LoOut)) * nl_max +
-                             (4 + sizeof(RefitSpan) + sizeof(LoObs)) * (size_t)S + 4 + 9 * 256;
-    if (w.h.reserve(std::max(std::max(grp_up_end, keep_end), sol_bound)) != hipSuccess || w.d.reserve(std::max(grp_end, sol_bound)) != hipSuccess ||
-        w.scan_ws.reserve_zeroed(std::max(scan_ws_words(n_rec, 4), scan_ws_words(S, 4)), st) != hipSuccess)
-        return fail(L3D_ERR_HIP, "refit: allocation failed");
-    char* h = w.h.p; char* d = w.d.p;
+    const size_t nl_max = std::min<size_t>(n_lines, J.n_model);
+    const size_t tail = sizeof(LoCam) * n_cams + (32 + 4 + 4 + 48 + sizeof(LoOut)) * nl_max +
+                        (4 + sizeof(RefitSpan) + sizeof(LoObs)) * (size_t)S64 + 4 + 9 * 256;
     float* const ms = kernel_ms;
-    KernelTimer t_assoc(ms ? ms + 0 : nullptr), t_list(ms ? ms + 1 : nullptr), t_obs(ms ? ms + 2 : nullptr), t_solve(ms ? ms + 3 : nullptr),
-        t_spans(ms ? ms + 4 : nullptr);
-    if (!t_assoc.ok() || !t_list.ok() || !t_obs.ok() || !t_solve.ok() || !t_spans.ok()) return fail(L3D_ERR_HIP, "refit: no event");
+    RefitObserved O;
+    if (int rc = refit_observe(w, st, J, p.max_distance, p.min_cos2, p.min_overlap, p.near_plane, p.use_ambiguous, n_lines, tail, "refit",
+                               ms ? ms + 0 : nullptr, ms ? ms + 1 : nullptr, O))
+        return rc;
+    KernelTimer t_obs(ms ? ms + 2 : nullptr), t_solve(ms ? ms + 3 : nullptr), t_spans(ms ? ms + 4 : nullptr);
+    if (!t_obs.ok() || !t_solve.ok() || !t_spans.ok()) return fail(L3D_ERR_HIP, "refit: no event");
     auto hip_fail = [](hipError_t e) { return fail(L3D_ERR_HIP, std::string("refit: ") + hipGetErrorString(e)); };
-
-    // the model as given, its line indices, every camera's segments and where they begin: one upload
-    std::memcpy(h + o_P, J.segs, 48 * (size_t)n_model);
-    std::memcpy(h + o_line, J.line, 4 * (size_t)n_model);
-    for (uint32_t k = 0; k < n_cams; ++k)
-        if (J.n_seg[k]) std::memcpy(h + o_segs + 16 * (size_t)seg_begin[k], J.seg[k], 16 * (size_t)J.n_seg[k]);
-    std::memcpy(h + o_begin, seg_begin.data(), 4 * ((size_t)n_cams + 1));
-    hipError_t e = hipMemcpyAsync(d, h, up_end, hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) return hip_fail(e);
-
-    // stage 2: projection and association, group by group, in the frame of the model as given
-    for (const Group& G : groups) {
-        if (!G.g) continue;
-        ProjCam* pcam = (ProjCam*)(h + o_pcam); AssocCam* acam = (AssocCam*)(h + o_acam);
-        uint32_t i = 0, n_tiles = 0;
-        for (uint32_t k = G.c0; k < G.c1; ++k) {
-            if (!J.n_seg[k]) continue;
-            const l3d_camera& in = J.cams[k];
-            ProjCam pc;
-            std::memcpy(pc.K, in.K, 72); std::memcpy(pc.R, in.R, 72); std::memcpy(pc.t, in.t, 24);
-            pc.xmax = (double)(in.width - 1); pc.ymax = (double)(in.height - 1);
-            pcam[i] = pc;
-            acam[i] = AssocCam{n_tiles, seg_begin[k], J.n_seg[k], 0u, 0u};
-            n_tiles += (J.n_seg[k] + kAssocTile - 1) / kAssocTile;
-            ++i;
-        }
-        ProjArgs pa{(const ProjCam*)(d + o_pcam), G.g, n_model, (const double*)(d + o_P), (const uint32_t*)(d + o_line), p.near_plane,
-                    (ProjRecord*)(d + o_rec), (uint32_t*)(d + o_vis), (ProjRecord*)(d + o_out), (uint32_t*)(d + o_bounds)};
-        AssocArgs aa{(const AssocCam*)(d + o_acam), G.g, (const float4*)(d + o_segs), (const ProjRecord*)(d + o_out), (AssocOut*)(d + o_assoc),
-                     p.max_distance * p.max_distance, p.min_cos2, p.min_overlap};
-        e = hipMemcpyAsync(d + o_pcam, h + o_pcam, grp_up_end - o_pcam, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = t_assoc.start(st);
-        if (e == hipSuccess) e = launch_project_stage1(w, pa, st);
-        if (e == hipSuccess) e = launch_pose_bounds((AssocCam*)(d + o_acam), G.g, pa.bounds, st);
-        if (e == hipSuccess) e = launch_associate(aa, n_tiles, st);
-        if (e == hipSuccess) e = t_assoc.stop(st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);       // (the next group reuses the tables)
-        if (e != hipSuccess) return hip_fail(e);
-        t_assoc.add();
-    }
-    // stage 3: the observation list
-    const RefitCompactArgs ca{(const AssocOut*)(d + o_assoc), S, p.use_ambiguous, (uint32_t*)(d + o_flag), (uint32_t*)(d + o_oseg),
-                              (uint32_t*)(d + o_oline)};
-    uint32_t n_obs = 0;
-    e = t_list.start(st);
-    if (e == hipSuccess) e = launch_refit_flag(ca, st);
-    if (e == hipSuccess) e = launch_scan(ca.flag, S, ca.flag, w.scan_ws.p, nullptr, st);
-    if (e == hipSuccess) e = launch_refit_compact(ca, st);
-    if (e == hipSuccess) e = t_list.stop(st);
-    if (e == hipSuccess) e = hipMemcpyAsync(h + o_flag, d + o_flag + 4 * (size_t)S, 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(h + o_assoc, d + o_assoc, 24 * (size_t)S, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return hip_fail(e);
-    t_list.add();
-    std::memcpy(&n_obs, h + o_flag, 4);
-    if (n_obs > S) return fail(L3D_ERR_HIP, "refit: the observation count is out of range");
-    if (n_obs) {
-        e = hipMemcpyAsync(h + o_oline, d + o_oline, 4 * (size_t)n_obs, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) return hip_fail(e);
-    }
+    char* h = w.h.p; char* d = w.d.p;
+    hipError_t e = hipSuccess;
+    const std::vector<uint32_t>& seg_begin = O.seg_begin;
+    const std::vector<uint32_t>&oseg = O.oseg, &csr = O.csr;
+    const size_t o_segs = O.o_segs, o_begin = O.o_begin, o_oseg = O.o_oseg, keep_end = O.keep_end, sol_bound = O.bound;
+    const uint32_t n_obs = O.n_obs;
     g_refit_observations.store(n_obs, std::memory_order_relaxed);
-    R.assoc.resize(S);
-    // the associations as they are handed out; from them the flat 2D segment of every observation, which the device keeps
-    // to itself: the list is in flat order, so its j-th entry is the j-th segment that the rule of stage 3 accepts
-    std::vector<uint32_t> oseg;
-    oseg.reserve(n_obs);
-    {
-        const AssocOut* res = (const AssocOut*)(h + o_assoc);
-        for (uint32_t i = 0; i < S; ++i) {
-            const AssocOut& r = res[i];
-            R.assoc[i] = l3d_association{r.record, r.line, r.segment, std::sqrt(r.d2), r.overlap, r.n_accepted};
-            if (r.record >= 0 && r.n_accepted > 1 && !p.use_ambiguous) ++R.sum.n_ambiguous_left_out;
-            if (r.record >= 0 && (r.n_accepted == 1 || p.use_ambiguous)) oseg.push_back(i);
-        }
-    }
+    R.assoc = std::move(O.assoc);
+    R.sum.n_ambiguous_left_out = O.n_ambiguous_left_out;
     R.sum.n_observations = n_obs;
-    // the CSR per line (stable counting sort: a line's observations in ascending flat 2D segment), views and eligibility
-    const std::vector<uint32_t> oline((const uint32_t*)(h + o_oline), (const uint32_t*)(h + o_oline) + n_obs);
-    if (oseg.size() != n_obs) return fail(L3D_ERR_HIP, "refit: the observation list does not match the associations");
-    for (uint32_t j = 0; j < n_obs; ++j)
-        if (oline[j] >= n_lines || oline[j] != R.assoc[oseg[j]].line) return fail(L3D_ERR_HIP, "refit: an observation is out of range");
     lines_as_given(J, ml, R);
+    R.obs_off = O.obs_off;
     std::vector<uint32_t>& obs_off = R.obs_off;
-    for (uint32_t j = 0; j < n_obs; ++j) ++obs_off[oline[j] + 1];
-    for (uint32_t l = 0; l < n_lines; ++l) obs_off[l + 1] += obs_off[l];
-    std::vector<uint32_t> csr(n_obs);            // the observation (its rank in the compaction) at a CSR position
-    {
-        std::vector<uint32_t> at(obs_off.begin(), obs_off.end() - 1);
-        for (uint32_t j = 0; j < n_obs; ++j) csr[at[oline[j]]++] = j;
-    }
     R.obs.resize(n_obs);
     const uint32_t need = std::max<uint32_t>(2u, p.visibility);
     std::vector<uint32_t> sol;                   // the lines handed to the solver, ascending
@@ -354,7 +406,7 @@ int refit_core(ProjWork& w, hipStream_t st, const Job& J, const l3d_refit_params
         const size_t o_obs = sl.take(sizeof(LoObs) * no), sol_end = sl.at;
         if (sol_end > sol_bound || sol_host_end > sol_bound) return fail(L3D_ERR_HIP, "refit: the solve's tables exceed their bound");
         LoCam* lc = (LoCam*)(h + o_cam);
-        for (uint32_t k = 0; k < n_cams; ++k) lc[k] = lo_camera(J.cams[k], c);
+        for (uint32_t k = 0; k < n_cams; ++k) lc[k] = refit_lo_camera(J.cams[k], c);
         std::memcpy(h + o_x0, x0.data(), 32 * (size_t)ns);
         std::memcpy(h + o_off, res_off.data(), 4 * ((size_t)ns + 1));
         std::memcpy(h + o_ord, order.data(), 4 * (size_t)ns);
@@ -449,25 +501,8 @@ int refit_core(ProjWork& w, hipStream_t st, const Job& J, const l3d_refit_params
 // sound.  done: the call is answered (an error, or every line as given)
 int prepare(const Job& J, const l3d_refit_params& p, double c[3], ModelLines& ml, RefitResult& R, bool& done) {
     done = true;
-    for (uint32_t i = 0; i < J.n_model; ++i)
-        if (J.line[i] >= 0x80000000u) return fail(L3D_ERR_LIMIT, "segment " + std::to_string(i) + " has a line index of 2^31 or more");
-    if (int rc = check_refit_cameras(J.n_cams, J.cams, p.near_plane)) return rc;
     uint64_t n_seg = 0;
-    for (uint32_t k = 0; k < J.n_cams; ++k) n_seg += J.n_seg[k];
-    if (n_seg >= ((uint64_t)1 << 32)) return fail(L3D_ERR_LIMIT, "2^32 or more segments in total");
-    for (uint32_t k = 0; k < J.n_cams; ++k) {
-        if (J.n_seg[k] && !J.seg[k]) return fail(L3D_ERR_ARG, "null argument");
-        for (size_t i = 0; i < 4 * (size_t)J.n_seg[k]; ++i)
-            if (!std::isfinite(J.seg[k][i]))
-                return fail(L3D_ERR_ARG, "camera " + std::to_string(k) + ": segment " + std::to_string(i / 4) + " has a non-finite entry");
-    }
-    c[0] = c[1] = c[2] = 0.0;
-    if (J.n_model) {
-        double diag;
-        bounding_box(J.n_model, J.segs, c, diag);
-        if (!(diag > 0.0)) return fail(L3D_ERR_ARG, "the model's bounding box is a point");
-    }
-    ml.build(J.n_model, J.line);
+    if (int rc = refit_check_job(J, p.near_plane, c, ml, n_seg)) return rc;
     if (J.n_model && J.n_cams && n_seg) { done = false; return L3D_OK; }
     // an empty model, no camera or no 2D segment: every line as given
     lines_as_given(J, ml, R);
