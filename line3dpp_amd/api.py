@@ -1490,6 +1490,21 @@ class _PoseOutputs:
                     associations=split_records(self.assoc, self.n_seg), trace=trace)
 
 
+def _model_and_cameras(segs, line, cams, segs_per_cam):
+    """the arguments that refine_cameras, refit_segments and bundle_segments share, as the library takes them -> the model
+    [n, 6] float64 and its line indices, the float32 [M, 4] arrays per camera, their counts and their concatenation (each
+    with one entry to spare, so that neither is empty) and the camera array"""
+    s = np.ascontiguousarray(segs, np.float64).reshape(-1, 6); ln = np.ascontiguousarray(line, np.uint32).reshape(-1)
+    if len(ln) != len(s):
+        raise ValueError("one line index per segment")
+    if len(cams) != len(segs_per_cam):
+        raise ValueError("one array of segments per camera")
+    seg = [np.ascontiguousarray(v, np.float32).reshape(-1, 4) for v in segs_per_cam]
+    n_seg = np.array([len(v) for v in seg] + [0], np.uint32)
+    seg4 = np.concatenate(seg + [np.zeros((1, 4), np.float32)])
+    return s, ln, seg, n_seg, seg4, camera_array(list(cams))
+
+
 def refine_cameras(segs, line, cams, segs_per_cam, max_distance=L3D_DEF_SCORING_POS_REGULARIZER, start_distance=0.0,
                    max_angle=L3D_DEF_SCORING_ANG_REGULARIZER, min_overlap=0.5, stall_tolerance=1e-4, step_tolerance=1e-9,
                    max_iterations=50, min_matches=8, near=1e-6, device=0):
@@ -1500,17 +1515,9 @@ def refine_cameras(segs, line, cams, segs_per_cam, max_distance=L3D_DEF_SCORING_
     n_matched, rms in pixels, last_step, the delta q and t), associations (one ASSOCIATION_DTYPE array per camera, of the
     refined camera at max_distance) and trace (one POSE_ITERATION_DTYPE array per camera)"""
     L = _lib.load()
-    s = np.ascontiguousarray(segs, np.float64).reshape(-1, 6); ln = np.ascontiguousarray(line, np.uint32).reshape(-1)
-    if len(ln) != len(s):
-        raise ValueError("one line index per segment")
-    if len(cams) != len(segs_per_cam):
-        raise ValueError("one array of segments per camera")
-    seg = [np.ascontiguousarray(v, np.float32).reshape(-1, 4) for v in segs_per_cam]
-    n_seg = np.array([len(v) for v in seg] + [0], np.uint32)
-    seg4 = np.concatenate(seg + [np.zeros((1, 4), np.float32)])
+    s, ln, seg, n_seg, seg4, arr = _model_and_cameras(segs, line, cams, segs_per_cam)
     par = pose_params(max_distance, start_distance, max_angle, min_overlap, stall_tolerance, step_tolerance, max_iterations,
                       min_matches, near)
-    arr = camera_array(list(cams))
     out = _PoseOutputs(len(cams), n_seg[:len(cams)], par.max_iterations)
     rc = L.l3d_refine_cameras(int(device), len(s), ptr(s), ptr(ln), len(cams), arr, ptr(n_seg), ptr(seg4), C.byref(par), out.cams,
                               ptr(out.summaries), ptr(out.assoc), ptr(out.trace))
@@ -1535,6 +1542,28 @@ def refit_summary_dict(s):
                 cost1=float(s.cost1))
 
 
+def _handle_counts(counts, h, n):
+    """the first n counts of a result handle (l3d_refit_counts, l3d_bundle_counts)"""
+    v = [C.c_uint64() for _ in range(n)]
+    counts(h, *[C.byref(x) for x in v])
+    return [int(x.value) for x in v]
+
+
+def _line_arrays(ns, nl, no, na, line_dtype):
+    """the arrays that l3d_refit_get and l3d_bundle_get fill first, none of them empty: segments, line, lines, observations,
+    associations"""
+    return (np.zeros((max(ns, 1), 6), np.float64), np.zeros(max(ns, 1), np.uint32), np.zeros(max(nl, 1), line_dtype),
+            np.zeros(max(no, 1), REFIT_OBSERVATION_DTYPE), np.zeros(max(na, 1), ASSOCIATION_DTYPE))
+
+
+def _lines_dict(arrays, ns, nl, no, na, n_seg_per_cam):
+    """... cut to their counts, as the dict that take_refit and take_bundle share"""
+    segs, line, lines, obs, assoc = arrays
+    assoc = assoc[:na]
+    return dict(segments=segs[:ns], line=line[:ns], lines=lines[:nl], observations=obs[:no],
+                associations=split_records(assoc, n_seg_per_cam) if n_seg_per_cam is not None else assoc)
+
+
 def take_refit(h, n_seg_per_cam):
     """the contents of an l3d_refit handle as a dict, and the handle closed: segments [n, 6] and line [n] (the output
     model), lines (REFIT_LINE_DTYPE, one per line index; `status` an index into REFIT_STATUS), observations
@@ -1542,20 +1571,13 @@ def take_refit(h, n_seg_per_cam):
     known) and the summary"""
     L = _lib.load()
     try:
-        n = [C.c_uint64() for _ in range(4)]
-        L.l3d_refit_counts(h, *[C.byref(v) for v in n])
-        ns, nl, no, na = (int(v.value) for v in n)
-        segs = np.zeros((max(ns, 1), 6), np.float64); line = np.zeros(max(ns, 1), np.uint32)
-        lines = np.zeros(max(nl, 1), REFIT_LINE_DTYPE); obs = np.zeros(max(no, 1), REFIT_OBSERVATION_DTYPE)
-        assoc = np.zeros(max(na, 1), ASSOCIATION_DTYPE)
+        n = _handle_counts(L.l3d_refit_counts, h, 4)
+        arrays = _line_arrays(*n, REFIT_LINE_DTYPE)
         s = _lib.RefitSummary()
-        L.l3d_refit_get(h, ptr(segs), ptr(line), ptr(lines), ptr(obs), ptr(assoc), C.byref(s))
+        L.l3d_refit_get(h, *[ptr(a) for a in arrays], C.byref(s))
     finally:
         L.l3d_refit_close(h)
-    assoc = assoc[:na]
-    return dict(segments=segs[:ns], line=line[:ns], lines=lines[:nl], observations=obs[:no],
-                associations=split_records(assoc, n_seg_per_cam) if n_seg_per_cam is not None else assoc,
-                summary=refit_summary_dict(s))
+    return dict(_lines_dict(arrays, *n, n_seg_per_cam), summary=refit_summary_dict(s))
 
 
 def refit_segments(segs, line, cams, segs_per_cam, max_distance=L3D_DEF_SCORING_POS_REGULARIZER,
@@ -1565,16 +1587,8 @@ def refit_segments(segs, line, cams, segs_per_cam, max_distance=L3D_DEF_SCORING_
     from the 2D segments that observe it in `cams` (dicts K, R, t, width, height; segs_per_cam: one float32 [M, 4] array
     per camera) and cut anew -> the dict of take_refit.  A line that is not REFIT keeps its segments bit for bit."""
     L = _lib.load()
-    s = np.ascontiguousarray(segs, np.float64).reshape(-1, 6); ln = np.ascontiguousarray(line, np.uint32).reshape(-1)
-    if len(ln) != len(s):
-        raise ValueError("one line index per segment")
-    if len(cams) != len(segs_per_cam):
-        raise ValueError("one array of segments per camera")
-    seg = [np.ascontiguousarray(v, np.float32).reshape(-1, 4) for v in segs_per_cam]
-    n_seg = np.array([len(v) for v in seg] + [0], np.uint32)
-    seg4 = np.concatenate(seg + [np.zeros((1, 4), np.float32)])
+    s, ln, seg, n_seg, seg4, arr = _model_and_cameras(segs, line, cams, segs_per_cam)
     par = refit_params(max_distance, max_angle, min_overlap, near, min_length, visibility, max_iterations, use_ambiguous)
-    arr = camera_array(list(cams))
     h = C.c_void_p()
     rc = L.l3d_refit_segments(int(device), len(s), ptr(s), ptr(ln), len(cams), arr, ptr(n_seg), ptr(seg4), C.byref(par), C.byref(h))
     if rc != 0:
@@ -1632,22 +1646,15 @@ def take_bundle(h, n_seg_per_cam):
     (None where none was kept) and the summary"""
     L = _lib.load()
     try:
-        n = [C.c_uint64() for _ in range(7)]
-        L.l3d_bundle_counts(h, *[C.byref(v) for v in n])
-        ns, nl, no, na, nc, ni, nsys = (int(v.value) for v in n)
-        segs = np.zeros((max(ns, 1), 6), np.float64); line = np.zeros(max(ns, 1), np.uint32)
-        lines = np.zeros(max(nl, 1), BUNDLE_LINE_DTYPE); obs = np.zeros(max(no, 1), REFIT_OBSERVATION_DTYPE)
-        assoc = np.zeros(max(na, 1), ASSOCIATION_DTYPE); cams = (_lib.Camera * max(nc, 1))()
-        trace = np.zeros(max(ni, 1), BUNDLE_ITERATION_DTYPE)
+        *n, nc, ni, nsys = _handle_counts(L.l3d_bundle_counts, h, 7)
+        arrays = _line_arrays(*n, BUNDLE_LINE_DTYPE)
+        cams = (_lib.Camera * max(nc, 1))(); trace = np.zeros(max(ni, 1), BUNDLE_ITERATION_DTYPE)
         system = np.zeros((max(nsys, 1), max(nsys, 1)), np.float64); rhs = np.zeros(max(nsys, 1), np.float64)
         s = _lib.BundleSummary()
-        L.l3d_bundle_get(h, ptr(segs), ptr(line), ptr(lines), ptr(obs), ptr(assoc), cams, ptr(trace), ptr(system), ptr(rhs), C.byref(s))
+        L.l3d_bundle_get(h, *[ptr(a) for a in arrays], cams, ptr(trace), ptr(system), ptr(rhs), C.byref(s))
     finally:
         L.l3d_bundle_close(h)
-    assoc = assoc[:na]
-    return dict(segments=segs[:ns], line=line[:ns], lines=lines[:nl], observations=obs[:no],
-                associations=split_records(assoc, n_seg_per_cam) if n_seg_per_cam is not None else assoc,
-                cameras=[camera_dict(cams[k]) for k in range(nc)], trace=trace[:ni],
+    return dict(_lines_dict(arrays, *n, n_seg_per_cam), cameras=[camera_dict(cams[k]) for k in range(nc)], trace=trace[:ni],
                 system=system[:nsys, :nsys] if s.captured else None, rhs=rhs[:nsys] if s.captured else None,
                 summary=bundle_summary_dict(s))
 
@@ -1670,18 +1677,10 @@ def bundle_segments(segs, line, cams, segs_per_cam, fixed=None, max_distance=L3D
     Levenberg-Marquardt jointly over the poses of the cameras that are not `fixed` (one 0 / 1 per camera; None: none) and
     the lines that enough cameras see, and the lines' segments cut anew -> the dict of take_bundle"""
     L = _lib.load()
-    s = np.ascontiguousarray(segs, np.float64).reshape(-1, 6); ln = np.ascontiguousarray(line, np.uint32).reshape(-1)
-    if len(ln) != len(s):
-        raise ValueError("one line index per segment")
-    if len(cams) != len(segs_per_cam):
-        raise ValueError("one array of segments per camera")
-    seg = [np.ascontiguousarray(v, np.float32).reshape(-1, 4) for v in segs_per_cam]
-    n_seg = np.array([len(v) for v in seg] + [0], np.uint32)
-    seg4 = np.concatenate(seg + [np.zeros((1, 4), np.float32)])
+    s, ln, seg, n_seg, seg4, arr = _model_and_cameras(segs, line, cams, segs_per_cam)
     par = bundle_params(max_distance, max_angle, min_overlap, near, min_length, visibility, max_iterations, use_ambiguous,
                         initial_damping, min_damping, max_damping, function_tolerance, capture_iteration)
     fx = _fixed_bytes(fixed, len(cams))
-    arr = camera_array(list(cams))
     h = C.c_void_p()
     rc = L.l3d_bundle_segments(int(device), len(s), ptr(s), ptr(ln), len(cams), arr, ptr(fx) if fx is not None else None, ptr(n_seg),
                                ptr(seg4), C.byref(par), C.byref(h))

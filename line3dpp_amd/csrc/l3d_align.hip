@@ -39,11 +39,6 @@ int check_params(const l3d_align_params* p) {
     return L3D_OK;
 }
 
-void normalise(double q[4]) {
-    const double n = std::sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
-    for (int i = 0; i < 4; ++i) q[i] = q[i] / n;
-}
-
 int check_similarity(const l3d_similarity* s) {
     if (!(s->scale > 0.0) || !std::isfinite(s->scale)) return fail(L3D_ERR_ARG, "similarity: scale must be finite and greater than 0");
     const double qq = ((s->q[0] * s->q[0] + s->q[1] * s->q[1]) + s->q[2] * s->q[2]) + s->q[3] * s->q[3];
@@ -58,7 +53,7 @@ int entry_similarity(const l3d_similarity* s, l3d_similarity& T) {
     if (!s) { T = l3d_similarity{1.0, {1.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}}; return L3D_OK; }
     if (int rc = check_similarity(s)) return rc;
     T = *s;
-    normalise(T.q);
+    quat_normalise(T.q);
     return L3D_OK;
 }
 
@@ -66,7 +61,7 @@ int entry_similarity(const l3d_similarity* s, l3d_similarity& T) {
 // alike, so that the latter reproduces a pass from the similarity the call returned.
 void unit_quaternion(const l3d_similarity& T, double qh[4]) {
     for (int i = 0; i < 4; ++i) qh[i] = T.q[i];
-    normalise(qh);
+    quat_normalise(qh);
 }
 
 void transform_host(size_t n, const double* segs, const l3d_similarity& T, double* out) {
@@ -74,20 +69,6 @@ void transform_host(size_t n, const double* segs, const l3d_similarity& T, doubl
     unit_quaternion(T, qh);
     sim_rotation(qh, R);
     for (size_t i = 0; i < 2 * n; ++i) sim_point(T.scale, R, T.t, segs + 3 * i, out + 3 * i);
-}
-
-// midpoint c and diagonal of the bounding box of the n > 0 segments' end points
-void bounding_box(size_t n, const double* segs, double c[3], double& diag) {
-    double lo[3] = {segs[0], segs[1], segs[2]}, hi[3] = {segs[0], segs[1], segs[2]};
-    for (size_t i = 0; i < 2 * n; ++i)
-        for (int k = 0; k < 3; ++k) {
-            const double v = segs[3 * i + k];
-            if (v < lo[k]) lo[k] = v;
-            if (v > hi[k]) hi[k] = v;
-        }
-    double e[3];
-    for (int k = 0; k < 3; ++k) { c[k] = (lo[k] + hi[k]) * 0.5; e[k] = hi[k] - lo[k]; }
-    diag = std::sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
 }
 
 // H delta = -b by a plain Cholesky factorisation H = L L^T, column by column (DESIGN §23 writes the loops out; they are
@@ -98,12 +79,12 @@ bool solve_normal(const double* s, bool with_scale, double delta[7]) {
     int idx[7], n = 0;
     for (int i = 0; i < 7; ++i)
         if (with_scale || i != 3) idx[n++] = i;
-    double H[7 * 7] = {}, rhs[7], x[7];
+    double H[7 * 7] = {}, rhs[7], x[7], work[kCholeskyWork];
     for (int i = 0; i < n; ++i) {
         for (int j = i; j < n; ++j) H[i * n + j] = s[kRow[idx[i]] + (idx[j] - idx[i])];
         rhs[i] = -s[28 + idx[i]];
     }
-    if (!cholesky_solve(n, H, rhs, x)) return false;
+    if (!cholesky_solve(n, H, rhs, x, work)) return false;
     for (int i = 0; i < 7; ++i) delta[i] = 0.0;
     for (int i = 0; i < n; ++i) delta[idx[i]] = x[i];
     return true;
@@ -111,20 +92,11 @@ bool solve_normal(const double* s, bool with_scale, double delta[7]) {
 
 // step 6: the update about c
 void update(l3d_similarity& T, const double delta[7], const double c[3]) {
-    double dq[4] = {1.0, delta[0] * 0.5, delta[1] * 0.5, delta[2] * 0.5};
-    normalise(dq);
     double dR[9];
-    sim_rotation(dq, dR);
+    quat_step(delta, T.q, dR);
     const double m = 1.0 + delta[3];
-    const double* q = T.q;
-    double qn[4] = {((dq[0] * q[0] - dq[1] * q[1]) - dq[2] * q[2]) - dq[3] * q[3],
-                    ((dq[0] * q[1] + dq[1] * q[0]) + dq[2] * q[3]) - dq[3] * q[2],
-                    ((dq[0] * q[2] - dq[1] * q[3]) + dq[2] * q[0]) + dq[3] * q[1],
-                    ((dq[0] * q[3] + dq[1] * q[2]) - dq[2] * q[1]) + dq[3] * q[0]};
-    normalise(qn);
     const d3 u = mul33(dR, d3{T.t[0] - c[0], T.t[1] - c[1], T.t[2] - c[2]});
     T.scale = T.scale * m;
-    for (int i = 0; i < 4; ++i) T.q[i] = qn[i];
     T.t[0] = (c[0] + m * u.x) + delta[4]; T.t[1] = (c[1] + m * u.y) + delta[5]; T.t[2] = (c[2] + m * u.z) + delta[6];
 }
 

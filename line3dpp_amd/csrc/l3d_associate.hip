@@ -136,41 +136,24 @@ int l3d_associate_view_segments(l3d_ctx* c, uint32_t n_views, const uint32_t* ca
     if (!(near_plane > 0.0) || !std::isfinite(near_plane)) return fail(L3D_ERR_ARG, "the near plane must be positive and finite");
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     if (int rc = lines_ready(c, "segments are associated", "associate with")) return rc;
-    std::vector<const HostView*> views(n_views);
-    std::vector<uint32_t> sorted(camIDs, camIDs + n_views);
-    std::sort(sorted.begin(), sorted.end());
-    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return fail(L3D_ERR_ARG, "a camera ID is named twice");
+    ContextViews V;
+    if (int rc = context_views(c, n_views, camIDs, nullptr, V)) return rc;
     uint64_t n_seg = 0;
-    for (uint32_t k = 0; k < n_views; ++k) {
-        auto f = c->views.find(camIDs[k]);
-        if (f == c->views.end()) return fail(L3D_ERR_ARG, "unknown camera ID");
-        views[k] = f->second.get();
-        n_seg += views[k]->M;
-    }
-    if (n_seg >= ((uint64_t)1 << 32)) return fail(L3D_ERR_LIMIT, "2^32 or more segments in total");
-    std::vector<uint32_t> m(n_views);
-    std::vector<const float*> seg(n_views);
-    for (uint32_t k = 0; k < n_views; ++k) {
-        m[k] = views[k]->M; seg[k] = views[k]->segs.data();
-        for (size_t i = 0; i < 4 * (size_t)m[k]; ++i)
-            if (!std::isfinite(seg[k][i]))
-                return fail(L3D_ERR_ARG, "camera " + std::to_string(k) + ": segment " + std::to_string(i / 4) + " has a non-finite entry");
-    }
+    if (int rc = check_camera_segments(n_views, V.m.data(), V.seg.data(), n_seg)) return rc;
+    const std::vector<uint32_t>& m = V.m;
     if (!out) {                                     // the sizes only
         offsets[0] = 0;
         for (uint32_t k = 0; k < n_views; ++k) offsets[k + 1] = offsets[k] + m[k];
         return L3D_OK;
     }
-    std::vector<l3d_camera> cams(n_views);
-    for (uint32_t k = 0; k < n_views; ++k) cams[k] = camera_of(*views[k]);
     std::vector<uint32_t> n_rec;
-    if (int rc = project_context_lines(c, n_views, cams.data(), near_plane, n_rec)) return rc;
+    if (int rc = project_context_lines(c, n_views, V.cams.data(), near_plane, n_rec)) return rc;
     for (uint32_t k = 0; k < n_views; ++k)
         if (n_rec[k] >= 0x80000000u) return fail(L3D_ERR_LIMIT, "camera " + std::to_string(k) + " has 2^31 or more records");
     std::vector<l3d_association> res(n_seg);
     float ms = 0.0f;
     if (n_seg)
-        if (int rc = associate_core(c->proj, c->stream, n_views, n_rec.data(), c->proj_records.data(), m.data(), seg.data(), *params,
+        if (int rc = associate_core(c->proj, c->stream, n_views, n_rec.data(), c->proj_records.data(), m.data(), V.seg.data(), *params,
                                     res.data(), c->timing_level >= 2 ? &ms : nullptr))
             return rc;
     if (c->timing_level >= 2) g_assoc_kernel_ns.store((uint64_t)((double)ms * 1e6), std::memory_order_relaxed);

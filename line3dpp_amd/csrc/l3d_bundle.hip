@@ -28,18 +28,10 @@ using namespace l3d;
 
 namespace {
 
-struct BundleResult {
-    std::vector<double> segs;                    // the output model
-    std::vector<uint32_t> seg_line;
-    std::vector<uint32_t> seg_off;               // [n_lines + 1] where a line's segments begin in it
-    std::vector<l3d_bundle_line> lines;
-    std::vector<l3d_refit_observation> obs;      // line after line
-    std::vector<uint32_t> obs_off;               // [n_lines + 1]
-    std::vector<l3d_association> assoc;
+struct BundleResult : LinesResult<l3d_bundle_line, l3d_bundle_summary> {
     std::vector<l3d_camera> cams;
     std::vector<l3d_bundle_iteration> trace;
     std::vector<double> system, rhs;             // of the captured iteration: [n x n] (upper triangle set), [n]
-    l3d_bundle_summary sum{};
 };
 
 }  // namespace
@@ -71,73 +63,12 @@ int check_params(const l3d_bundle_params* p) {
     return L3D_OK;
 }
 
-l3d_association no_association() { return l3d_association{-1, 0xFFFFFFFFu, 0xFFFFFFFFu, 0.0f, 0.0f, 0u}; }
-
-// every line as given: EMPTY without a segment, else HELD with its carrier
-void lines_as_given(const Job& J, const ModelLines& ml, BundleResult& R) {
-    R.lines.assign(ml.n_lines, l3d_bundle_line{});
-    for (uint32_t l = 0; l < ml.n_lines; ++l) {
-        l3d_bundle_line& L = R.lines[l];
-        if (ml.off[l] == ml.off[l + 1]) { L.status = L3D_BUNDLE_EMPTY; continue; }
-        L.status = L3D_BUNDLE_HELD;
-        const double* a = J.segs + 6 * (size_t)ml.seg[ml.off[l]];
-        const double* b = J.segs + 6 * (size_t)ml.seg[ml.off[l + 1] - 1] + 3;
-        for (int k = 0; k < 3; ++k) { L.P1[k] = a[k]; L.P2[k] = b[k]; }
-    }
-    R.obs_off.assign((size_t)ml.n_lines + 1, 0);
-}
-
-// the output model and the summary's counts from the lines' statuses and the BUNDLED lines' pieces
-void assemble(const Job& J, const ModelLines& ml, const std::vector<std::vector<double>>& pieces, BundleResult& R) {
-    R.segs.clear(); R.seg_line.clear();
-    R.seg_off.assign((size_t)ml.n_lines + 1, 0);
-    R.sum.n_lines = ml.n_lines;
-    R.sum.n_segments_before = J.n_model;
-    for (uint32_t l = 0; l < ml.n_lines; ++l) {
-        l3d_bundle_line& L = R.lines[l];
-        if (L.status == L3D_BUNDLE_BUNDLED) {
-            R.segs.insert(R.segs.end(), pieces[l].begin(), pieces[l].end());
-            R.seg_line.insert(R.seg_line.end(), pieces[l].size() / 6, l);
-        } else {
-            for (uint32_t k = ml.off[l]; k < ml.off[l + 1]; ++k) {
-                R.segs.insert(R.segs.end(), J.segs + 6 * (size_t)ml.seg[k], J.segs + 6 * (size_t)ml.seg[k] + 6);
-                R.seg_line.push_back(l);
-            }
-        }
-        R.seg_off[l + 1] = (uint32_t)R.seg_line.size();
-        L.n_pieces = R.seg_off[l + 1] - R.seg_off[l];
-        ++R.sum.n_status[L.status];
-    }
-    R.sum.n_segments_after = R.seg_line.size();
-}
-
-// S delta = -g for the symmetric S of n rows whose upper triangle S[i * n + j], i <= j, is read: the loops of
-// cholesky_solve (l3d_model.h) on heap storage.  false: a pivot that is not finite and > 0, delta untouched.
+// S delta = -g for the symmetric S of n rows whose upper triangle S[i * n + j], i <= j, is read, by cholesky_solve
+// (l3d_model.h) on heap storage.  false: a pivot that is not finite and > 0, delta untouched.
 bool dense_solve(size_t n, const double* S, const double* g, double* delta) {
-    std::vector<double> L(n * n, 0.0), y(n), z(n);
-    for (size_t j = 0; j < n; ++j) {
-        double p = S[j * n + j];
-        for (size_t k = 0; k < j; ++k) p = p - L[j * n + k] * L[j * n + k];
-        if (!(p > 0.0) || !std::isfinite(p)) return false;
-        L[j * n + j] = std::sqrt(p);
-        for (size_t i = j + 1; i < n; ++i) {
-            double v = S[j * n + i];
-            for (size_t k = 0; k < j; ++k) v = v - L[i * n + k] * L[j * n + k];
-            L[i * n + j] = v / L[j * n + j];
-        }
-    }
-    for (size_t i = 0; i < n; ++i) {
-        double v = -g[i];
-        for (size_t k = 0; k < i; ++k) v = v - L[i * n + k] * y[k];
-        y[i] = v / L[i * n + i];
-    }
-    for (size_t i = n; i-- > 0;) {
-        double v = y[i];
-        for (size_t k = i + 1; k < n; ++k) v = v - L[k * n + i] * z[k];
-        z[i] = v / L[i * n + i];
-    }
-    for (size_t i = 0; i < n; ++i) delta[i] = z[i];
-    return true;
+    std::vector<double> work(n * (n + 1)), rhs(n);
+    for (size_t i = 0; i < n; ++i) rhs[i] = -g[i];
+    return cholesky_solve(n, S, rhs.data(), delta, work.data());
 }
 
 // where the stage's tables lie behind `base`, for given counts
@@ -192,27 +123,13 @@ int bundle_core(ProjWork& w, hipStream_t st, const Job& J, const uint8_t* fixed,
     R.assoc = std::move(O.assoc);
     R.sum.n_ambiguous_left_out = O.n_ambiguous_left_out;
     R.sum.n_observations = n_obs;
-    lines_as_given(J, ml, R);
+    lines_as_given(J, ml, L3D_BUNDLE_EMPTY, L3D_BUNDLE_HELD, R);
     R.obs_off = O.obs_off;
     const std::vector<uint32_t>& obs_off = R.obs_off;
-    // the cells: within a line the observations come in ascending flat index, so a camera's are neighbours
-    R.obs.resize(n_obs);
-    std::vector<uint32_t> cell_off, cell_line, cell_cam, line_cell_off((size_t)n_lines + 1, 0);
-    for (uint32_t l = 0; l < n_lines; ++l) {
-        uint32_t last_cam = 0xFFFFFFFFu;
-        for (uint32_t r = obs_off[l]; r < obs_off[l + 1]; ++r) {
-            const uint32_t flat = O.oseg[O.csr[r]];
-            const uint32_t cam = (uint32_t)(std::upper_bound(O.seg_begin.begin(), O.seg_begin.end(), flat) - O.seg_begin.begin()) - 1;
-            if (cam != last_cam) {
-                cell_off.push_back(r);
-                cell_line.push_back(l); cell_cam.push_back(cam);
-                last_cam = cam;
-            }
-            R.obs[r] = l3d_refit_observation{cam, flat - O.seg_begin[cam], l, 0u, 0.0, 0.0};
-        }
-        line_cell_off[l + 1] = (uint32_t)cell_line.size();
-    }
-    cell_off.push_back(n_obs);
+    RefitCells cells;
+    refit_list_observations(O, n_lines, R.obs, cells);
+    const std::vector<uint32_t>&cell_off = cells.cell_off, &cell_line = cells.cell_line, &cell_cam = cells.cell_cam,
+                               &line_cell_off = cells.line_cell_off;
     const uint32_t n_cells = (uint32_t)cell_line.size();
     R.sum.n_cells = n_cells;
     // eligible lines, carriers about the centre
@@ -428,43 +345,24 @@ int bundle_core(ProjWork& w, hipStream_t st, const Job& J, const uint8_t* fixed,
         if (is_eligible[l] && R.sum.accepted_steps)
             for (int k = 0; k < 3; ++k) { R.lines[l].P1[k] = q[k] + c[k]; R.lines[l].P2[k] = q[3 + k] + c[k]; }
     }
-    std::vector<std::vector<double>> pieces(n_lines);
+    RefitPieces pieces(n_lines);
     if (n_elig) {
         // §28's stages 8 and 9 on the new carriers and cameras
+        std::vector<RefitCut> cuts;
+        for (uint32_t l : eligible) {
+            R.lines[l].status = L3D_BUNDLE_NO_EXTENT;
+            cuts.push_back(RefitCut{l, obs_off[l], obs_off[l], obs_off[l + 1] - obs_off[l], finite6(&AB[6 * (size_t)l]) ? &carrier[6 * (size_t)l] : nullptr});
+        }
         put(P.locam, locam.data(), sizeof(LoCam) * n_cams); put(P.carrier, carrier.data(), 48 * (size_t)n_lines);
         e = hipMemcpyAsync(d + P.locam, h + P.locam, sizeof(LoCam) * n_cams, hipMemcpyHostToDevice, st);
         if (e == hipSuccess) e = hipMemcpyAsync(d + P.carrier, h + P.carrier, 48 * (size_t)n_lines, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = timer.start(st);
-        if (e == hipSuccess) e = launch_refit_spans(oa, st);
-        if (e == hipSuccess) e = timer.stop(st);
-        if (e == hipSuccess) e = hipMemcpyAsync(h + P.spans, d + P.spans, sizeof(RefitSpan) * n_obs, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
         if (e != hipSuccess) return hip_fail(e);
-        timer.add();
-        const RefitSpan* span = (const RefitSpan*)(h + P.spans);
-        std::vector<uint32_t> cam_open(n_cams, 0), cams_v;
-        std::vector<double> lo_v, hi_v, cut;
-        for (uint32_t l : eligible) {
-            l3d_bundle_line& L = R.lines[l];
-            L.status = L3D_BUNDLE_NO_EXTENT;
-            if (!finite6(&AB[6 * (size_t)l])) continue;
-            lo_v.clear(); hi_v.clear(); cams_v.clear(); cut.clear();
-            for (uint32_t r = obs_off[l]; r < obs_off[l + 1]; ++r) {
-                l3d_refit_observation& ob = R.obs[r];
-                const RefitSpan& sp = span[r];
-                ob.valid = sp.valid; ob.s_lo = sp.valid ? sp.lo : 0.0; ob.s_hi = sp.valid ? sp.hi : 0.0;
-                if (ob.valid) { lo_v.push_back(sp.lo); hi_v.push_back(sp.hi); cams_v.push_back(ob.camera); }
-            }
-            const double* M = &carrier[6 * (size_t)l]; const double* u = M + 3;
-            const double u_norm = std::sqrt((u[0] * u[0] + u[1] * u[1]) + u[2] * u[2]);
-            refit_sweep((uint32_t)lo_v.size(), lo_v.data(), hi_v.data(), cams_v.data(), p.visibility, p.min_length, u_norm, cam_open, cut);
-            if (cut.empty()) continue;
-            L.status = L3D_BUNDLE_BUNDLED;
-            for (size_t k = 0; k < cut.size(); ++k)
-                for (int i = 0; i < 3; ++i) pieces[l].push_back((M[i] + cut[k] * u[i]) + c[i]);
-        }
+        if (int rc = refit_cut_lines(st, timer, oa, (RefitSpan*)(h + P.spans), cuts, n_cams, p.visibility, p.min_length, c, "bundle", R.obs, pieces))
+            return rc;
+        for (uint32_t l : eligible)
+            if (pieces.n[l]) R.lines[l].status = L3D_BUNDLE_BUNDLED;
     }
-    assemble(J, ml, pieces, R);
+    assemble(J, ml, pieces, L3D_BUNDLE_BUNDLED, R);
     if (kernel_ms) *kernel_ms = ms[0] + ms[1] + ms[2];
     return L3D_OK;
 }
@@ -484,11 +382,11 @@ int prepare(const Job& J, const uint8_t* fixed, const l3d_bundle_params& p, doub
     if ((uint64_t)ml.n_lines * J.n_cams >= ((uint64_t)1 << 28)) return fail(L3D_ERR_LIMIT, "lines x cameras reach 2^28: the slot table is dense");
     if (J.n_model && J.n_cams && n_seg) { done = false; return L3D_OK; }
     // an empty model, no camera or no 2D segment: everything as given
-    lines_as_given(J, ml, R);
+    lines_as_given(J, ml, L3D_BUNDLE_EMPTY, L3D_BUNDLE_HELD, R);
     R.assoc.assign((size_t)n_seg, no_association());
     R.cams.assign(J.cams, J.cams + J.n_cams);
     R.sum.status = L3D_BUNDLE_NO_VARIABLES;
-    assemble(J, ml, std::vector<std::vector<double>>(ml.n_lines), R);
+    assemble(J, ml, RefitPieces(ml.n_lines), L3D_BUNDLE_BUNDLED, R);
     return L3D_OK;
 }
 
@@ -502,13 +400,8 @@ int l3d_bundle_segments(int device, uint32_t n_segments, const double* segs6, co
     if (int rc = check_params(params)) return rc;
     if (!out) return fail(L3D_ERR_ARG, "null argument");
     if (int rc = check_model(nullptr, n_segments, segs6, line)) return rc;
-    if (n_cams && (!cams || !n_segments_per_cam)) return fail(L3D_ERR_ARG, "null argument");
-    uint64_t n_seg = 0;
-    for (uint32_t k = 0; k < n_cams; ++k) n_seg += n_segments_per_cam[k];
-    if (n_seg && !segs4) return fail(L3D_ERR_ARG, "null argument");
-    std::vector<const float*> seg(n_cams);
-    uint64_t at = 0;
-    for (uint32_t k = 0; k < n_cams; ++k) { seg[k] = segs4 ? segs4 + 4 * at : nullptr; at += n_segments_per_cam[k]; }
+    std::vector<const float*> seg;
+    if (int rc = camera_segments(n_cams, cams, n_segments_per_cam, segs4, seg)) return rc;
     const Job J{n_segments, segs6, line, n_cams, cams, n_segments_per_cam, seg.data()};
     auto bd = std::make_unique<l3d_bundle>();
     double c[3]; bool done; ModelLines ml;
@@ -530,22 +423,8 @@ int l3d_bundle_view_lines(l3d_ctx* c, uint32_t n_views, const uint32_t* camIDs, 
     if (int rc = check_params(params)) return rc;
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     if (int rc = lines_ready(c, "lines are bundled", "bundle")) return rc;
-    std::vector<uint32_t> sorted(camIDs, camIDs + n_views);
-    std::sort(sorted.begin(), sorted.end());
-    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return fail(L3D_ERR_ARG, "a camera ID is named twice");
-    std::vector<l3d_camera> cams(n_views);
-    std::vector<uint32_t> m(n_views);
-    std::vector<const float*> seg(n_views);
-    for (uint32_t k = 0; k < n_views; ++k) {
-        auto f = c->views.find(camIDs[k]);
-        if (f == c->views.end()) return fail(L3D_ERR_ARG, "unknown camera ID");
-        cams[k] = cams_in ? cams_in[k] : camera_of(*f->second);
-        m[k] = f->second->M; seg[k] = f->second->segs.data();
-    }
-    std::vector<double> P6; std::vector<uint32_t> line;
-    context_segments(c, P6, line);
-    if (int rc = check_model("context's", line.size(), P6.data(), line.data())) return rc;
-    const Job J{(uint32_t)line.size(), P6.data(), line.data(), n_views, cams.data(), m.data(), seg.data()};
+    ContextViews V; Job J;
+    if (int rc = context_job(c, n_views, camIDs, cams_in, V, J)) return rc;
     auto bd = std::make_unique<l3d_bundle>();
     BundleResult& R = bd->r;
     double ctr[3]; bool done; ModelLines ml;
@@ -559,24 +438,7 @@ int l3d_bundle_view_lines(l3d_ctx* c, uint32_t n_views, const uint32_t* camIDs, 
     }
     // the bundled model takes the place of lines3D_: the BUNDLED lines change, every other line is untouched; the views'
     // cameras stay as they are
-    auto seg3 = [](const double* a, const double* b) {
-        const d3 P1{a[0], a[1], a[2]}, P2{b[0], b[1], b[2]};
-        ReconSeg3D s = segment3d(P1, P2);
-        s.P1 = P1; s.P2 = P2;
-        return s;
-    };
-    for (uint32_t l = 0; l < ml.n_lines; ++l) {
-        const l3d_bundle_line& bl = R.lines[l];
-        if (bl.status != L3D_BUNDLE_BUNDLED) continue;
-        ReconLine& L = c->lines3D[l];
-        L.collinear.clear();
-        for (uint32_t k = R.seg_off[l]; k < R.seg_off[l + 1]; ++k) L.collinear.push_back(seg3(&R.segs[6 * (size_t)k], &R.segs[6 * (size_t)k + 3]));
-        L.cluster_seg = seg3(bl.P1, bl.P2);
-        L.residuals.clear();
-        for (uint32_t r = R.obs_off[l]; r < R.obs_off[l + 1]; ++r) L.residuals.emplace_back(camIDs[R.obs[r].camera], R.obs[r].segment);
-    }
-    if (R.sum.n_status[L3D_BUNDLE_BUNDLED]) {              // (else the model is what it was, bit for bit, and so is its name)
-        c->proj_records.clear();                           // (they hold the lines as they were)
+    if (context_take_lines(c, camIDs, R, lines_cut_anew(R.lines, L3D_BUNDLE_BUNDLED))) {   // (else the model is what it was, bit for bit, and so is its name)
         c->lines_bundled = true;
         c->bundle_distance = params->max_distance;
     }

@@ -6,7 +6,8 @@
 //   l3d_output.hip         get3Dlines and the result writers (TXT / OBJ / STL)
 //   l3d_lineopt.hip        line bundling (optimizeClusters) between the clustering and the final 3D segments
 //   l3d_seam.hip           the accelerator-seam entries (cudawrapper.h:54-80) with CPU-path semantics
-//   l3d_model.hip          what the stages on the 3D lines as a flat model share (project, associate, compare, merge)
+//   l3d_model.hip          what the stages on the 3D lines as a flat model share (project, associate, compare, merge), and
+//                          the entries on a model, cameras and their 2D segments (refine, refit, bundle)
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -154,6 +155,31 @@ void context_segments(const ::l3d_ctx* c, std::vector<double>& P6, std::vector<u
 // the context forms' opening (mutex held): "<busy> while a split call is open" (null: not checked), "no 3D lines to <verb>: ..."
 int lines_ready(const ::l3d_ctx* c, const char* busy, const char* verb);
 l3d_camera camera_of(const HostView& v);
+// ---- l3d_model.hip: what the stages on a model, cameras and the cameras' 2D segments share (DESIGN §27-§29, and §17's
+// context entry) ----
+struct RefitJob; struct RefitModel; struct NewLine;   // l3d_refit.h
+l3d_association no_association();            // of a 2D segment that no line was assigned to
+// the near plane, the cameras' sides and entries as stage 1 checks them, and the form of K the closed K^-T needs: upper
+// triangular with K22 = 1 and K00, K11 not 0; no_skew: then K01 = 0 as well, which is what LoCam can hold (§28, §29)
+int check_pose_cameras(uint32_t n_cams, const l3d_camera* cams, double near_plane, bool no_skew);
+// every camera's 2D segments: fewer than 2^32 in all (n_total: how many), a pointer where there are some, finite entries
+int check_camera_segments(uint32_t n_cams, const uint32_t* n_seg, const float* const* seg, uint64_t& n_total);
+// the stateless entries' cameras and segs4, camera after camera: their null checks, and seg[k] = camera k's segments
+int camera_segments(uint32_t n_cams, const l3d_camera* cams, const uint32_t* n_segments_per_cam, const float* segs4,
+                    std::vector<const float*>& seg);
+// The context entries' views camIDs (mutex held): refused for an ID named twice, then for an unknown ID; cams: cams_in
+// where given, else the views' own; m, seg: the views' segments.  context_job: then the context's lines as the model of J
+// (check_model's "context's" messages).  J points into V.
+struct ContextViews {
+    std::vector<l3d_camera> cams; std::vector<uint32_t> m; std::vector<const float*> seg;
+    std::vector<double> P6; std::vector<uint32_t> line;
+};
+int context_views(const ::l3d_ctx* c, uint32_t n_views, const uint32_t* camIDs, const l3d_camera* cams_in, ContextViews& V);
+int context_job(const ::l3d_ctx* c, uint32_t n_views, const uint32_t* camIDs, const l3d_camera* cams_in, ContextViews& V, RefitJob& J);
+// A refit or bundled model R takes the place of the context's lines: every line of `anew` gets R's segments of it as
+// `collinear`, its carrier as `cluster_seg` and its observations, in the views camIDs, as `residuals`; every other line is
+// untouched.  true: a line changed, and proj_records, which held the lines as they were, are cleared.
+bool context_take_lines(::l3d_ctx* c, const uint32_t* camIDs, const RefitModel& R, const std::vector<NewLine>& anew);
 // l3d_wireframe.hip: stage 1 of §24, the junctions of a model (n > 0, arguments checked), for the wireframe and for the
 // planes of §25.  With `keep` the list is not downloaded: it stays in w.keys, the model in w.d, until w is used again.
 struct WfRecord;                             // l3d_wireframe.h

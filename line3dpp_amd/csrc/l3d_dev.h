@@ -47,6 +47,24 @@ L3D_HD void sim_rotation(const double q[4], double R[9]) {
     R[3] = 2.0 * (x * y + w * z);       R[4] = 1.0 - 2.0 * (x * x + z * z); R[5] = 2.0 * (y * z - w * x);
     R[6] = 2.0 * (x * z - w * y);       R[7] = 2.0 * (y * z + w * x);       R[8] = 1.0 - 2.0 * (x * x + y * y);
 }
+// q / |q|
+L3D_HD void quat_normalise(double q[4]) {
+    const double n = sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
+    for (int i = 0; i < 4; ++i) q[i] = q[i] / n;
+}
+// The rotation part of a step omega (§23 step 6, §27 step 5): dq = (1, omega / 2) normalised, dR = R(dq), and
+// q <- dq (x) q, normalised
+L3D_HD void quat_step(const double omega[3], double q[4], double dR[9]) {
+    double dq[4] = {1.0, omega[0] * 0.5, omega[1] * 0.5, omega[2] * 0.5};
+    quat_normalise(dq);
+    sim_rotation(dq, dR);
+    const double qn[4] = {((dq[0] * q[0] - dq[1] * q[1]) - dq[2] * q[2]) - dq[3] * q[3],
+                          ((dq[0] * q[1] + dq[1] * q[0]) + dq[2] * q[3]) - dq[3] * q[2],
+                          ((dq[0] * q[2] - dq[1] * q[3]) + dq[2] * q[0]) + dq[3] * q[1],
+                          ((dq[0] * q[3] + dq[1] * q[2]) - dq[2] * q[1]) + dq[3] * q[0]};
+    for (int i = 0; i < 4; ++i) q[i] = qn[i];
+    quat_normalise(q);
+}
 // y_i = scale * (R_i0 x0 + R_i1 x1 + R_i2 x2) + t_i
 L3D_HD void sim_point(double scale, const double R[9], const double t[3], const double* x, double* y) {
     const d3 v = mul33(R, d3{x[0], x[1], x[2]});

@@ -1,6 +1,7 @@
 // l3d_model.h -- the sizes and the slicing that the stages on a flat model of 3D segments share (DESIGN §16-§19:
-// project, associate, compare, merge; their host plumbing is l3d_model.hip, declared in l3d_ctx.h).  Plain C++17 without
-// a HIP include (g++ compiles it for tests/test_model_slicing.py).
+// project, associate, compare, merge; their host plumbing is l3d_model.hip, declared in l3d_ctx.h), and the bounding box
+// and the Cholesky solve of the stages that iterate about a model's centre (§23, §27-§29).  Plain C++17 without a HIP
+// include (g++ compiles it for tests/test_model_slicing.py).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -38,35 +39,51 @@ inline SlicePlan slice_plan(uint32_t n_queries, uint32_t n_refs, uint32_t asked_
     return p;
 }
 
-// H x = rhs for a symmetric H of n <= kCholeskyMax rows, of which the upper triangle H[i * n + j], i <= j, is read, by a
-// plain Cholesky factorisation H = L L^T, column by column, then the forward and the backward substitution: the loops
-// DESIGN §23 writes out, which the alignment (n = 6 or 7) and the pose refinement of §27 (n = 6) share.  false: a pivot
-// that is not finite and > 0, x untouched.
-constexpr int kCholeskyMax = 7;
-inline bool cholesky_solve(int n, const double* H, const double* rhs, double* x) {
-    double L[kCholeskyMax][kCholeskyMax] = {}, y[kCholeskyMax], z[kCholeskyMax];
-    for (int j = 0; j < n; ++j) {
+// midpoint c and diagonal of the bounding box of the n > 0 segments' end points (the centre about which the
+// alignment, the pose refinement, the refit and the bundle work)
+inline void bounding_box(size_t n, const double* segs, double c[3], double& diag) {
+    double lo[3] = {segs[0], segs[1], segs[2]}, hi[3] = {segs[0], segs[1], segs[2]};
+    for (size_t i = 0; i < 2 * n; ++i)
+        for (int k = 0; k < 3; ++k) {
+            const double v = segs[3 * i + k];
+            if (v < lo[k]) lo[k] = v;
+            if (v > hi[k]) hi[k] = v;
+        }
+    double e[3];
+    for (int k = 0; k < 3; ++k) { c[k] = (lo[k] + hi[k]) * 0.5; e[k] = hi[k] - lo[k]; }
+    diag = std::sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
+}
+
+// H x = rhs for a symmetric H of n rows, of which the upper triangle H[i * n + j], i <= j, is read, by a plain Cholesky
+// factorisation H = L L^T, column by column, then the forward and the backward substitution: the loops DESIGN §23 writes
+// out, which the alignment (n = 6 or 7), the pose refinement of §27 (n = 6) and the reduced camera system of §29 share.
+// work: n * (n + 1) doubles of the caller's -- kCholeskyWork on the stack for n <= kCholeskyMax, the heap beyond; x may be
+// rhs.  false: a pivot that is not finite and > 0, x untouched.
+constexpr size_t kCholeskyMax = 7, kCholeskyWork = kCholeskyMax * (kCholeskyMax + 1);
+inline bool cholesky_solve(size_t n, const double* H, const double* rhs, double* x, double* work) {
+    double* L = work;            // [n x n], the lower triangle
+    double* y = work + n * n;
+    for (size_t j = 0; j < n; ++j) {
         double p = H[j * n + j];
-        for (int k = 0; k < j; ++k) p = p - L[j][k] * L[j][k];
+        for (size_t k = 0; k < j; ++k) p = p - L[j * n + k] * L[j * n + k];
         if (!(p > 0.0) || !std::isfinite(p)) return false;
-        L[j][j] = std::sqrt(p);
-        for (int i = j + 1; i < n; ++i) {
+        L[j * n + j] = std::sqrt(p);
+        for (size_t i = j + 1; i < n; ++i) {
             double v = H[j * n + i];
-            for (int k = 0; k < j; ++k) v = v - L[i][k] * L[j][k];
-            L[i][j] = v / L[j][j];
+            for (size_t k = 0; k < j; ++k) v = v - L[i * n + k] * L[j * n + k];
+            L[i * n + j] = v / L[j * n + j];
         }
     }
-    for (int i = 0; i < n; ++i) {
+    for (size_t i = 0; i < n; ++i) {
         double v = rhs[i];
-        for (int k = 0; k < i; ++k) v = v - L[i][k] * y[k];
-        y[i] = v / L[i][i];
+        for (size_t k = 0; k < i; ++k) v = v - L[i * n + k] * y[k];
+        y[i] = v / L[i * n + i];
     }
-    for (int i = n - 1; i >= 0; --i) {
+    for (size_t i = n; i-- > 0;) {
         double v = y[i];
-        for (int k = i + 1; k < n; ++k) v = v - L[k][i] * z[k];
-        z[i] = v / L[i][i];
+        for (size_t k = i + 1; k < n; ++k) v = v - L[k * n + i] * x[k];
+        x[i] = v / L[i * n + i];
     }
-    for (int i = 0; i < n; ++i) x[i] = z[i];
     return true;
 }
 

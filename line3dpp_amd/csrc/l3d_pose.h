@@ -9,11 +9,6 @@
 
 namespace l3d {
 
-inline void pose_normalise(double q[4]) {
-    const double n = std::sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
-    for (int i = 0; i < 4; ++i) q[i] = q[i] / n;
-}
-
 // the delta (q, tau) on the input pose, t'_in = t_in + R_in c, and whether a step has been applied
 struct PoseDelta {
     double q[4] = {1.0, 0.0, 0.0, 0.0}, tau[3] = {0.0, 0.0, 0.0}, tin[3] = {0.0, 0.0, 0.0};
@@ -23,7 +18,7 @@ struct PoseDelta {
 // R = R(q^) R_in and t' = R(q^) t'_in + tau: the pose in the frame about c
 inline void pose_about_centre(const l3d_camera& in, const PoseDelta& s, double R[9], double tc[3]) {
     double qh[4] = {s.q[0], s.q[1], s.q[2], s.q[3]}, Rd[9];
-    pose_normalise(qh);
+    quat_normalise(qh);
     sim_rotation(qh, Rd);
     for (int i = 0; i < 3; ++i)
         for (int j = 0; j < 3; ++j) R[3 * i + j] = (Rd[3 * i] * in.R[j] + Rd[3 * i + 1] * in.R[3 + j]) + Rd[3 * i + 2] * in.R[6 + j];
@@ -42,20 +37,11 @@ inline l3d_camera pose_camera_now(const l3d_camera& in, const PoseDelta& s, cons
     return out;
 }
 
-// step 5's update of the delta: q <- dq (x) q, normalised; tau <- dR tau + delta_3..5
+// step 5's update of the delta: q <- dq (x) q, normalised (quat_step of l3d_dev.h, the alignment's); tau <- dR tau + delta_3..5
 inline void pose_update(PoseDelta& s, const double delta[6]) {
-    double dq[4] = {1.0, delta[0] * 0.5, delta[1] * 0.5, delta[2] * 0.5};
-    pose_normalise(dq);
     double dR[9];
-    sim_rotation(dq, dR);
-    const double* q = s.q;
-    double qn[4] = {((dq[0] * q[0] - dq[1] * q[1]) - dq[2] * q[2]) - dq[3] * q[3],
-                    ((dq[0] * q[1] + dq[1] * q[0]) + dq[2] * q[3]) - dq[3] * q[2],
-                    ((dq[0] * q[2] - dq[1] * q[3]) + dq[2] * q[0]) + dq[3] * q[1],
-                    ((dq[0] * q[3] + dq[1] * q[2]) - dq[2] * q[1]) + dq[3] * q[0]};
-    pose_normalise(qn);
+    quat_step(delta, s.q, dR);
     const d3 u = mul33(dR, d3{s.tau[0], s.tau[1], s.tau[2]});
-    for (int i = 0; i < 4; ++i) s.q[i] = qn[i];
     s.tau[0] = u.x + delta[3]; s.tau[1] = u.y + delta[4]; s.tau[2] = u.z + delta[5];
     s.updated = true;
 }

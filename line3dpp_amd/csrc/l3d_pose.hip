@@ -16,6 +16,7 @@
 
 #include "l3d_ctx.h"
 #include "l3d_pose.h"
+#include "l3d_refit.h"
 
 namespace l3d {
 // test hooks (l3d_debug_counter): iterations run (summed over the cameras) and launches of k_pose_normal so far, and the
@@ -44,31 +45,6 @@ int check_params(const l3d_pose_params* p) {
     return L3D_OK;
 }
 
-// the near plane, the cameras' sides and entries as stage 1 checks them, and the form of K the closed K^-T needs
-int check_pose_cameras(uint32_t n_cams, const l3d_camera* cams, double near_plane) {
-    if (int rc = check_projection_cameras(n_cams, cams, near_plane)) return rc;
-    for (uint32_t c = 0; c < n_cams; ++c) {
-        const double* K = cams[c].K;
-        if (!(K[3] == 0.0 && K[6] == 0.0 && K[7] == 0.0 && K[8] == 1.0 && K[0] != 0.0 && K[4] != 0.0))
-            return fail(L3D_ERR_ARG, "camera " + std::to_string(c) + ": K must be upper triangular with K22 = 1 and K00, K11 not 0");
-    }
-    return L3D_OK;
-}
-
-// midpoint c and diagonal of the bounding box of the n > 0 segments' end points (§23's)
-void bounding_box(size_t n, const double* segs, double c[3], double& diag) {
-    double lo[3] = {segs[0], segs[1], segs[2]}, hi[3] = {segs[0], segs[1], segs[2]};
-    for (size_t i = 0; i < 2 * n; ++i)
-        for (int k = 0; k < 3; ++k) {
-            const double v = segs[3 * i + k];
-            if (v < lo[k]) lo[k] = v;
-            if (v > hi[k]) hi[k] = v;
-        }
-    double e[3];
-    for (int k = 0; k < 3; ++k) { c[k] = (lo[k] + hi[k]) * 0.5; e[k] = hi[k] - lo[k]; }
-    diag = std::sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
-}
-
 // one camera's state: the delta (q, tau) on the input pose and t'_in = t_in + R_in c (l3d_pose.h), the gate and how far
 // it has come
 struct CamState : PoseDelta {
@@ -80,12 +56,12 @@ struct CamState : PoseDelta {
 // H delta = -b from the 29 sums (n = 6), by the alignment's Cholesky.  false: a pivot that is not finite and > 0
 bool solve_normal(const double* s, double delta[6]) {
     static const int kRow[6] = {0, 6, 11, 15, 18, 20};   // where row i of the upper triangle begins
-    double H[36] = {}, rhs[6];
+    double H[36] = {}, rhs[6], work[kCholeskyWork];
     for (int i = 0; i < 6; ++i) {
         for (int j = i; j < 6; ++j) H[i * 6 + j] = s[kRow[i] + (j - i)];
         rhs[i] = -s[21 + i];
     }
-    return cholesky_solve(6, H, rhs, delta);
+    return cholesky_solve(6, H, rhs, delta, work);
 }
 
 double step_of(const double delta[6], double diag) {
@@ -97,13 +73,8 @@ double step_of(const double delta[6], double diag) {
     return s;
 }
 
-struct Job {
-    uint32_t n_model; const double* segs; const uint32_t* line;
-    uint32_t n_cams; const l3d_camera* cams; const uint32_t* n_seg; const float* const* seg;
-};
+using Job = RefitJob;
 struct Outputs { l3d_camera* cams; l3d_pose_summary* summaries; l3d_association* assoc; l3d_pose_iteration* trace; };
-
-l3d_association no_association() { return l3d_association{-1, 0xFFFFFFFFu, 0xFFFFFFFFu, 0.0f, 0.0f, 0u}; }
 
 // the offsets of a group's tables behind the model, and where the host's part and the whole end
 struct GroupLayout { size_t pcam, acam, ncam, pose, segs, tiles, assoc, bounds, host_end, vis, rec, out, end; };
@@ -359,16 +330,9 @@ int refine_core(ProjWork& w, hipStream_t st, const Job& J, const l3d_pose_params
 int prepare(const Job& J, const l3d_pose_params& p, const Outputs& o, double c[3], double& diag, bool& done) {
     done = true;
     if (J.n_cams && (!o.cams || !o.summaries)) return fail(L3D_ERR_ARG, "null argument");
-    if (int rc = check_pose_cameras(J.n_cams, J.cams, p.near_plane)) return rc;
+    if (int rc = check_pose_cameras(J.n_cams, J.cams, p.near_plane, false)) return rc;
     uint64_t n_seg = 0;
-    for (uint32_t k = 0; k < J.n_cams; ++k) n_seg += J.n_seg[k];
-    if (n_seg >= ((uint64_t)1 << 32)) return fail(L3D_ERR_LIMIT, "2^32 or more segments in total");
-    for (uint32_t k = 0; k < J.n_cams; ++k) {
-        if (J.n_seg[k] && !J.seg[k]) return fail(L3D_ERR_ARG, "null argument");
-        for (size_t i = 0; i < 4 * (size_t)J.n_seg[k]; ++i)
-            if (!std::isfinite(J.seg[k][i]))
-                return fail(L3D_ERR_ARG, "camera " + std::to_string(k) + ": segment " + std::to_string(i / 4) + " has a non-finite entry");
-    }
+    if (int rc = check_camera_segments(J.n_cams, J.n_seg, J.seg, n_seg)) return rc;
     c[0] = c[1] = c[2] = 0.0; diag = 0.0;
     if (J.n_model) {
         bounding_box(J.n_model, J.segs, c, diag);
@@ -398,13 +362,8 @@ int l3d_refine_cameras(int device, uint32_t n_segments, const double* segs6, con
                        l3d_association* out_assoc, l3d_pose_iteration* trace) {
     if (int rc = check_params(params)) return rc;
     if (int rc = check_model(nullptr, n_segments, segs6, line)) return rc;
-    if (n_cams && (!cams || !n_segments_per_cam)) return fail(L3D_ERR_ARG, "null argument");
-    uint64_t n_seg = 0;
-    for (uint32_t k = 0; k < n_cams; ++k) n_seg += n_segments_per_cam[k];
-    if (n_seg && !segs4) return fail(L3D_ERR_ARG, "null argument");
-    std::vector<const float*> seg(n_cams);
-    uint64_t at = 0;
-    for (uint32_t k = 0; k < n_cams; ++k) { seg[k] = segs4 ? segs4 + 4 * at : nullptr; at += n_segments_per_cam[k]; }
+    std::vector<const float*> seg;
+    if (int rc = camera_segments(n_cams, cams, n_segments_per_cam, segs4, seg)) return rc;
     const Job J{n_segments, segs6, line, n_cams, cams, n_segments_per_cam, seg.data()};
     const Outputs o{out_cams, summaries, out_assoc, trace};
     double c[3], diag; bool done;
@@ -422,22 +381,8 @@ int l3d_refine_view_cameras(l3d_ctx* c, uint32_t n_views, const uint32_t* camIDs
     if (int rc = check_params(params)) return rc;
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     if (int rc = lines_ready(c, "cameras are refined", "refine cameras against")) return rc;
-    std::vector<uint32_t> sorted(camIDs, camIDs + n_views);
-    std::sort(sorted.begin(), sorted.end());
-    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return fail(L3D_ERR_ARG, "a camera ID is named twice");
-    std::vector<l3d_camera> cams(n_views);
-    std::vector<uint32_t> m(n_views);
-    std::vector<const float*> seg(n_views);
-    for (uint32_t k = 0; k < n_views; ++k) {
-        auto f = c->views.find(camIDs[k]);
-        if (f == c->views.end()) return fail(L3D_ERR_ARG, "unknown camera ID");
-        cams[k] = camera_of(*f->second);
-        m[k] = f->second->M; seg[k] = f->second->segs.data();
-    }
-    std::vector<double> P6; std::vector<uint32_t> line;
-    context_segments(c, P6, line);
-    if (int rc = check_model("context's", line.size(), P6.data(), line.data())) return rc;
-    const Job J{(uint32_t)line.size(), P6.data(), line.data(), n_views, cams.data(), m.data(), seg.data()};
+    ContextViews V; Job J;
+    if (int rc = context_job(c, n_views, camIDs, nullptr, V, J)) return rc;
     const Outputs o{out_cams, summaries, out_assoc, trace};
     double ctr[3], diag; bool done;
     if (int rc = prepare(J, *params, o, ctr, diag, done)) return rc;
@@ -449,7 +394,7 @@ int l3d_refine_view_cameras(l3d_ctx* c, uint32_t n_views, const uint32_t* camIDs
         if (timed) g_pose_kernel_ns.store((uint64_t)((double)ms * 1e6), std::memory_order_relaxed);
     }
     offsets[0] = 0;
-    for (uint32_t k = 0; k < n_views; ++k) offsets[k + 1] = offsets[k] + m[k];
+    for (uint32_t k = 0; k < n_views; ++k) offsets[k + 1] = offsets[k] + V.m[k];
     return L3D_OK;
 }
 

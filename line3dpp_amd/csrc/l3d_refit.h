@@ -1,6 +1,7 @@
 // l3d_refit.h -- the 3D lines refit against cameras and their 2D segments, shared by the host stage
 // (l3d_refit.hip) and the kernels (k_refit.hip): the records of the two new kernels, the span of a 2D end point along a
-// carrier as one function for the device and the host hook, and the sweep of stage 9.
+// carrier as one function for the device and the host hook, and the sweep of stage 9.  Behind them the host pieces that
+// the joint bundle of §29 runs too: the observation list, the lines cut anew, the skeleton of a result.
 #pragma once
 #include <algorithm>
 #include <vector>
@@ -106,13 +107,14 @@ struct RefitObsArgs {
 hipError_t launch_refit_obs(const RefitObsArgs& a, hipStream_t st);
 hipError_t launch_refit_spans(const RefitObsArgs& a, hipStream_t st);
 
-// ---- host (l3d_refit.hip): stages 1 to 3, shared with the joint bundle of DESIGN §29 (l3d_bundle.hip) ----
-struct ProjWork;               // l3d_ctx.h
+// ---- host (l3d_refit.hip): what the refit shares with the joint bundle of DESIGN §29 (l3d_bundle.hip) ----
+struct ProjWork; struct KernelTimer;             // l3d_ctx.h
+// a call's model, its cameras and every camera's 2D segments (of §27's entries too)
 struct RefitJob {
     uint32_t n_model; const double* segs; const uint32_t* line;
     uint32_t n_cams; const l3d_camera* cams; const uint32_t* n_seg; const float* const* seg;
 };
-// What the stages leave behind.  On the device (offsets into w.d, kept until the caller overwrites them): the model as
+// What stages 1 to 3 leave behind.  On the device (offsets into w.d, kept until the caller overwrites them): the model as
 // given at o_P, its line indices at o_line, every camera's float4 segments at o_segs, their first indices [n_cams + 1]
 // at o_begin, the flat 2D segment of every observation at o_oseg; the caller's own tables go at keep_end and behind, up
 // to `bound` = up256(keep_end) + tail_bytes, which w.h and w.d hold.
@@ -125,16 +127,17 @@ struct RefitObserved {
     std::vector<uint32_t> oseg, oline;           // [n_obs] in flat order: the flat 2D segment, the line
     std::vector<uint32_t> obs_off, csr;          // [n_lines + 1]; [n_obs] the observation at a CSR position
 };
-// Arguments already checked; model, cameras and 2D segments non-empty.  `who` opens the messages ("refit", "bundle");
-// ms_assoc / ms_list (may be null): the time of the launches of stage 2 and of stage 3.
+// Stages 1 to 3.  Arguments already checked; model, cameras and 2D segments non-empty.  `who` opens the messages ("refit",
+// "bundle"); ms_assoc / ms_list (may be null): the time of the launches of stage 2 and of stage 3.
 int refit_observe(ProjWork& w, hipStream_t st, const RefitJob& J, double max_distance, double min_cos2, double min_overlap, double near_plane,
                   uint32_t use_ambiguous, uint32_t n_lines, size_t tail_bytes, const char* who, float* ms_assoc, float* ms_list,
                   RefitObserved& O);
+// The observation records in CSR order, {camera, segment in its camera, line, 0, 0, 0}, and the list cut into cells --
+// (line, camera) pairs: within a line the observations come in ascending flat index, so a camera's are neighbours.  A
+// line's views are its cells.
+struct RefitCells { std::vector<uint32_t> cell_off, cell_line, cell_cam, line_cell_off; };   // [n_cells + 1], [n_cells] x 2, [n_lines + 1]
+void refit_list_observations(const RefitObserved& O, uint32_t n_lines, std::vector<l3d_refit_observation>& obs, RefitCells& cells);
 
-// the near plane, the cameras' sides and entries as stage 1 checks them, and the form of K that LoCam can hold
-int check_refit_cameras(uint32_t n_cams, const l3d_camera* cams, double near_plane);
-// midpoint c and diagonal of the bounding box of the n > 0 segments' end points (§23's)
-void refit_bounding_box(size_t n, const double* segs, double c[3], double& diag);
 // LoCam of a camera about the centre c
 LoCam refit_lo_camera(const l3d_camera& cam, const double c[3]);
 // The model's side of a call: the lines' segments in input order (a stable counting sort by line index)
@@ -153,5 +156,89 @@ struct ModelLines {
 
 // the checks of the entries of §28 and §29 behind their parameters (messages and order as §28 lists them)
 int refit_check_job(const RefitJob& J, double near_plane, double c[3], ModelLines& ml, uint64_t& n_seg);
+
+// Stages 8 and 9 for the lines of `cuts`, in their order.  The caller has enqueued the uploads of the carriers (and of the
+// LoCams, where they are new) that oa names; here k_refit_spans runs under the caller's timer, the spans come down to
+// `down` (oa.n_obs of them, the pinned place of oa.spans) and, after one synchronisation, every line's observations take
+// their valid / s_lo / s_hi, refit_sweep cuts the line and its pieces (M + s u) + c are appended.  A line without a
+// carrier is unusable: its observations keep valid = 0, s_lo = s_hi = 0 and it gets no sweep.
+struct RefitPieces {                             // of the lines cut anew: line l's n[l] pieces are xyz[6 * off[l] ..], 6 doubles each
+    std::vector<double> xyz;
+    std::vector<uint32_t> off, n;                // [n_lines] (0, 0 for a line that was not cut or kept no piece)
+    explicit RefitPieces(uint32_t n_lines) : off(n_lines, 0), n(n_lines, 0) {}
+};
+struct RefitCut {
+    uint32_t line, obs0, span0, n;               // its n observations are obs[obs0 ..], their spans down[span0 ..]
+    const double* carrier;                       // M, u about the centre; null: unusable
+};
+int refit_cut_lines(hipStream_t st, KernelTimer& timer, const RefitObsArgs& oa, RefitSpan* down, const std::vector<RefitCut>& cuts,
+                    uint32_t n_cams, uint32_t visibility, double min_length, const double c[3], const char* who,
+                    std::vector<l3d_refit_observation>& obs, RefitPieces& pieces);
+
+// What the results of §28 and §29 share: the output model, the observations and the associations, and per line -- under
+// the same names in l3d_refit_line and l3d_bundle_line -- status, n_observations, n_views, n_pieces, P1, P2
+struct RefitModel {
+    std::vector<double> segs;                    // the output model
+    std::vector<uint32_t> seg_line;
+    std::vector<uint32_t> seg_off;               // [n_lines + 1] where a line's segments begin in it
+    std::vector<l3d_refit_observation> obs;      // line after line
+    std::vector<uint32_t> obs_off;               // [n_lines + 1]
+    std::vector<l3d_association> assoc;
+};
+template <class Line, class Summary> struct LinesResult : RefitModel {
+    std::vector<Line> lines;
+    Summary sum{};
+};
+
+// every line as given: `empty` without a segment, else `given` with its carrier
+template <class Line, class Summary>
+void lines_as_given(const RefitJob& J, const ModelLines& ml, uint32_t empty, uint32_t given, LinesResult<Line, Summary>& R) {
+    R.lines.assign(ml.n_lines, Line{});
+    for (uint32_t l = 0; l < ml.n_lines; ++l) {
+        Line& L = R.lines[l];
+        if (ml.off[l] == ml.off[l + 1]) { L.status = empty; continue; }
+        L.status = given;
+        const double* a = J.segs + 6 * (size_t)ml.seg[ml.off[l]];
+        const double* b = J.segs + 6 * (size_t)ml.seg[ml.off[l + 1] - 1] + 3;
+        for (int k = 0; k < 3; ++k) { L.P1[k] = a[k]; L.P2[k] = b[k]; }
+    }
+    R.obs_off.assign((size_t)ml.n_lines + 1, 0);
+}
+
+// Stage 10: the output model and the summary's counts from the lines' statuses: the pieces of a line that was cut `anew`,
+// every other line's segments as given in input order
+template <class Line, class Summary>
+void assemble(const RefitJob& J, const ModelLines& ml, const RefitPieces& pieces, uint32_t anew, LinesResult<Line, Summary>& R) {
+    R.segs.clear(); R.seg_line.clear();
+    R.seg_off.assign((size_t)ml.n_lines + 1, 0);
+    R.sum.n_lines = ml.n_lines;
+    R.sum.n_segments_before = J.n_model;
+    for (uint32_t l = 0; l < ml.n_lines; ++l) {
+        Line& L = R.lines[l];
+        if (L.status == anew) {
+            const auto first = pieces.xyz.begin() + 6 * (size_t)pieces.off[l];
+            R.segs.insert(R.segs.end(), first, first + 6 * (size_t)pieces.n[l]);
+            R.seg_line.insert(R.seg_line.end(), pieces.n[l], l);
+        } else {
+            for (uint32_t k = ml.off[l]; k < ml.off[l + 1]; ++k) {
+                R.segs.insert(R.segs.end(), J.segs + 6 * (size_t)ml.seg[k], J.segs + 6 * (size_t)ml.seg[k] + 6);
+                R.seg_line.push_back(l);
+            }
+        }
+        R.seg_off[l + 1] = (uint32_t)R.seg_line.size();
+        L.n_pieces = R.seg_off[l + 1] - R.seg_off[l];
+        ++R.sum.n_status[L.status];
+    }
+    R.sum.n_segments_after = R.seg_line.size();
+}
+
+// the lines of a result that were cut anew, with their carriers: what context_take_lines (l3d_ctx.h) puts into a context
+struct NewLine { uint32_t line; const double *P1, *P2; };
+template <class Line> std::vector<NewLine> lines_cut_anew(const std::vector<Line>& lines, uint32_t anew) {
+    std::vector<NewLine> out;
+    for (uint32_t l = 0; l < lines.size(); ++l)
+        if (lines[l].status == anew) out.push_back(NewLine{l, lines[l].P1, lines[l].P2});
+    return out;
+}
 
 }  // namespace l3d

@@ -30,22 +30,8 @@ std::atomic<uint64_t> g_refit_observations{0}, g_refit_lines_solved{0}, g_refit_
 
 using namespace l3d;
 
-namespace {
-
-struct RefitResult {
-    std::vector<double> segs;                    // the output model
-    std::vector<uint32_t> seg_line;
-    std::vector<uint32_t> seg_off;               // [n_lines + 1] where a line's segments begin in it
-    std::vector<l3d_refit_line> lines;
-    std::vector<l3d_refit_observation> obs;      // line after line
-    std::vector<uint32_t> obs_off;               // [n_lines + 1]
-    std::vector<l3d_association> assoc;
-    l3d_refit_summary sum{};
-};
-
-}  // namespace
-
-struct l3d_refit { RefitResult r; };
+struct l3d_refit { LinesResult<l3d_refit_line, l3d_refit_summary> r; };
+using RefitResult = decltype(l3d_refit::r);
 
 namespace {
 
@@ -67,37 +53,9 @@ int check_params(const l3d_refit_params* p) {
 
 using Job = RefitJob;
 
-l3d_association no_association() { return l3d_association{-1, 0xFFFFFFFFu, 0xFFFFFFFFu, 0.0f, 0.0f, 0u}; }
-
 }  // namespace
 
 namespace l3d {
-
-// the near plane, the cameras' sides and entries as stage 1 checks them, and the form of K that LoCam can hold
-int check_refit_cameras(uint32_t n_cams, const l3d_camera* cams, double near_plane) {
-    if (int rc = check_projection_cameras(n_cams, cams, near_plane)) return rc;
-    for (uint32_t c = 0; c < n_cams; ++c) {
-        const double* K = cams[c].K;
-        if (!(K[3] == 0.0 && K[6] == 0.0 && K[7] == 0.0 && K[8] == 1.0 && K[0] != 0.0 && K[4] != 0.0))
-            return fail(L3D_ERR_ARG, "camera " + std::to_string(c) + ": K must be upper triangular with K22 = 1 and K00, K11 not 0");
-        if (K[1] != 0.0) return fail(L3D_ERR_ARG, "camera " + std::to_string(c) + ": K01 must be 0 (no skew)");
-    }
-    return L3D_OK;
-}
-
-// midpoint c and diagonal of the bounding box of the n > 0 segments' end points (§23's)
-void refit_bounding_box(size_t n, const double* segs, double c[3], double& diag) {
-    double lo[3] = {segs[0], segs[1], segs[2]}, hi[3] = {segs[0], segs[1], segs[2]};
-    for (size_t i = 0; i < 2 * n; ++i)
-        for (int k = 0; k < 3; ++k) {
-            const double v = segs[3 * i + k];
-            if (v < lo[k]) lo[k] = v;
-            if (v > hi[k]) hi[k] = v;
-        }
-    double e[3];
-    for (int k = 0; k < 3; ++k) { c[k] = (lo[k] + hi[k]) * 0.5; e[k] = hi[k] - lo[k]; }
-    diag = std::sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
-}
 
 // LoCam of a camera about the centre c: R, C = Q - c with Q_i = -((R_0i t0 + R_1i t1) + R_2i t2), and K's four entries
 LoCam refit_lo_camera(const l3d_camera& cam, const double c[3]) {
@@ -113,20 +71,12 @@ LoCam refit_lo_camera(const l3d_camera& cam, const double c[3]) {
 int refit_check_job(const RefitJob& J, double near_plane, double c[3], ModelLines& ml, uint64_t& n_seg) {
     for (uint32_t i = 0; i < J.n_model; ++i)
         if (J.line[i] >= 0x80000000u) return fail(L3D_ERR_LIMIT, "segment " + std::to_string(i) + " has a line index of 2^31 or more");
-    if (int rc = check_refit_cameras(J.n_cams, J.cams, near_plane)) return rc;
-    n_seg = 0;
-    for (uint32_t k = 0; k < J.n_cams; ++k) n_seg += J.n_seg[k];
-    if (n_seg >= ((uint64_t)1 << 32)) return fail(L3D_ERR_LIMIT, "2^32 or more segments in total");
-    for (uint32_t k = 0; k < J.n_cams; ++k) {
-        if (J.n_seg[k] && !J.seg[k]) return fail(L3D_ERR_ARG, "null argument");
-        for (size_t i = 0; i < 4 * (size_t)J.n_seg[k]; ++i)
-            if (!std::isfinite(J.seg[k][i]))
-                return fail(L3D_ERR_ARG, "camera " + std::to_string(k) + ": segment " + std::to_string(i / 4) + " has a non-finite entry");
-    }
+    if (int rc = check_pose_cameras(J.n_cams, J.cams, near_plane, true)) return rc;
+    if (int rc = check_camera_segments(J.n_cams, J.n_seg, J.seg, n_seg)) return rc;
     c[0] = c[1] = c[2] = 0.0;
     if (J.n_model) {
         double diag;
-        refit_bounding_box(J.n_model, J.segs, c, diag);
+        bounding_box(J.n_model, J.segs, c, diag);
         if (!(diag > 0.0)) return fail(L3D_ERR_ARG, "the model's bounding box is a point");
     }
     ml.build(J.n_model, J.line);
@@ -281,49 +231,64 @@ int refit_observe(ProjWork& w, hipStream_t st, const RefitJob& J, double max_dis
     return L3D_OK;
 }
 
+void refit_list_observations(const RefitObserved& O, uint32_t n_lines, std::vector<l3d_refit_observation>& obs, RefitCells& cells) {
+    obs.resize(O.n_obs);
+    cells = RefitCells{};
+    cells.cell_off.reserve((size_t)O.n_obs + 1); cells.cell_line.reserve(O.n_obs); cells.cell_cam.reserve(O.n_obs);
+    cells.line_cell_off.assign((size_t)n_lines + 1, 0);
+    for (uint32_t l = 0; l < n_lines; ++l) {
+        uint32_t last_cam = 0xFFFFFFFFu;
+        for (uint32_t r = O.obs_off[l]; r < O.obs_off[l + 1]; ++r) {
+            const uint32_t flat = O.oseg[O.csr[r]];
+            const uint32_t cam = (uint32_t)(std::upper_bound(O.seg_begin.begin(), O.seg_begin.end(), flat) - O.seg_begin.begin()) - 1;
+            if (cam != last_cam) {
+                cells.cell_off.push_back(r);
+                cells.cell_line.push_back(l); cells.cell_cam.push_back(cam);
+                last_cam = cam;
+            }
+            obs[r] = l3d_refit_observation{cam, flat - O.seg_begin[cam], l, 0u, 0.0, 0.0};
+        }
+        cells.line_cell_off[l + 1] = (uint32_t)cells.cell_line.size();
+    }
+    cells.cell_off.push_back(O.n_obs);
+}
+
+int refit_cut_lines(hipStream_t st, KernelTimer& timer, const RefitObsArgs& oa, RefitSpan* down, const std::vector<RefitCut>& cuts,
+                    uint32_t n_cams, uint32_t visibility, double min_length, const double c[3], const char* who,
+                    std::vector<l3d_refit_observation>& obs, RefitPieces& pieces) {
+    // stage 8: spans
+    hipError_t e = timer.start(st);
+    if (e == hipSuccess) e = launch_refit_spans(oa, st);
+    if (e == hipSuccess) e = timer.stop(st);
+    if (e == hipSuccess) e = hipMemcpyAsync(down, oa.spans, sizeof(RefitSpan) * oa.n_obs, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(L3D_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    timer.add();
+    // stage 9: extents
+    std::vector<uint32_t> cam_open(n_cams, 0), cams_v;
+    std::vector<double> lo_v, hi_v, cut;
+    for (const RefitCut& k : cuts) {
+        if (!k.carrier) continue;
+        lo_v.clear(); hi_v.clear(); cams_v.clear(); cut.clear();
+        for (uint32_t i = 0; i < k.n; ++i) {
+            l3d_refit_observation& ob = obs[k.obs0 + i];
+            const RefitSpan& sp = down[k.span0 + i];
+            ob.valid = sp.valid; ob.s_lo = sp.valid ? sp.lo : 0.0; ob.s_hi = sp.valid ? sp.hi : 0.0;
+            if (ob.valid) { lo_v.push_back(sp.lo); hi_v.push_back(sp.hi); cams_v.push_back(ob.camera); }
+        }
+        const double* M = k.carrier; const double* u = M + 3;
+        const double u_norm = std::sqrt((u[0] * u[0] + u[1] * u[1]) + u[2] * u[2]);
+        refit_sweep((uint32_t)lo_v.size(), lo_v.data(), hi_v.data(), cams_v.data(), visibility, min_length, u_norm, cam_open, cut);
+        pieces.off[k.line] = (uint32_t)(pieces.xyz.size() / 6); pieces.n[k.line] = (uint32_t)(cut.size() / 2);
+        for (size_t j = 0; j < cut.size(); ++j)
+            for (int i = 0; i < 3; ++i) pieces.xyz.push_back((M[i] + cut[j] * u[i]) + c[i]);
+    }
+    return L3D_OK;
+}
+
 }  // namespace l3d
 
 namespace {
-
-// Stage 10: the output model and the summary from the lines' statuses and the REFIT lines' pieces (piece_off [n_lines + 1]
-// into pieces, 6 doubles each)
-void assemble(const Job& J, const ModelLines& ml, const std::vector<uint32_t>& piece_off, const std::vector<double>& pieces, RefitResult& R) {
-    R.segs.clear(); R.seg_line.clear();
-    R.seg_off.assign((size_t)ml.n_lines + 1, 0);
-    R.sum.n_lines = ml.n_lines;
-    R.sum.n_segments_before = J.n_model;
-    for (uint32_t l = 0; l < ml.n_lines; ++l) {
-        l3d_refit_line& L = R.lines[l];
-        if (L.status == L3D_REFIT_REFIT) {
-            R.segs.insert(R.segs.end(), pieces.begin() + 6 * (size_t)piece_off[l], pieces.begin() + 6 * (size_t)piece_off[l + 1]);
-            R.seg_line.insert(R.seg_line.end(), piece_off[l + 1] - piece_off[l], l);
-            R.sum.cost0 += L.cost0; R.sum.cost1 += L.cost1;
-        } else {
-            for (uint32_t k = ml.off[l]; k < ml.off[l + 1]; ++k) {
-                R.segs.insert(R.segs.end(), J.segs + 6 * (size_t)ml.seg[k], J.segs + 6 * (size_t)ml.seg[k] + 6);
-                R.seg_line.push_back(l);
-            }
-        }
-        R.seg_off[l + 1] = (uint32_t)R.seg_line.size();
-        L.n_pieces = R.seg_off[l + 1] - R.seg_off[l];
-        ++R.sum.n_status[L.status];
-    }
-    R.sum.n_segments_after = R.seg_line.size();
-}
-
-// every line as given: EMPTY without a segment, else TOO_FEW_VIEWS with its carrier
-void lines_as_given(const Job& J, const ModelLines& ml, RefitResult& R) {
-    R.lines.assign(ml.n_lines, l3d_refit_line{});
-    for (uint32_t l = 0; l < ml.n_lines; ++l) {
-        l3d_refit_line& L = R.lines[l];
-        if (ml.off[l] == ml.off[l + 1]) { L.status = L3D_REFIT_EMPTY; continue; }
-        L.status = L3D_REFIT_TOO_FEW_VIEWS;
-        const double* a = J.segs + 6 * (size_t)ml.seg[ml.off[l]];
-        const double* b = J.segs + 6 * (size_t)ml.seg[ml.off[l + 1] - 1] + 3;
-        for (int k = 0; k < 3; ++k) { L.P1[k] = a[k]; L.P2[k] = b[k]; }
-    }
-    R.obs_off.assign((size_t)ml.n_lines + 1, 0);
-}
 
 bool finite4(const double* x) { return std::isfinite(x[0]) && std::isfinite(x[1]) && std::isfinite(x[2]) && std::isfinite(x[3]); }
 
@@ -348,33 +313,27 @@ int refit_core(ProjWork& w, hipStream_t st, const Job& J, const l3d_refit_params
     auto hip_fail = [](hipError_t e) { return fail(L3D_ERR_HIP, std::string("refit: ") + hipGetErrorString(e)); };
     char* h = w.h.p; char* d = w.d.p;
     hipError_t e = hipSuccess;
-    const std::vector<uint32_t>& seg_begin = O.seg_begin;
-    const std::vector<uint32_t>&oseg = O.oseg, &csr = O.csr;
+    const std::vector<uint32_t>& csr = O.csr;
     const size_t o_segs = O.o_segs, o_begin = O.o_begin, o_oseg = O.o_oseg, keep_end = O.keep_end, sol_bound = O.bound;
     const uint32_t n_obs = O.n_obs;
     g_refit_observations.store(n_obs, std::memory_order_relaxed);
     R.assoc = std::move(O.assoc);
     R.sum.n_ambiguous_left_out = O.n_ambiguous_left_out;
     R.sum.n_observations = n_obs;
-    lines_as_given(J, ml, R);
+    lines_as_given(J, ml, L3D_REFIT_EMPTY, L3D_REFIT_TOO_FEW_VIEWS, R);
     R.obs_off = O.obs_off;
-    std::vector<uint32_t>& obs_off = R.obs_off;
-    R.obs.resize(n_obs);
+    const std::vector<uint32_t>& obs_off = R.obs_off;
+    RefitCells cells;
+    refit_list_observations(O, n_lines, R.obs, cells);
     const uint32_t need = std::max<uint32_t>(2u, p.visibility);
     std::vector<uint32_t> sol;                   // the lines handed to the solver, ascending
     std::vector<uint32_t> res_off(1, 0u), perm;
     std::vector<double> x0, carrier0;            // [4 x solved], [6 x solved] the centred carriers as given
     for (uint32_t l = 0; l < n_lines; ++l) {
         l3d_refit_line& L = R.lines[l];
-        uint32_t views = 0, last_cam = 0xFFFFFFFFu;
-        for (uint32_t r = obs_off[l]; r < obs_off[l + 1]; ++r) {
-            const uint32_t flat = oseg[csr[r]];
-            const uint32_t cam = (uint32_t)(std::upper_bound(seg_begin.begin(), seg_begin.end(), flat) - seg_begin.begin()) - 1;
-            if (cam != last_cam) { ++views; last_cam = cam; }
-            R.obs[r] = l3d_refit_observation{cam, flat - seg_begin[cam], l, 0u, 0.0, 0.0};
-        }
-        L.n_observations = obs_off[l + 1] - obs_off[l]; L.n_views = views;
-        if (L.status == L3D_REFIT_EMPTY || views < need) continue;
+        L.n_observations = obs_off[l + 1] - obs_off[l];
+        L.n_views = cells.line_cell_off[l + 1] - cells.line_cell_off[l];
+        if (L.status == L3D_REFIT_EMPTY || L.n_views < need) continue;
         double q[6];
         for (int k = 0; k < 3; ++k) { q[k] = L.P1[k] - c[k]; q[3 + k] = L.P2[k] - c[k]; }
         if (line_to_cayley(d3{q[0], q[1], q[2]}, d3{q[3], q[4], q[5]}, L.x0)) {
@@ -390,8 +349,7 @@ int refit_core(ProjWork& w, hipStream_t st, const Job& J, const l3d_refit_params
         res_off.push_back((uint32_t)perm.size());
     }
     const uint32_t ns = (uint32_t)sol.size(), no = (uint32_t)perm.size();
-    std::vector<uint32_t> piece_off((size_t)n_lines + 1, 0);
-    std::vector<double> pieces;
+    RefitPieces pieces(n_lines);
     if (ns) {
         // stages 4 and 6: the solver's tables in the place of the group's
         std::vector<uint32_t> order(ns);
@@ -431,10 +389,11 @@ int refit_core(ProjWork& w, hipStream_t st, const Job& J, const l3d_refit_params
         // stage 7: write-back
         const LoOut* res = (const LoOut*)(h + o_res);
         double* car = (double*)(h + o_car);
-        std::vector<char> failed(ns, 1);
+        std::vector<RefitCut> cuts(ns);              // (a line stays without a carrier where the solve failed)
         for (uint32_t s = 0; s < ns; ++s) {
             l3d_refit_line& L = R.lines[sol[s]];
             const LoOut& o = res[s];
+            cuts[s] = RefitCut{sol[s], obs_off[sol[s]], res_off[s], res_off[s + 1] - res_off[s], nullptr};
             std::memcpy(L.x, o.x, 32);
             L.cost0 = o.cost0; L.cost1 = o.cost1; L.iterations = o.iters; L.solver_status = o.status;
             for (int k = 0; k < 6; ++k) car[6 * (size_t)s + k] = 0.0;
@@ -445,55 +404,24 @@ int refit_core(ProjWork& w, hipStream_t st, const Job& J, const l3d_refit_params
             const double a[3] = {P1.x, P1.y, P1.z}, b[3] = {P2.x, P2.y, P2.z};
             if (!(std::isfinite(a[0]) && std::isfinite(a[1]) && std::isfinite(a[2]) && std::isfinite(b[0]) && std::isfinite(b[1]) && std::isfinite(b[2])))
                 continue;
-            failed[s] = 0;
+            cuts[s].carrier = car + 6 * (size_t)s;
             for (int k = 0; k < 3; ++k) {
                 car[6 * (size_t)s + k] = a[k] * 0.5 + b[k] * 0.5;
                 car[6 * (size_t)s + 3 + k] = (a[k] - b[k]) * 0.5;
                 L.P1[k] = a[k] + c[k]; L.P2[k] = b[k] + c[k];
             }
         }
-        // stage 8: spans
+        // stages 8 and 9: the lines cut anew on the carriers written back
         e = hipMemcpyAsync(d + o_car, h + o_car, 48 * (size_t)ns, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = t_spans.start(st);
-        if (e == hipSuccess) e = launch_refit_spans(oa, st);
-        if (e == hipSuccess) e = t_spans.stop(st);
-        if (e == hipSuccess) e = hipMemcpyAsync(h + o_span, d + o_span, sizeof(RefitSpan) * no, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
         if (e != hipSuccess) return hip_fail(e);
-        t_spans.add();
-        // stage 9: extents
-        const RefitSpan* span = (const RefitSpan*)(h + o_span);
-        std::vector<uint32_t> cam_open(n_cams, 0), cams_v;
-        std::vector<double> lo_v, hi_v, cut;
-        for (uint32_t s = 0; s < ns; ++s) {
-            const uint32_t l = sol[s];
-            l3d_refit_line& L = R.lines[l];
-            piece_off[l] = (uint32_t)(pieces.size() / 6);
-            lo_v.clear(); hi_v.clear(); cams_v.clear(); cut.clear();
-            for (uint32_t r = res_off[s]; r < res_off[s + 1]; ++r) {
-                l3d_refit_observation& ob = R.obs[obs_off[l] + (r - res_off[s])];
-                const RefitSpan& sp = span[r];
-                ob.valid = failed[s] ? 0u : sp.valid; ob.s_lo = ob.valid ? sp.lo : 0.0; ob.s_hi = ob.valid ? sp.hi : 0.0;
-                if (ob.valid) { lo_v.push_back(sp.lo); hi_v.push_back(sp.hi); cams_v.push_back(ob.camera); }
-            }
-            if (failed[s]) continue;
-            const double* M = car + 6 * (size_t)s; const double* u = M + 3;
-            const double u_norm = std::sqrt((u[0] * u[0] + u[1] * u[1]) + u[2] * u[2]);
-            refit_sweep((uint32_t)lo_v.size(), lo_v.data(), hi_v.data(), cams_v.data(), p.visibility, p.min_length, u_norm, cam_open, cut);
-            L.status = cut.empty() ? L3D_REFIT_NO_EXTENT : L3D_REFIT_REFIT;
-            for (size_t k = 0; k < cut.size(); ++k)
-                for (int i = 0; i < 3; ++i) pieces.push_back((M[i] + cut[k] * u[i]) + c[i]);
-        }
+        if (int rc = refit_cut_lines(st, t_spans, oa, (RefitSpan*)(h + o_span), cuts, n_cams, p.visibility, p.min_length, c, "refit", R.obs, pieces))
+            return rc;
+        for (const RefitCut& k : cuts)
+            if (k.carrier) R.lines[k.line].status = pieces.n[k.line] ? L3D_REFIT_REFIT : L3D_REFIT_NO_EXTENT;
     }
-    // (piece_off of the lines that were not solved: where the next solved line begins)
-    {
-        uint32_t at = (uint32_t)(pieces.size() / 6);
-        std::vector<char> is_sol(n_lines, 0);
-        for (uint32_t l : sol) is_sol[l] = 1;
-        piece_off[n_lines] = at;
-        for (uint32_t l = n_lines; l-- > 0;) { if (is_sol[l]) at = piece_off[l]; else piece_off[l] = at; }
-    }
-    assemble(J, ml, piece_off, pieces, R);
+    assemble(J, ml, pieces, L3D_REFIT_REFIT, R);
+    for (const l3d_refit_line& L : R.lines)
+        if (L.status == L3D_REFIT_REFIT) { R.sum.cost0 += L.cost0; R.sum.cost1 += L.cost1; }
     return L3D_OK;
 }
 
@@ -505,9 +433,9 @@ int prepare(const Job& J, const l3d_refit_params& p, double c[3], ModelLines& ml
     if (int rc = refit_check_job(J, p.near_plane, c, ml, n_seg)) return rc;
     if (J.n_model && J.n_cams && n_seg) { done = false; return L3D_OK; }
     // an empty model, no camera or no 2D segment: every line as given
-    lines_as_given(J, ml, R);
+    lines_as_given(J, ml, L3D_REFIT_EMPTY, L3D_REFIT_TOO_FEW_VIEWS, R);
     R.assoc.assign((size_t)n_seg, no_association());
-    assemble(J, ml, std::vector<uint32_t>((size_t)ml.n_lines + 1, 0), std::vector<double>(), R);
+    assemble(J, ml, RefitPieces(ml.n_lines), L3D_REFIT_REFIT, R);
     return L3D_OK;
 }
 
@@ -527,13 +455,8 @@ int l3d_refit_segments(int device, uint32_t n_segments, const double* segs6, con
     if (int rc = check_params(params)) return rc;
     if (!out) return fail(L3D_ERR_ARG, "null argument");
     if (int rc = check_model(nullptr, n_segments, segs6, line)) return rc;
-    if (n_cams && (!cams || !n_segments_per_cam)) return fail(L3D_ERR_ARG, "null argument");
-    uint64_t n_seg = 0;
-    for (uint32_t k = 0; k < n_cams; ++k) n_seg += n_segments_per_cam[k];
-    if (n_seg && !segs4) return fail(L3D_ERR_ARG, "null argument");
-    std::vector<const float*> seg(n_cams);
-    uint64_t at = 0;
-    for (uint32_t k = 0; k < n_cams; ++k) { seg[k] = segs4 ? segs4 + 4 * at : nullptr; at += n_segments_per_cam[k]; }
+    std::vector<const float*> seg;
+    if (int rc = camera_segments(n_cams, cams, n_segments_per_cam, segs4, seg)) return rc;
     const Job J{n_segments, segs6, line, n_cams, cams, n_segments_per_cam, seg.data()};
     auto rf = std::make_unique<l3d_refit>();
     double c[3]; bool done; ModelLines ml;
@@ -555,22 +478,8 @@ int l3d_refit_view_lines(l3d_ctx* c, uint32_t n_views, const uint32_t* camIDs, c
     if (int rc = check_params(params)) return rc;
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     if (int rc = lines_ready(c, "lines are refit", "refit")) return rc;
-    std::vector<uint32_t> sorted(camIDs, camIDs + n_views);
-    std::sort(sorted.begin(), sorted.end());
-    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return fail(L3D_ERR_ARG, "a camera ID is named twice");
-    std::vector<l3d_camera> cams(n_views);
-    std::vector<uint32_t> m(n_views);
-    std::vector<const float*> seg(n_views);
-    for (uint32_t k = 0; k < n_views; ++k) {
-        auto f = c->views.find(camIDs[k]);
-        if (f == c->views.end()) return fail(L3D_ERR_ARG, "unknown camera ID");
-        cams[k] = cams_in ? cams_in[k] : camera_of(*f->second);
-        m[k] = f->second->M; seg[k] = f->second->segs.data();
-    }
-    std::vector<double> P6; std::vector<uint32_t> line;
-    context_segments(c, P6, line);
-    if (int rc = check_model("context's", line.size(), P6.data(), line.data())) return rc;
-    const Job J{(uint32_t)line.size(), P6.data(), line.data(), n_views, cams.data(), m.data(), seg.data()};
+    ContextViews V; Job J;
+    if (int rc = context_job(c, n_views, camIDs, cams_in, V, J)) return rc;
     auto rf = std::make_unique<l3d_refit>();
     RefitResult& R = rf->r;
     double ctr[3]; bool done; ModelLines ml;
@@ -583,24 +492,7 @@ int l3d_refit_view_lines(l3d_ctx* c, uint32_t n_views, const uint32_t* camIDs, c
         if (timed) store_kernel_time(ms);
     }
     // the refit model takes the place of lines3D_: the REFIT lines change, every other line is untouched
-    auto seg3 = [](const double* a, const double* b) {
-        const d3 P1{a[0], a[1], a[2]}, P2{b[0], b[1], b[2]};
-        ReconSeg3D s = segment3d(P1, P2);
-        s.P1 = P1; s.P2 = P2;
-        return s;
-    };
-    for (uint32_t l = 0; l < ml.n_lines; ++l) {
-        const l3d_refit_line& rl = R.lines[l];
-        if (rl.status != L3D_REFIT_REFIT) continue;
-        ReconLine& L = c->lines3D[l];
-        L.collinear.clear();
-        for (uint32_t k = R.seg_off[l]; k < R.seg_off[l + 1]; ++k) L.collinear.push_back(seg3(&R.segs[6 * (size_t)k], &R.segs[6 * (size_t)k + 3]));
-        L.cluster_seg = seg3(rl.P1, rl.P2);
-        L.residuals.clear();
-        for (uint32_t r = R.obs_off[l]; r < R.obs_off[l + 1]; ++r) L.residuals.emplace_back(camIDs[R.obs[r].camera], R.obs[r].segment);
-    }
-    if (R.sum.n_status[L3D_REFIT_REFIT]) {                 // (else the model is what it was, bit for bit, and so is its name)
-        c->proj_records.clear();                           // (they hold the lines as they were)
+    if (context_take_lines(c, camIDs, R, lines_cut_anew(R.lines, L3D_REFIT_REFIT))) {   // (else the model is what it was, bit for bit, and so is its name)
         c->lines_refit = true;
         c->refit_distance = params->max_distance;
     }

@@ -388,3 +388,9 @@ def test_empty_forms_need_no_device():
         assert len(got["cameras"]) == len(cams)
         for a, b in zip(got["cameras"], cams):
             PC.same_camera(a, b, what)
+    # a line's segments need not be neighbours: grouped by ascending line index, in input order within a line, bit for bit
+    segs = np.random.default_rng(7).uniform(-3.0, 3.0, (5, 6)); ln = np.array([2, 0, 2, 1, 0], np.uint32)
+    got = api.bundle_segments(segs, ln, [], [])
+    assert got["segments"].tobytes() == segs[[1, 4, 3, 0, 2]].tobytes() and got["line"].tolist() == [0, 0, 1, 2, 2]
+    assert got["lines"]["status"].tolist() == [BM.HELD] * 3 and got["lines"]["n_pieces"].tolist() == [2, 1, 2]
+    assert got["lines"]["P1"].tobytes() == segs[[1, 3, 0], :3].tobytes() and got["lines"]["P2"].tobytes() == segs[[4, 3, 2], 3:].tobytes()

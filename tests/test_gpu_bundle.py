@@ -249,6 +249,41 @@ def test_context_form_replaces_the_model(golden):
     assert api.flatten_lines(g.get3Dlines())[0].tobytes() == segs_now.tobytes() and "BUNDLE" not in g.outputFilename()
 
 
+def test_context_errors(golden):
+    """the context entry's refusals, which are refitLines': nothing of the context changes, neither its lines nor the
+    records of the last projection"""
+    g, ids = golden["g"], golden["cam_ids"]
+    L = _lib.load()
+
+    def records():
+        n = C.c_uint64(0)
+        assert L.l3d_get_projected_lines(g.h, None, 0, C.byref(n)) == 0
+        rec = np.zeros(max(n.value, 1), api.PROJECTED_SEGMENT_DTYPE)
+        assert L.l3d_get_projected_lines(g.h, _lib.ptr(rec), n.value, C.byref(n)) == 0
+        return rec[:n.value].tobytes()
+
+    assert sum(len(r) for r in g.projectLines([ids[0], ids[1]])) > 0
+    segs, rec = api.flatten_lines(g.get3Dlines())[0], records()
+    assert len(rec) > 0
+    for what, arg, message in (("an ID named twice", [ids[1], ids[0], ids[1]], "a camera ID is named twice"),
+                               ("an unknown ID", [ids[0], 987654], "unknown camera ID"),
+                               ("both: named twice comes first", [987654, ids[0], 987654], "a camera ID is named twice")):
+        assert g.bundleModel(arg) is None and g.last_status == -1 and _lib.last_error() == message, what
+        assert api.flatten_lines(g.get3Dlines())[0].tobytes() == segs.tobytes() and records() == rec, what
+        assert "BUNDLE" not in g.outputFilename(), what
+    # before the lines exist, and while a split call is open
+    from line3dpp_amd.scene import make_scene
+    h = Line3D()
+    h.add_scene(make_scene(4, 60, n_neighbors=2, seed=2))
+    assert h.bundleModel() is None and h.last_status == -7 and _lib.last_error().startswith("no 3D lines to bundle")
+    assert h.matchBegin()
+    par = api.bundle_params()
+    ids4 = np.arange(4, dtype=np.uint32)
+    assert L.l3d_bundle_view_lines(h.h, 4, _lib.ptr(ids4), None, None, C.byref(par), None, None) == -7 and "split call" in _lib.last_error()
+    h.matchAbort()
+    h.close()
+
+
 # ---- the C++ facade ---------------------------------------------------------------------------------------------------
 def test_facade_bundle_model(tmp_path):
     import os

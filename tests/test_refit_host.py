@@ -230,6 +230,12 @@ def test_empty_forms_need_no_device():
         sm = got["summary"]
         assert sm["n_segments_before"] == sm["n_segments_after"] == n and sm["n_observations"] == 0
         assert sm["status"]["EMPTY"] == (3 if n else 0) and sm["status"]["TOO_FEW_VIEWS"] == (9 if n else 0)
+    # a line's segments need not be neighbours: grouped by ascending line index, in input order within a line, bit for bit
+    segs = np.random.default_rng(7).uniform(-3.0, 3.0, (5, 6)); ln = np.array([2, 0, 2, 1, 0], np.uint32)
+    got = api.refit_segments(segs, ln, [], [])
+    assert got["segments"].tobytes() == segs[[1, 4, 3, 0, 2]].tobytes() and got["line"].tolist() == [0, 0, 1, 2, 2]
+    assert got["lines"]["status"].tolist() == [RM.TOO_FEW_VIEWS] * 3 and got["lines"]["n_pieces"].tolist() == [2, 1, 2]
+    assert got["lines"]["P1"].tobytes() == segs[[1, 3, 0], :3].tobytes() and got["lines"]["P2"].tobytes() == segs[[4, 3, 2], 3:].tobytes()
 
 
 # ---- the recovery figures of the model -------------------------------------------------------------------------
